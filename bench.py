@@ -11,15 +11,29 @@ once at the end of the timed region (T_render ends at the film reduce, BASELINE.
 `--gpus N` without a launcher starts N rank processes itself (torch.distributed.run as a
 child, acceleratedvolrenderer_amd/launch.py); under a launcher WORLD_SIZE must equal N.
 
-Prints ONE JSON line (rank 0) with
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up
+the scene, warms up, times the N steps, writes the film if `--dump-outputs DIR` is given and
+prints ONE JSON line (rank 0) with `value`, `ms_per_step` and
   * roofline: k_paths (the fused delta-tracking / ratio-tracking / density-fetch kernel),
     algorithmic HBM bytes per launch / its HIP-event time on the context stream, against the
-    HBM peak; `traffic` (memory-side reads priced by request size + WRITE_SIZE) and the
-    `limiter` block come from rocprofv3 PMC passes that this script runs as child processes
-    on the same configuration (N=1, --pmc auto); the fast-mode and NanoVDB legs carry the
-    same roofline block (NanoVDB's 64^3 majorant reads, served by L2, reported apart);
+    HBM peak, from the counters of the timed steps themselves.
+
+`--full` adds every measurement that takes runs of its own, after the headline's timed region
+(the headline figures are measured the same way with and without it):
+  * roofline `traffic` (memory-side reads priced by request size + WRITE_SIZE) and the
+    `limiter` block, from rocprofv3 PMC passes that this script runs as child processes
+    on the same configuration (N=1, --pmc auto);
+  * fast_mode and nanovdb: the same steps in fast mode and over the cloud as a NanoVDBMedium,
+    with the same roofline block (NanoVDB's 64^3 majorant reads, served by L2, reported apart);
   * cpu_baseline: the oracle restatement (`port`) on a bounded sample of the same
     workload, on every host core this process may use (affinity and cgroup quota).
+Without `--full` those blocks are null. `--fast-leg`, `--nanovdb-leg`, `--no-cpu-baseline` and
+`--pmc` choose among them under `--full`.
+
+`--dump-outputs DIR` writes what the timed steps leave a caller, the fp64 film sums of the
+timed region (reduced over the ranks), as DIR/<name>.npy (`dump_outputs`). The density grid,
+the camera and the sample indices depend on the arguments alone, so two builds run with the
+same arguments can be compared array for array.
 """
 import argparse
 import csv
@@ -257,8 +271,53 @@ def parse(argv=None):
                    help="after the headline (S-cloud GridMedium), time the same sample indices over the same cloud as a "
                         "NanoVDBMedium (disney-cloud's medium type; tree built on the device), reported as `nanovdb`")
     p.add_argument("--nanovdb-steps", type=int, default=8, help="timed steps of the NanoVDB leg (at most --steps)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the measurements that take runs of their own: the fast-mode and "
+                        "NanoVDB legs, the CPU baseline and the rocprofv3 counter passes (a plain run leaves their "
+                        "blocks null)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the film of the timed steps (fp64 sums; rank 0's reduced film) as DIR/<name>.npy")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run measures the headline only
+        args.fast_leg = args.nanovdb_leg = 0
+        args.no_cpu_baseline = True
+        args.pmc = "off"
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, film, width, height, nbuckets=0, seed=0):
+    """Write the exported film (avr_film_export_device layout, fp64: rgb sums, weight sums and,
+    for a SpectralFilm, bucket and bucket-weight sums per pixel) as float64 .npy files under
+    `dirname`: film_rgb_sum (H, W, 3), film_weight_sum (H, W) and spectral_bucket_sum /
+    spectral_weight_sum (H, W, nbuckets). A film over DUMP_MAX_BYTES is written as the same
+    fixed, seeded sample of pixels of every array (rows in the order of pixel_index.npy)."""
+    npix = width * height
+    host = film.detach().cpu().numpy()
+    arrays = {"film_rgb_sum": host[:3 * npix].reshape(npix, 3), "film_weight_sum": host[3 * npix:4 * npix].reshape(npix, 1)}
+    if nbuckets:
+        k = npix * nbuckets
+        arrays["spectral_bucket_sum"] = host[4 * npix:4 * npix + k].reshape(npix, nbuckets)
+        arrays["spectral_weight_sum"] = host[4 * npix + k:4 * npix + 2 * k].reshape(npix, nbuckets)
+    per_pixel = 8 * sum(a.shape[1] for a in arrays.values())
+    if per_pixel * npix > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(npix, size=keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    else:
+        arrays = {name: a.reshape((height, width) + ((a.shape[1],) if a.shape[1] > 1 else ()))
+                  for name, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def log(msg):
@@ -746,6 +805,10 @@ def main():
     # the k_paths instantiation the timed steps ran (before the fast-mode leg launches another)
     timed_kernel = integ.ctx.last_kernel() if agg.get("loop_iterations") else "k_medium"
     elapsed = max_over_ranks(elapsed, world, f"cuda:{dev}")
+    if args.dump_outputs and rank == 0 and not args.pmc_child:
+        # the film of the timed steps (before a later leg reuses the buffer)
+        names = dump_outputs(args.dump_outputs, buf, args.width, args.height, getattr(scene.film, "nbuckets", 0))
+        log(f"outputs written to {args.dump_outputs}: {', '.join(names)}")
     if args.pmc_child:
         integ.close()
         return
@@ -890,7 +953,7 @@ def main():
             host_scene = host_density = host_rgb = None
         # HBM traffic and the VALU limiter from rocprofv3 counter passes of this same
         # configuration (child processes; the guide's gfx950 rule: FETCH_SIZE x2 + WRITE_SIZE)
-        traffic, limiter, pmc_note, cache = None, None, "pmc off", None
+        traffic, limiter, pmc_note, cache = None, None, "pmc off" if args.full else "pmc off (counter passes: --full)", None
         traffic_raw = traffic_x2 = None
         want_pmc = args.pmc == "on" or (args.pmc == "auto" and world == 1)
         pmc_kernel = None
@@ -990,6 +1053,7 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",

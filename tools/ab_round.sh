@@ -13,7 +13,7 @@ done
 shift
 for spec in "$@"; do
   IFS='|' read -r tag envs args <<< "$spec"
-  env $envs timeout -k 10 400 python bench.py --no-cpu-baseline $args > $O/ab_$tag.json 2> $O/ab_$tag.err || { echo "$tag failed"; tail -5 $O/ab_$tag.err; exit 2; }
+  env $envs timeout -k 10 400 python bench.py --full --no-cpu-baseline $args > $O/ab_$tag.json 2> $O/ab_$tag.err || { echo "$tag failed"; tail -5 $O/ab_$tag.err; exit 2; }
   python - "$O" "$tag" <<'PY'
 import json, sys
 o, t = sys.argv[1], sys.argv[2]
