@@ -15,8 +15,12 @@ from .rgbspectrum import RGBToSpectrumTable
 from .integrator import VolPathIntegrator, shard_samples, INTEGRATOR_NAMES
 from . import capi
 from . import scenes
+from . import graph
+from .capi import GraphIndex
+from .graph import GraphIntegrator
 
 __all__ = ["spectra", "transform", "GridMedium", "DistantLight", "UniformInfiniteLight", "OrthographicCamera",
            "PerspectiveCamera", "RGBFilm", "Scene", "film_rgb", "VolPathIntegrator", "shard_samples",
            "INTEGRATOR_NAMES", "capi", "scenes", "HomogeneousMedium", "CloudMedium", "NanoVDBMedium", "NanoVDBGrid", "RGBGridMedium", "RGBToSpectrumTable",
-           "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler"]
+           "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler",
+           "graph", "GraphIndex", "GraphIntegrator"]

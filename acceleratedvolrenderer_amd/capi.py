@@ -207,6 +207,16 @@ SIGNATURES = {
     "avr_graph_transport": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, c_float_p]),
     "avr_graph_in_node_path_length": (ctypes.c_int, [ctypes.c_void_p, c_float_p,
                                                      ctypes.POINTER(ctypes.c_longlong)]),
+    "avr_graph_index_create": (ctypes.c_int, [ctypes.c_longlong, c_float_p, c_float_p, c_float_p, ctypes.c_float,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
+    "avr_graph_index_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "avr_graph_index_connect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p, c_int_p]),
+    "avr_graph_connect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p,
+                                         c_int_p]),
+    "avr_graph_render": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int]),
+    "avr_graph_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int_p,
+                                           ctypes.c_longlong]),
 }
 
 _lib = None
@@ -590,6 +600,29 @@ class Context:
                                             _fp(total), ctypes.byref(it)))
         return total, it.value
 
+    def graph_connect(self, index, points):
+        """ConnectToGraph on the device for (n, 3) graph-space points: (light, counts), bitwise
+        GraphIndex.connect's."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        light = np.zeros(len(p), np.float32)
+        counts = np.zeros(len(p), np.int32)
+        _check(self.lib.avr_graph_connect(self.h, index.h, len(p), _fp(p), _fp(light), counts.ctypes.data_as(c_int_p)))
+        return light, counts
+
+    def graph_render(self, index, spp_begin, spp_end, seed, graph_from_render=None):
+        """GraphIntegrator::Li (free graph) for sample indices [spp_begin, spp_end) into the film."""
+        m = None if graph_from_render is None else np.ascontiguousarray(graph_from_render, np.float32).reshape(16)
+        _check(self.lib.avr_graph_render(self.h, index.h, _fp(m), int(spp_begin), int(spp_end), int(seed)))
+
+    def graph_last_pass(self, npix, max_samples):
+        """The last graph pass per sample (indexed as last_pass_samples): camera ray o, d, the
+        scatter point in render space ((n, 3) each) and the vertices averaged (-1: no scatter)."""
+        n = npix * max_samples
+        o, d, pts = (np.zeros((n, 3), np.float32) for _ in range(3))
+        counts = np.zeros(n, np.int32)
+        _check(self.lib.avr_graph_last_pass(self.h, _fp(o), _fp(d), _fp(pts), counts.ctypes.data_as(c_int_p), n))
+        return o, d, pts, counts
+
     def film_export_device(self, d_dst_ptr):
         _check(self.lib.avr_film_export_device(self.h, ctypes.c_void_p(d_dst_ptr)))
 
@@ -706,6 +739,48 @@ class Graph:
         a, n = ctypes.c_float(), ctypes.c_longlong()
         _check(self.lib.avr_graph_in_node_path_length(self.h, ctypes.byref(a), ctypes.byref(n)))
         return a.value, n.value
+
+
+class GraphIndex:
+    """The graph render's vertex index (avr_graph_index_*): vertices (n, 3), their lightScalar,
+    optionally their renderSearchRange, and the vertex radius. Host code; Context.graph_render
+    and Context.graph_connect upload it to the device on first use."""
+
+    def __init__(self, points, light_scalar, search_range=None, radius=None):
+        if radius is None:
+            raise ValueError("GraphIndex needs the graph's vertex radius")
+        self.lib = load()
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        light = np.ascontiguousarray(light_scalar, np.float32).reshape(-1)
+        rng = None if search_range is None else np.ascontiguousarray(search_range, np.float32).reshape(-1)
+        if len(light) != len(p) or (rng is not None and len(rng) != len(p)):
+            raise ValueError("GraphIndex: one light scalar (and search range) per vertex")
+        h = ctypes.c_void_p()
+        self.h = None
+        _check(self.lib.avr_graph_index_create(len(p), _fp(p), _fp(light), _fp(rng), float(radius), ctypes.byref(h)))
+        self.h = h
+        self.num_vertices = len(p)
+        self.radius = float(radius)
+        self.has_search_range = rng is not None
+
+    def connect(self, points):
+        """ConnectToGraph on the host for (n, 3) graph-space points: (light, counts)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        light = np.zeros(len(p), np.float32)
+        counts = np.zeros(len(p), np.int32)
+        _check(self.lib.avr_graph_index_connect(self.h, len(p), _fp(p), _fp(light), counts.ctypes.data_as(c_int_p)))
+        return light, counts
+
+    def close(self):
+        if self.h:
+            self.lib.avr_graph_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def film_reduce_rccl(contexts, root=0):

@@ -191,6 +191,15 @@ struct avr_context {
     // order) it was created with by ncclCommInitAll; reused while the same clique reduces
     ncclComm_t comm = nullptr;
     std::vector<avr_context *> comm_group;
+    // graph render (avr_graph_render / avr_graph_connect): the device copy of the last index
+    // used, named by the index's id (an address could be reused by a later index); one
+    // allocation behind gidx's pointers. d_gside: the pass's {scatter point, neighbour count}.
+    unsigned long long gidx_uid = 0;
+    char *d_gidx = nullptr;
+    avr::graph::IndexView gidx{};
+    float4 *d_gside = nullptr;
+    long long gside_cap = 0;
+    bool last_graph = false;        // the last render was avr_graph_render's
 };
 
 namespace {
@@ -805,6 +814,8 @@ int avr_context_destroy(avr_context *c) {
     if (c->d_metric) (void)hipFree(c->d_metric);
     if (c->d_fat) (void)hipFree(c->d_fat);
     if (c->d_brick) (void)hipFree(c->d_brick);
+    if (c->d_gidx) (void)hipFree(c->d_gidx);
+    if (c->d_gside) (void)hipFree(c->d_gside);
     free_pixel_order(c);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->h_count) (void)hipHostFree(c->h_count);
@@ -1872,13 +1883,9 @@ static int next_event(avr_context *c, int *idx) {
         if (rc_) return rc_;              \
     } while (0)
 
-int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_depth) {
-    if (!c) return fail(AVR_ERR_ARG, "null context");
-    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
-    if (spp_begin < 0 || spp_end < spp_begin || max_depth < 0) return fail(AVR_ERR_ARG, "bad sample range");
-    if (c->image_lights_ready < c->n_image_lights) return fail(AVR_ERR_STATE, "image light without avr_light_image");
-    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
-        return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
+// The pixel sampler of a render call (avr_render, avr_graph_render): the ZSobol range checks,
+// the device selected, and the ZSobol pixel table rebuilt when the sampler or film changed.
+static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobolParams *out) {
     avr::smp::ZSobolParams zs{};
     if (c->sampler_kind == 1) {
         // ZSobolSampler indexes (Morton(pixel) << log2(spp)) | sampleIndex: indices must stay
@@ -1927,6 +1934,22 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
         zs.upper = c->d_zs_table;
         zs.dmax = c->d_zs_table ? c->zs_dims : 0;
     }
+    *out = zs;
+    return AVR_OK;
+}
+
+int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_depth) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
+    if (spp_begin < 0 || spp_end < spp_begin || max_depth < 0) return fail(AVR_ERR_ARG, "bad sample range");
+    if (c->image_lights_ready < c->n_image_lights) return fail(AVR_ERR_STATE, "image light without avr_light_image");
+    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+        return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
+    avr::smp::ZSobolParams zs{};
+    {
+        int rc = render_sampler(c, spp_end, seed, &zs);
+        if (rc) return rc;
+    }
     const long long P = (long long)c->film.width * c->film.height;
     if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
     // k_paths runs every medium type with every light type: GridMedium, RGBGridMedium and
@@ -1974,6 +1997,7 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
         const long long n0 = P * S;
         c->last_persistent = persistent;
         c->last_fast = persistent && c->render_mode == 1;
+        c->last_graph = false;
         if (persistent) {
             // PCG32 Advance(s*65536) as an affine map state' = A*state + inc*H (rng.h:132-146:
             // every step is linear in inc, so H = accPlus computed with inc = 1).

@@ -16,10 +16,17 @@
 //                  CSR row per lane, terms summed in ascending column order (Eigen's
 //                  column-major sparse x sparse-vector order), NaN/Inf flag per bounce; the
 //                  previous bounce's vector is added to the total in the same pass.
+//  k_graph_connect GraphIntegrator::ConnectToGraph (graph_integrator.cpp:249-280) for a batch
+//                  of graph-space points: index_connect (avr_graph_index.h), one lane per point.
+//  k_graph_render  GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247): one
+//                  lane per camera record of the pass; delta tracking to the first real
+//                  scatter, then the same index_connect.
 //
 // Geometry model (shared with the oracle): the medium's boundary primitive is
 // its bounds box (medium-space slab test, ray mapped without error offsets); spheres solve
 // Sphere::BasicIntersect's interval quadric once for both roots.
+#include "avr_graph_index.h"
+
 namespace avr {
 namespace graph {
 
@@ -343,6 +350,104 @@ __global__ void __launch_bounds__(256) k_graph_accumulate(int n, const float *__
     for (int j = 0; j < it; ++j)
         if (flags[j]) return;
     for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n; row += gridDim.x * blockDim.x) total[row] += cur[row];
+}
+
+// index_connect's sorted keys in LDS: entry i of this lane at [i * 256] (consecutive lanes in
+// consecutive banks), 2 x 16 KiB per block; the buffer is indexed at run time, so registers
+// would turn into scratch
+struct ConnectBufLds {
+    float *d;
+    int *s;
+    __device__ __forceinline__ float &d2(int i) { return d[i * 256]; }
+    __device__ __forceinline__ int &slot(int i) { return s[i * 256]; }
+};
+
+// ConnectToGraph for n points already in graph space (avr_graph_connect)
+__global__ void __launch_bounds__(256) k_graph_connect(graph::IndexView ix, long long n, const float *__restrict__ pts,
+                                                       float *__restrict__ light, int *__restrict__ count) {
+    __shared__ float s_d2[graph::kConnectBuf * 256];
+    __shared__ int s_slot[graph::kConnectBuf * 256];
+    ConnectBufLds buf{s_d2 + threadIdx.x, s_slot + threadIdx.x};
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int cnt = 0, stage = 0;
+        light[i] = graph::index_connect(ix, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], buf, &cnt, &stage);
+        count[i] = cnt;
+    }
+}
+
+// GraphIntegrator::Li, free graph (graph_integrator.cpp:180-247), after k_camera: the camera
+// record's ray crosses the medium's bounds box in the graph tools' geometry model (box_hits;
+// a ray from outside starts at its entry point, as FreeGraphBuilder's rays do; a camera
+// inside the box, which the reference leaves commented out, tracks from its origin), hash0 and
+// hash1 seed the RNG, SampleT_maj runs with the medium's coefficients at the sample's own
+// wavelengths and the 3-way event choice on channel 0; the first real scatter p gives
+// L = lightSpectrum.Sample(lambda) * ConnectToGraph(graphFromRender(p)), absorption or
+// leaving the box L = 0. L goes where k_film reads it; side[id] = {p, count} (render space;
+// count -1 without a scatter).
+template <bool kZSobol>
+__global__ void __launch_bounds__(256) k_graph_render(Params P, graph::IndexView ix, Xf graphFromRender,
+                                                      float4 *__restrict__ side) {
+    __shared__ float s_maj[4096];
+    const float *maj = stage_majorant(P.med, s_maj);
+    __shared__ float s_d2[graph::kConnectBuf * 256];
+    __shared__ int s_slot[graph::kConnectBuf * 256];
+    ConnectBufLds buf{s_d2 + threadIdx.x, s_slot + threadIdx.x};
+    const float *lightL = P.lights.list[0].L;   // DistantLight::GetLEmit: scale * Lemit (lights.h:293-297)
+    const float lightScale = P.lights.list[0].scale;
+    unsigned long long nLookup = 0, nSteps = 0, nIn = 0;
+    const int n = P.pass_pixels * P.pass_samples;
+    for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
+        ++nIn;
+        const V3 o = from4(P.ps.o[id]), d = from4(P.ps.d[id]);
+        const Spec lam = spec4(P.ps.lambda[id]);
+        PathSampler<kZSobol> smp;
+        smp.load(P, id);
+        Spec L = Spec::c(0.f);
+        int count = -1;
+        V3 pS = {0.f, 0.f, 0.f};
+        const graph::Hits h = graph::box_hits(P.med, o, d);
+        if (h.type != graph::kOutsideZeroHits) {
+            V3 ro = o;
+            float tMax = h.t0;
+            if (h.type == graph::kOutsideTwoHits) {
+                ro = o + d * h.t0;
+                tMax = h.t1 - h.t0;
+            }
+            const LambdaIdx li = lambda_index(lam);
+            const Spec sig_a = sample_table(P.med.sigma_a, li), sig_s = sample_table(P.med.sigma_s, li);
+            const float h0 = smp.get1d(P);
+            const float h1 = smp.get1d(P);
+            Pcg32 rng;
+            rng.set_sequence(hash_u32(f2u(h0)), hash_u32(f2u(h1)));
+            const float u = smp.get1d(P);
+            bool scattered = false;
+            auto cb = [&](V3 p, const MediumSample &ms, const Spec &sigma_maj, const Spec &) -> bool {
+                const float pAbsorb = ms.sigma_a.v0 / sigma_maj.v0;
+                const float pScat = ms.sigma_s.v0 / sigma_maj.v0;
+                const float pNull = fmaxf_(0.f, 1 - pAbsorb - pScat);
+                const int mode = sample_discrete3(pAbsorb, pScat, pNull, rng.uniform());
+                if (mode == 0) return false;
+                if (mode == 1) {
+                    scattered = true;
+                    pS = p;
+                    return false;
+                }
+                return true;
+            };
+            sample_t_maj(P.med, maj, Ray{ro, d}, tMax, u, rng, sig_a, sig_s, Spec::c(0.f), lam, nLookup, nSteps, cb);
+            if (scattered) {
+                const V3 q = xf_point_lr(graphFromRender, pS);
+                int stage = 0;
+                const float conn = graph::index_connect(ix, q.x, q.y, q.z, buf, &count, &stage);
+                L = (sample_table(lightL, li) * lightScale) * conn;
+            }
+        }
+        P.ps.L[id] = to4(L);
+        side[id] = make_float4(pS.x, pS.y, pS.z, __int_as_float(count));
+    }
+    flush_stat(P.stats, 3, nLookup);
+    flush_stat(P.stats, 4, nIn);
+    flush_stat(P.stats, 6, nSteps);
 }
 
 }  // namespace avr

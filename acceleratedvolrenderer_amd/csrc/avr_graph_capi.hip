@@ -1,6 +1,9 @@
-// avr_graph_capi.hip — C-ABI of the lighting-graph precompute (include/avr.h, "Lighting
-// graph"), included at the end of avr_capi.hip (shares avr_context, fail(), HIP_TRY).
+// avr_graph_capi.hip — C-ABI of the lighting-graph precompute and of the graph render
+// (include/avr.h, "Lighting graph"), included at the end of avr_capi.hip (shares avr_context,
+// fail(), HIP_TRY, the render calls' sampler setup and path state).
 #include "avr_graph_host.h"
+
+#include <atomic>
 
 namespace {
 
@@ -31,6 +34,53 @@ int graph_params(avr_context *c, const avr_graph_sampling *s, unsigned long long
             return fail(AVR_ERR_ARG, "zsobol: graph sampling indices beyond the 2^32 Sobol' index range");
         p->zs = zs;
     }
+    return AVR_OK;
+}
+
+}  // namespace
+
+// The host vertex index (avr_graph_index.h) and the id its device copies are cached under
+struct avr_graph_index {
+    avr::graph::Index ix;
+    unsigned long long uid = 0;
+};
+
+namespace {
+
+std::atomic<unsigned long long> g_index_uid{0};
+
+// The context's device copy of `idx` (c->gidx), uploaded on first use and replaced when
+// another index is used: records | ids | cell offsets | squared ranges in one allocation.
+int ensure_graph_index(avr_context *c, const avr_graph_index *idx) {
+    if (c->gidx_uid == idx->uid) return AVR_OK;
+    // queued kernels may still read the previous copy
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_gidx) (void)hipFree(c->d_gidx);
+    c->d_gidx = nullptr;
+    c->gidx_uid = 0;
+    const avr::graph::IndexView h = idx->ix.View();
+    const size_t n = idx->ix.NumVertices(), cells = idx->ix.NumCells();
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t szRec = pad(n * sizeof(avr::graph::IndexRec)), szId = pad(n * sizeof(int));
+    const size_t szStart = pad((cells + 1) * sizeof(int)), szRange = h.range2 ? pad(n * sizeof(float)) : 0;
+    HIP_TRY(dalloc(&c->d_gidx, szRec + szId + szStart + szRange));
+    char *d = c->d_gidx;
+    hipError_t e = hipMemcpy(d, h.rec, n * sizeof(avr::graph::IndexRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + szRec, h.id, n * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + szRec + szId, h.cell_start, (cells + 1) * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h.range2)
+        e = hipMemcpy(d + szRec + szId + szStart, h.range2, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(c->d_gidx);
+        c->d_gidx = nullptr;
+        return fail(AVR_ERR_HIP, std::string("graph index upload: ") + hipGetErrorString(e));
+    }
+    c->gidx = h;
+    c->gidx.rec = (const avr::graph::IndexRec *)d;
+    c->gidx.id = (const int *)(d + szRec);
+    c->gidx.cell_start = (const int *)(d + szRec + szId);
+    c->gidx.range2 = h.range2 ? (const float *)(d + szRec + szId + szStart) : nullptr;
+    c->gidx_uid = idx->uid;
     return AVR_OK;
 }
 
@@ -357,6 +407,173 @@ int avr_graph_in_node_path_length(avr_graph *g, float *average, long long *count
     // Averager::GetAverage over the added values (util.h:545-565); a double sum here
     if (average) *average = g->b.PathLengthCount() ? (float)(g->b.PathLengthSum() / g->b.PathLengthCount()) : 0.f;
     if (count) *count = g->b.PathLengthCount();
+    return AVR_OK;
+}
+
+int avr_graph_index_create(long long n, const float *xyz, const float *light_scalar, const float *search_range,
+                           float vertex_radius, avr_graph_index **out) {
+    if (!out) return fail(AVR_ERR_ARG, "null out");
+    *out = nullptr;
+    auto *idx = new avr_graph_index();
+    if (const char *msg = idx->ix.Build(n, xyz, light_scalar, search_range, vertex_radius)) {
+        delete idx;
+        return fail(AVR_ERR_ARG, msg);
+    }
+    idx->uid = ++g_index_uid;
+    *out = idx;
+    return AVR_OK;
+}
+int avr_graph_index_destroy(avr_graph_index *idx) {
+    delete idx;
+    return AVR_OK;
+}
+int avr_graph_index_connect(const avr_graph_index *idx, long long n, const float *points, float *light_out,
+                            int *count_out) {
+    if (!idx || n < 0) return fail(AVR_ERR_ARG, "bad connect arguments");
+    if (n > 0 && !points) return fail(AVR_ERR_ARG, "null buffer");
+    idx->ix.Connect(n, points, light_out, count_out);
+    return AVR_OK;
+}
+
+int avr_graph_connect(avr_context *c, const avr_graph_index *idx, long long n, const float *points, float *light_out,
+                      int *count_out) {
+    if (!c || !idx || n < 0) return fail(AVR_ERR_ARG, "bad connect arguments");
+    if (n == 0) return AVR_OK;
+    if (!points || !light_out || !count_out) return fail(AVR_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_graph_index(c, idx);
+    if (rc) return rc;
+    char *buf = nullptr;
+    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
+    HIP_TRY(dalloc(&buf, szP + 2 * szL));
+    float *dP = (float *)buf, *dL = (float *)(buf + szP);
+    int *dC = (int *)(buf + szP + szL);
+    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_graph_connect, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n,
+                           dP, dL, dC);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(light_out, dL, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(count_out, dC, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph connect: ") + hipGetErrorString(e));
+    return AVR_OK;
+}
+
+int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                     int spp_end, int seed) {
+    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
+    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
+    if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
+    // GraphIntegrator::Create takes the scene's one DistantLight (lightSpectrum, lightDir)
+    if (c->lights.n != 1 || c->h_lights[0].type != 0)
+        return fail(AVR_ERR_STATE, "graph render: exactly one distant light required");
+    if (c->med.boundary != 0)
+        return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const float *gfr = graph_from_render ? graph_from_render : kIdentity;
+    if (!affine(gfr)) return fail(AVR_ERR_ARG, "graph_from_render must be affine");
+    avr::Xf xf;
+    copy_xf(xf, gfr);
+    avr::smp::ZSobolParams zs{};
+    int rc = render_sampler(c, spp_end, seed, &zs);
+    if (rc) return rc;
+    rc = ensure_graph_index(c, idx);
+    if (rc) return rc;
+    const long long P = (long long)c->film.width * c->film.height;
+    if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
+    // the pass loop of avr_render's wavefront organisation: k_camera, k_graph_render, k_film
+    const long long Smax = std::max<long long>(1, c->max_paths / P);
+    const long long need = P * std::min<long long>(Smax, std::max(1, spp_end - spp_begin));
+    rc = ensure_paths(c, need);
+    if (rc) return rc;
+    if (need > c->gside_cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->d_gside) (void)hipFree(c->d_gside);
+        c->d_gside = nullptr;
+        c->gside_cap = 0;
+        HIP_TRY(dalloc(&c->d_gside, (size_t)need));
+        c->gside_cap = need;
+    }
+    EV_MARK(evStart);
+    for (long long base = spp_begin; base < spp_end; base += Smax) {
+        const int S = (int)std::min<long long>(Smax, spp_end - base);
+        avr::Params p{};
+        p.med = c->med;
+        p.lights = c->lights;
+        p.cam = c->cam;
+        p.film = c->film;
+        p.film.filter_type = c->filter_type;
+        p.film.gauss = c->ftab;
+        p.sampler_kind = c->sampler_kind;
+        p.zs = zs;
+        p.ps = c->ps;
+        p.sh = c->sh;
+        p.max_depth = 1;
+        p.seed = seed;
+        p.pass_pixels = (int)P;
+        p.div_pixels = avr::fastdiv_make((uint32_t)P);
+        p.div_width = avr::fastdiv_make((uint32_t)c->film.width);
+        p.pass_samples = S;
+        p.sample_base = (int)base;
+        p.stats = c->d_stats;
+        const long long n0 = P * S;
+        c->last_persistent = false;
+        c->last_fast = false;
+        c->last_graph = true;
+        EV_MARK(c0);
+        if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
+        else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
+        HIP_TRY(hipGetLastError());
+        EV_MARK(c1);
+        c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});
+        // one lane per camera record, as many blocks as records up to 64 per CU's worth
+        const int nb = blocks_for(n0, 256, 256 * 64);
+        if (c->sampler_kind)
+            hipLaunchKernelGGL(avr::k_graph_render<true>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
+        else
+            hipLaunchKernelGGL(avr::k_graph_render<false>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
+        HIP_TRY(hipGetLastError());
+        EV_MARK(m1);
+        c->timed.push_back({c1, m1, &avr_stats::ms_medium, true});
+        hipLaunchKernelGGL((c->film.nbuckets > 0 ? avr::k_film<true> : avr::k_film<false>), dim3(blocks_for(P)), dim3(256),
+                           avr::film_lds_bytes(c->film.nbuckets), c->stream, p);
+        HIP_TRY(hipGetLastError());
+        EV_MARK(f1);
+        c->timed.push_back({m1, f1, &avr_stats::ms_film, false});
+        c->last_base = (int)base;
+        c->last_S = S;
+    }
+    EV_MARK(evEnd);
+    c->timed.push_back({evStart, evEnd, &avr_stats::ms_total, false});
+    return AVR_OK;
+}
+
+int avr_graph_last_pass(avr_context *c, float *o, float *d, float *points, int *counts, long long n_max) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
+    if (!c->last_graph) return fail(AVR_ERR_STATE, "the last render was not avr_graph_render's");
+    const long long n = (long long)c->film.width * c->film.height * c->last_S;
+    if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
+    if (n == 0) return AVR_OK;
+    std::vector<float4> h((size_t)n);
+    const float4 *src[3] = {c->ps.o, c->ps.d, c->d_gside};
+    float *dst[3] = {o, d, points};
+    for (int k = 0; k < 3; ++k) {
+        if (!dst[k] && !(k == 2 && counts)) continue;
+        HIP_TRY(hipMemcpy(h.data(), src[k], (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+        for (long long i = 0; i < n; ++i) {
+            if (dst[k]) {
+                dst[k][3 * i] = h[(size_t)i].x;
+                dst[k][3 * i + 1] = h[(size_t)i].y;
+                dst[k][3 * i + 2] = h[(size_t)i].z;
+            }
+            if (k == 2 && counts) std::memcpy(&counts[i], &h[(size_t)i].w, sizeof(int));
+        }
+    }
     return AVR_OK;
 }
 

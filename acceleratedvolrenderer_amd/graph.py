@@ -1,4 +1,5 @@
-"""Lighting-graph precompute — host mirror of the fork's src/graph tools.
+"""Lighting graph — host mirror of the fork's src/graph tools: the
+precompute and the render that consumes it.
 
 The reference builds a "free graph" of scatter points in a medium lit by one distant light,
 then solves light transport on it (cmd/graph_maker.cpp:70-160):
@@ -19,7 +20,17 @@ geometry is in the scene's render space; the medium's boundary primitive is its 
 (DESIGN.md §9).
 
 ReinforceSparseVertices (:280-475) runs its rays and walks on the GPU and its sparse-vertex
-checks on the host graph. Not mirrored: the graph's text file format.
+checks on the host graph.
+
+The render is GraphIntegrator (graph_integrator.cpp:180-280, free-graph branch):
+FreeGraph.index(light_scalar) builds the vertex index (a cell grid, capi.GraphIndex; host
+C++), and GraphIntegrator renders with it on the GPU: per camera sample the first real
+scatter in the medium is connected to the vertices within the vertex radius (or, with
+renderSearchRange active, within their search ranges), weighted by inverse squared distance
+(k_graph_render). build_graph -> LightingCalculator.compute_final_light -> index ->
+GraphIntegrator.render is the whole pipeline; the graph is handed over in memory.
+
+Not mirrored: the graph's text file format, the uniform-graph branch, --graph-debug.
 """
 import json
 import math
@@ -27,6 +38,8 @@ import math
 import numpy as np
 
 from . import capi
+from .integrator import FilmIntegrator
+from .scene import GBufferFilm
 
 f32 = np.float32
 
@@ -215,6 +228,13 @@ class FreeGraph:
         """GetTransportMatrix (lighting_calculator.cpp:61-82) as CSR."""
         return self._g.transport()
 
+    def index(self, light_scalar):
+        """The render's vertex index (GraphIntegrator::Initialize): these vertices with
+        `light_scalar` (LightingCalculator.light_scalar) as VertexData::lightScalar, the
+        vertex radius, and the search ranges when the builder computed them
+        (useRenderSearchRange)."""
+        return capi.GraphIndex(self.points, light_scalar, self.search_range, radius=self.radius)
+
 
 class FreeGraphBuilder:
     """FreeGraphBuilder (free/free_graph_builder.cpp): walks on the GPU, merge on the host."""
@@ -385,3 +405,48 @@ class LightingCalculator:
         total, it = self.ctx.graph_propagate(rp, col, val, light, self.config.bounces[bounces_index])
         self.light_scalar = total
         return it
+
+
+# ---------------------------------------------------------------------------
+# The render (graph_integrator.cpp)
+
+class GraphIntegrator(FilmIntegrator):
+    """GraphIntegrator, free-graph branch (graph_integrator.cpp:180-280): every camera ray's
+    first real scatter point in the medium is connected to the graph vertices around it
+    (k_graph_render, avr_graph_render), which gives the graph's multiple scattering at about
+    the cost of single scattering. `graph_index` is FreeGraph.index(light_scalar) or a
+    capi.GraphIndex over any vertices. `graph_from_render` (4x4, affine) maps a render-space
+    scatter point into the graph's space: the identity by default, since the graph tools here
+    work in the scene's render space; a graph made in world space, as the reference's
+    graph_maker makes them, takes inv(scene.render_from_world). The scene needs exactly one
+    DistantLight, no interface sphere or mesh, and not a GBufferFilm (its geometric channels
+    have no meaning here). render(), film_sums(), image(), get_image() and write_image()
+    are VolPathIntegrator's."""
+
+    def __init__(self, scene, graph_index, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0):
+        if isinstance(scene.film, GBufferFilm):
+            raise ValueError("GraphIntegrator does not render into a GBufferFilm")
+        self.scene = scene
+        self.index = graph_index
+        self.spp = int(spp)
+        self.seed = int(seed)
+        self.device = int(device)
+        self.graph_from_render = None if graph_from_render is None else np.asarray(graph_from_render, f32).reshape(4, 4)
+        self.ctx = capi.Context(device, max_paths)
+        self.ctx.set_scene(scene)
+
+    def _render_range(self, spp_begin, spp_end):
+        self.ctx.graph_render(self.index, spp_begin, spp_end, self.seed, self.graph_from_render)
+
+    def last_pass(self, max_samples=None):
+        """The last pass per sample: dict of first sample index, sample count, L, lambda, pdf
+        (n, 4), camera ray o, d, scatter point p (n, 3, render space) and the vertices
+        averaged (count, -1 without a scatter); n = pixels x samples of that pass, element
+        s * pixels + pixel."""
+        f = self.scene.film
+        npix = f.width * f.height
+        ms = self.spp if max_samples is None else int(max_samples)
+        first, ns, L, lam, pdf = self.ctx.last_pass_samples(npix, ms)
+        o, d, p, count = self.ctx.graph_last_pass(npix, ms)
+        n = npix * ns
+        return dict(first=first, samples=ns, L=L, lam=lam, pdf=pdf, o=o[:n], d=d[:n], p=p[:n], count=count[:n])

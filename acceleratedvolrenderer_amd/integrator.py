@@ -56,7 +56,95 @@ def reduce_film(buf, npix, nbuckets, rank, group=None):
 GRID_LAYOUTS = {"linear": 0, "fat": 1, "brick": 2}
 GRID_LAYOUT_NAMES = {v: k for k, v in GRID_LAYOUTS.items()}
 
-class VolPathIntegrator:
+class FilmIntegrator:
+    """What every integrator here shares: a context (self.ctx) with the scene set, the sample
+    loop's entry and the film's readback, image and file output. A subclass sets scene, spp,
+    seed and ctx and renders a range of sample indices in _render_range."""
+
+    def _render_range(self, spp_begin, spp_end):
+        raise NotImplementedError
+
+    def render(self, spp_begin=0, spp_end=None, clear=True):
+        """Render sample indices [spp_begin, spp_end); returns (rgb_sum, w_sum) fp64."""
+        if spp_end is None:
+            spp_end = self.spp
+        if clear:
+            self.ctx.film_clear()
+        self._render_range(spp_begin, spp_end)
+        return self.film_sums()
+
+    def film_sums(self):
+        f = self.scene.film
+        return self.ctx.film_read(f.width * f.height)
+
+    def spectral_sums(self):
+        """SpectralFilm Pixel::bucketSums / weightSums, (W*H, nbuckets) fp64 each."""
+        f = self.scene.film
+        if not getattr(f, "nbuckets", 0):
+            raise ValueError("the scene's film is not a SpectralFilm")
+        return self.ctx.film_read_spectral(f.width * f.height, f.nbuckets)
+
+    def spectral_image(self, fp16=True):
+        """SpectralFilm::GetImage: (H, W, 3 + nbuckets), channels film.channel_names()."""
+        from .scene import spectral_image
+        rgb, w = self.film_sums()
+        bs, bw = self.spectral_sums()
+        return spectral_image(self.scene.film, rgb, w, bs, bw, fp16=fp16)
+
+    def image(self, rgb_sum=None, w_sum=None):
+        if rgb_sum is None:
+            rgb_sum, w_sum = self.film_sums()
+        return film_rgb(self.scene.film, rgb_sum, w_sum)
+
+    def stats(self):
+        return self.ctx.stats()
+
+    def get_image(self, rgb_sum=None, w_sum=None, fp16=True):
+        """RGBFilm::GetImage (film.cpp:533-565): GetPixelRGB per pixel, and for the fp16
+        image ("savefp16", default true) the 65504 clamp and the half rounding."""
+        img = self.image(rgb_sum, w_sum)
+        if fp16:
+            img = np.minimum(img, np.float32(65504)).astype(np.float16).astype(np.float32)
+        return img
+
+    def write_image(self, path, rgb_sum=None, w_sum=None, spp=None, render_time=None, mse=None, fp16=True):
+        """RGBFilm::WriteImage -> Image::Write: EXR (pbrt's attributes, ZIP) or PFM by extension.
+        SpectralFilm (film.cpp:955-1028): EXR only, R G B + S0.<lambda>nm channels and the
+        spectral layout strings."""
+        f = self.scene.film
+        if getattr(f, "nbuckets", 0):
+            if not str(path).lower().endswith(".exr"):
+                raise ValueError(f"{path}: EXR is the only output format supported by the SpectralFilm.")
+            img = self.spectral_image(fp16)
+            if fp16:
+                img = img.astype(np.float16).astype(np.float32)
+            imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
+                              samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
+                              mse=mse, strings={"spectralLayoutVersion": "1.0", "emissiveUnits": "W.m^-2.sr^-1"})
+            return img
+        if isinstance(f, GBufferFilm):
+            if rgb_sum is None:
+                rgb_sum, w_sum = self.film_sums()
+            img = gbuffer_image(f, rgb_sum, w_sum, fp16)
+            if fp16:
+                img = img.astype(np.float16).astype(np.float32)
+            imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
+                              samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
+                              mse=mse)
+            return img
+        img = self.get_image(rgb_sum, w_sum, fp16)
+        if str(path).lower().endswith(".pfm"):
+            imageio.write_pfm(path, img)
+        else:
+            imageio.write_exr(path, img, half=fp16, samples_per_pixel=spp if spp is not None else self.spp,
+                              render_time_seconds=render_time, mse=mse)
+        return img
+
+    def close(self):
+        self.ctx.close()
+
+
+class VolPathIntegrator(FilmIntegrator):
     def __init__(self, scene, maxdepth=5, spp=16, seed=0, device=0, max_paths=0, lightsampler="bvh",
                  regularize=False, name="volpath", kernel="persistent", grid_layout="fat", mode="replay"):
         if name not in INTEGRATOR_NAMES:
@@ -155,81 +243,8 @@ class VolPathIntegrator:
         key = np.where(hit, (c[:, 2] * res[1] + c[:, 1]) * res[0] + c[:, 0], res.prod())
         return np.argsort(key, kind="stable").astype(np.int32)
 
-    def render(self, spp_begin=0, spp_end=None, clear=True):
-        """Render sample indices [spp_begin, spp_end); returns (rgb_sum, w_sum) fp64."""
-        if spp_end is None:
-            spp_end = self.spp
-        if clear:
-            self.ctx.film_clear()
+    def _render_range(self, spp_begin, spp_end):
         self.ctx.render(spp_begin, spp_end, self.seed, self.maxdepth)
-        return self.film_sums()
-
-    def film_sums(self):
-        f = self.scene.film
-        return self.ctx.film_read(f.width * f.height)
-
-    def spectral_sums(self):
-        """SpectralFilm Pixel::bucketSums / weightSums, (W*H, nbuckets) fp64 each."""
-        f = self.scene.film
-        if not getattr(f, "nbuckets", 0):
-            raise ValueError("the scene's film is not a SpectralFilm")
-        return self.ctx.film_read_spectral(f.width * f.height, f.nbuckets)
-
-    def spectral_image(self, fp16=True):
-        """SpectralFilm::GetImage: (H, W, 3 + nbuckets), channels film.channel_names()."""
-        from .scene import spectral_image
-        rgb, w = self.film_sums()
-        bs, bw = self.spectral_sums()
-        return spectral_image(self.scene.film, rgb, w, bs, bw, fp16=fp16)
-
-    def image(self, rgb_sum=None, w_sum=None):
-        if rgb_sum is None:
-            rgb_sum, w_sum = self.film_sums()
-        return film_rgb(self.scene.film, rgb_sum, w_sum)
-
-    def stats(self):
-        return self.ctx.stats()
-
-    def get_image(self, rgb_sum=None, w_sum=None, fp16=True):
-        """RGBFilm::GetImage (film.cpp:533-565): GetPixelRGB per pixel, and for the fp16
-        image ("savefp16", default true) the 65504 clamp and the half rounding."""
-        img = self.image(rgb_sum, w_sum)
-        if fp16:
-            img = np.minimum(img, np.float32(65504)).astype(np.float16).astype(np.float32)
-        return img
-
-    def write_image(self, path, rgb_sum=None, w_sum=None, spp=None, render_time=None, mse=None, fp16=True):
-        """RGBFilm::WriteImage -> Image::Write: EXR (pbrt's attributes, ZIP) or PFM by extension.
-        SpectralFilm (film.cpp:955-1028): EXR only, R G B + S0.<lambda>nm channels and the
-        spectral layout strings."""
-        f = self.scene.film
-        if getattr(f, "nbuckets", 0):
-            if not str(path).lower().endswith(".exr"):
-                raise ValueError(f"{path}: EXR is the only output format supported by the SpectralFilm.")
-            img = self.spectral_image(fp16)
-            if fp16:
-                img = img.astype(np.float16).astype(np.float32)
-            imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
-                              samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
-                              mse=mse, strings={"spectralLayoutVersion": "1.0", "emissiveUnits": "W.m^-2.sr^-1"})
-            return img
-        if isinstance(f, GBufferFilm):
-            if rgb_sum is None:
-                rgb_sum, w_sum = self.film_sums()
-            img = gbuffer_image(f, rgb_sum, w_sum, fp16)
-            if fp16:
-                img = img.astype(np.float16).astype(np.float32)
-            imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
-                              samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
-                              mse=mse)
-            return img
-        img = self.get_image(rgb_sum, w_sum, fp16)
-        if str(path).lower().endswith(".pfm"):
-            imageio.write_pfm(path, img)
-        else:
-            imageio.write_exr(path, img, half=fp16, samples_per_pixel=spp if spp is not None else self.spp,
-                              render_time_seconds=render_time, mse=mse)
-        return img
 
     def render_waves(self, mse_reference=None, mse_out=None, metric="MSE"):
         """ImageTileIntegrator::Render's wave loop (integrators.cpp:166-232): waves of
@@ -286,6 +301,3 @@ class VolPathIntegrator:
         buf = torch.empty(film_buffer_size(f.width * f.height, nb), dtype=torch.float64, device=f"cuda:{self.device}")
         self.ctx.film_export_device(buf.data_ptr())
         return reduce_film(buf, f.width * f.height, nb, rank, group)
-
-    def close(self):
-        self.ctx.close()

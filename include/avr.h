@@ -513,6 +513,62 @@ int avr_graph_transport(avr_graph *g, int *row_ptr, int *col, float *val);
 /* UseAndRemovePathInfo's in-node path length average (free_graph_builder.cpp:241-273) */
 int avr_graph_in_node_path_length(avr_graph *g, float *average, long long *count);
 
+/* The graph render's vertex index (GraphIntegrator::Initialize, graph_integrator.cpp:50-80:
+ * squared vertex radius, squared search ranges with their 99th percentile
+ * sorted[n * 99 / 100] and maximum, the search structure). Host code, no GPU needed. n
+ * vertices (id = row of xyz, n*3), their VertexData::lightScalar, and their
+ * renderSearchRange or NULL (streamFlags->useRenderSearchRange = false). Layout: a uniform
+ * cell grid over the vertices' bounding box, vertices counting-sorted by cell, one 16-B record
+ * {x, y, z, lightScalar} each; cell edge = vertex_radius, doubled until the grid holds at most
+ * 2^21 cells. AVR_ERR_ARG: n < 1, a radius that is not positive and finite, a non-finite
+ * coordinate, a negative or non-finite search range.
+ * avr_graph_index_connect: ConnectToGraph (:249-280) for n points already in graph space.
+ * Distance d2 = ((qx-vx)^2 + (qy-vy)^2) + (qz-vz)^2 in float (nanoflann L2_Simple_Adaptor); a
+ * vertex is in the result iff d2 < r2, strictly. Stage 0: r2 = Sqr(vertex_radius). With search
+ * ranges and an empty stage 0: stage 1, r2 = the 99th-percentile squared range, dropping
+ * vertices with d2 > Sqr(range[v]); if still empty stage 2, r2 = the largest squared range,
+ * same filter. Result in ascending d2 (nanoflann sorts; ties, unspecified there, go to the
+ * lower vertex id), then Averager (graph/util.h:529-568): average += light * (1 / d2),
+ * total += 1 / d2, in float in that order, for any number of neighbours; empty or total == 0
+ * gives 0, d2 == 0 the reference's infinite weight and NaN. count_out: vertices averaged.
+ * Points outside the grid's box and radii beyond it are handled. */
+typedef struct avr_graph_index avr_graph_index;
+int avr_graph_index_create(long long n, const float *xyz, const float *light_scalar, const float *search_range,
+                           float vertex_radius, avr_graph_index **out);
+int avr_graph_index_destroy(avr_graph_index *idx);
+int avr_graph_index_connect(const avr_graph_index *idx, long long n, const float *points, float *light_out,
+                            int *count_out);
+/* avr_graph_index_connect on the device: the same search routine, one lane per point, with
+ * bitwise the host's results. The index is uploaded on first use and cached on the context
+ * under an id stored in the index (not its address); the copy is released with the context
+ * or when another index is used. Host arrays, synchronous. */
+int avr_graph_connect(avr_context *ctx, const avr_graph_index *idx, long long n, const float *points,
+                      float *light_out, int *count_out);
+/* GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247), for sample indices
+ * [spp_begin, spp_end) of every pixel, added to the film: avr_render's wavefront pass loop
+ * (k_camera, then k_graph_render instead of the path kernels, then k_film; passes of at most
+ * max_paths samples). Per sample: the camera ray crosses the medium's bounds box (the graph
+ * tools' geometry model, DESIGN.md §9: a ray from outside starts at its entry point and
+ * ends at the exit; a camera inside the box, commented out in the reference, tracks from its
+ * origin; a miss gives L = 0), RNG(Hash(Get1D), Hash(Get1D)), SampleT_maj with the next Get1D
+ * and the medium's coefficients at the sample's own wavelengths, the 3-way event choice on
+ * channel 0; the first real scatter p gives L = lightSpectrum.Sample(lambda) *
+ * ConnectToGraph(graph_from_render(p)), lightSpectrum = the distant light's scale * Lemit;
+ * absorption or leaving the box L = 0. graph_from_render: row-major affine 4x4 (the
+ * reference's worldFromRender for a graph in world space), NULL = identity (the graph tools
+ * here work in render space). Requires medium, camera and film, exactly one light of type 0
+ * and no interface sphere / convex (AVR_ERR_STATE otherwise); sample-range and ZSobol limits
+ * as avr_render. Work counters: the avr_stats fields avr_graph_walks uses (shadow_lookups,
+ * shadow_items, shadow_dda_steps); the kernel's time in ms_medium. */
+int avr_graph_render(avr_context *ctx, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                     int spp_end, int seed);
+/* The last pass of the last avr_graph_render, indexed as avr_last_pass_samples (which, with
+ * avr_last_pass_weights, returns that pass's L, wavelengths, pdfs and filter weights): the
+ * camera ray o, d (n*3 each), the scatter point in render space (n*3) and the number of
+ * vertices averaged, -1 when the sample did not scatter. Any output may be NULL.
+ * AVR_ERR_STATE when the last render was avr_render's. */
+int avr_graph_last_pass(avr_context *ctx, float *o, float *d, float *points, int *counts, long long n_max);
+
 /* Per-sample radiance of the LAST wavefront pass of the last avr_render (replay checks;
  * pbrt's --debugstart analogue, integrators.cpp:74-102). Element id = s*W*H + pixel,
  * s = sampleIndex - first sample of that pass. Writes n_max*4 floats into each of

@@ -1,0 +1,111 @@
+"""The graph render end to end on S-cloud (GPU): build the lighting graph of an n^3 S-cloud
+GridMedium lit by its distant light, render 1280x720 with GraphIntegrator at 1 and 16 spp,
+write the 16-spp EXR and a JSON with the render's times (avr_stats ms_medium = k_graph_render,
+ms_total), the vertex count and the neighbour-count histogram of the 1-spp pass. Beside them,
+for context, a VolPathIntegrator render of the same scene and spp at maxdepth = bounces + 1.
+
+usage: python tools/graph_render_demo.py [--n 256] [--out DIR] [--steps 64] [--iterations 8]
+                                         [--radius-modifier 20] [--bounces 10]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(ctx, fn):
+    """Run fn() once to warm up (allocations, the index upload), then once timed."""
+    fn()
+    ctx.sync()
+    ctx.reset_stats()
+    t0 = time.perf_counter()
+    fn()
+    ctx.sync()
+    wall = (time.perf_counter() - t0) * 1e3
+    s = ctx.stats()
+    return {"ms_camera": s["ms_camera"], "ms_medium": s["ms_medium"], "ms_film": s["ms_film"],
+            "ms_total": s["ms_total"], "ms_wall": wall}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--n", type=int, default=256)
+    p.add_argument("--out", default="graph_render_demo")
+    p.add_argument("--steps", type=int, default=64)
+    p.add_argument("--iterations", type=int, default=8)
+    p.add_argument("--max-depth", type=int, default=100)
+    p.add_argument("--radius-modifier", type=float, default=20.0)
+    p.add_argument("--bounces", type=int, default=10)
+    p.add_argument("--width", type=int, default=1280)
+    p.add_argument("--height", type=int, default=720)
+    a = p.parse_args()
+    import torch
+    from acceleratedvolrenderer_amd import GraphIntegrator, VolPathIntegrator, capi, graph, scenes
+    from acceleratedvolrenderer_amd.scene import Scene
+    os.makedirs(a.out, exist_ok=True)
+    density = torch.empty((a.n, a.n, a.n), dtype=torch.float32, device="cuda:0")
+    gen = capi.Context(0)
+    gen.generate_cloud(density.data_ptr(), a.n, 0, a.n ** 3)
+    gen.sync()
+    gen.close()
+    cloud = scenes.s_cloud(density, width=a.width, height=a.height, sampler="zsobol", spp=16, filter="gaussian")
+    scene = Scene(cloud.camera, cloud.film, cloud.medium, cloud.lights[:1], sampler=cloud.sampler)   # the distant light
+
+    integ = GraphIntegrator(scene, None, spp=16, seed=0)
+    cfg = graph.Config(
+        graph.GraphBuilderConfig(radius_modifier=a.radius_modifier, max_depth=a.max_depth, dimension_steps=a.steps,
+                                 iterations_per_step=a.iterations,
+                                 render_search_range={"active": True, "neighboursToUse": 4}),
+        graph.LightingCalculatorConfig(light_iterations=16, points_on_radius_light=2, bounces=[a.bounces]))
+    md = graph.MediumData(scene)
+    in_dir = (-np.asarray(scene.light_w[0], np.float32)).astype(np.float32)   # the way the light travels
+    smp = graph.GraphSampling.for_config(cfg, sampler=0, seed=0)
+    t0 = time.perf_counter()
+    builder = graph.FreeGraphBuilder(integ.ctx, md, in_dir, smp, cfg.graph_builder)
+    g = builder.build_graph()
+    t1 = time.perf_counter()
+    lc = graph.LightingCalculator(integ.ctx, g, md, in_dir, smp, cfg.lighting_calculator)
+    done = lc.compute_final_light()
+    t2 = time.perf_counter()
+    integ.index = g.index(lc.light_scalar)
+    t3 = time.perf_counter()
+
+    out = {"scene": f"S-cloud GridMedium {a.n}^3, distant light, {a.width}x{a.height}, zsobol + gaussian",
+           "graph": {"vertices": int(g.num_vertices), "edges": int(len(g.edge_from)), "vertex_radius": float(g.radius),
+                     "dimension_steps": a.steps, "iterations_per_step": a.iterations, "max_depth": a.max_depth,
+                     "bounces": a.bounces, "bounces_completed": int(done), "search_range_neighbours": 4,
+                     "s_build": t1 - t0, "s_light": t2 - t1, "s_index": t3 - t2}}
+    out["graph_render_1spp"] = timed(integ.ctx, lambda: integ.render(0, 1))
+    npix = a.width * a.height
+    counts = integ.last_pass(1)["count"]
+    hist = np.bincount(counts[counts >= 0])
+    out["neighbours_1spp"] = {"no_scatter": int(np.sum(counts < 0)), "scattered": int(np.sum(counts >= 0)),
+                              "histogram": [int(v) for v in hist], "mean": float(counts[counts >= 0].mean()),
+                              "max": int(counts.max())}
+    out["graph_render_16spp"] = timed(integ.ctx, lambda: integ.render(0, 16))
+    rgb, w = integ.film_sums()
+    img = integ.write_image(os.path.join(a.out, "graph_render_16spp.exr"), rgb, w, spp=16)
+    out["graph_image_mean"] = float(img.mean())
+    integ.close()
+
+    vp = VolPathIntegrator(scene, maxdepth=a.bounces + 1, spp=16, seed=0)
+    out["volpath_1spp"] = timed(vp.ctx, lambda: vp.render(0, 1))
+    out["volpath_16spp"] = timed(vp.ctx, lambda: vp.render(0, 16))
+    out["volpath_maxdepth"] = a.bounces + 1
+    out["volpath_image_mean"] = float(vp.get_image().mean())
+    vp.close()
+    out["Msamples_per_s_16spp"] = {"graph": npix * 16 / out["graph_render_16spp"]["ms_total"] / 1e3,
+                                   "volpath": npix * 16 / out["volpath_16spp"]["ms_total"] / 1e3}
+    with open(os.path.join(a.out, "graph_render_demo.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
