@@ -35,8 +35,19 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # (fresh_params, round 6: 126 -> 107 VGPRs), the hoisting fits (128 VGPRs, no scratch) and wins
 # +0.6 % (profiles/r06_ab_walk.json). `python -m acceleratedvolrenderer_amd.build <variant>
 # --no-licm` builds the old way.
+# The GridMedium units (medium 0) are built without it again: their parked gray instantiations
+# run at 5 waves/SIMD (96 VGPRs), where the hoisted invariants cost 44 B/lane of scratch and
+# without them there is none (tools/kres.py; profiles/kpaths_5waves_ab.json).
 KP_FLAGS = []
 NO_LICM = ["-mllvm", "-disable-machine-licm"]
+KP_MED_FLAGS = {0: NO_LICM}
+
+
+def kp_unit_flags(med):
+    """The extra compiler flags of the k_paths unit of medium kind `med`."""
+    return KP_FLAGS + KP_MED_FLAGS.get(int(med), [])
+
+
 # RCCL for avr_film_reduce_rccl (in-process multi-GPU film reduce)
 LIBS = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
 
@@ -49,7 +60,7 @@ def source_hash(defines=()):
         h.update(os.path.basename(d).encode() + b"\0")
         with open(d, "rb") as f:
             h.update(f.read())
-    h.update(repr((FLAGS, KP_FLAGS, LIBS, KP_UNITS, list(defines))).encode())
+    h.update(repr((FLAGS, KP_FLAGS, KP_MED_FLAGS, LIBS, KP_UNITS, list(defines))).encode())
     return h.hexdigest()
 
 
@@ -86,7 +97,8 @@ def build(force=False, verbose=False, jobs=None, variant=None, defines=(), kp_fl
     units = [(SRC, os.path.join(objdir, "avr_capi.o"), ["-DAVR_KP_SPLIT"] + defines, verbose)]
     for med, fast in KP_UNITS:
         units.append((KPATHS, os.path.join(objdir, f"avr_kpaths_m{med}_f{fast}.o"),
-                      (KP_FLAGS if kp_flags is None else list(kp_flags)) + [f"-DAVR_KP_MED={med}", f"-DAVR_KP_FAST={fast}"]
+                      (kp_unit_flags(med) if kp_flags is None else list(kp_flags))
+                      + [f"-DAVR_KP_MED={med}", f"-DAVR_KP_FAST={fast}"]
                       + defines, verbose))
     jobs = jobs or max(1, min(len(units), int(os.environ.get("MAX_JOBS", os.cpu_count() or 4))))
     with ThreadPoolExecutor(jobs) as ex:

@@ -945,6 +945,56 @@ __device__ __forceinline__ int coop_draws_lds(smp::ZSobol &z, const smp::ZSobolP
     return rank;
 }
 
+// Set bits of a wave mask below the calling lane (v_mbcnt: no lane mask kept in registers)
+__device__ __forceinline__ int mask_rank(uint64_t m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// The same for k_paths' parked instantiations, whose sampler state lives in LDS: s_st holds
+// this wave's states field-major ({morton, hi, dimension}[256], 64 lanes from s_st) and is not
+// copied; s_rl receives the wave's 64 rank -> lane bytes. The lane that evaluates draw j of
+// the requester in lane l hands it to store(l, slot[j], value) (a 2D draw's second value to the
+// slot after it), so the caller decides where lane l's results live; the requesters' dimension
+// advances in LDS.
+template <int kW, int N, typename Store>
+__device__ __forceinline__ void coop_draws_parked(const smp::ZSobolParams &zp, bool req, const int (&off)[N],
+                                                  const bool (&two)[N], const int (&slot)[N], int adv, Store store,
+                                                  uint32_t *s_st, uint8_t *s_rl, const uint64_t *dhash = nullptr,
+                                                  const uint8_t *zpt = nullptr) {
+    const uint64_t mask = __ballot(req);
+    const int lane = lane_id();
+    if (req) s_rl[mask_rank(mask)] = (uint8_t)lane;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int total = __popcll(mask) * N;
+    for (int c = 0; c < total; c += 64) {
+        const int t = c + lane;
+        if (t < total) {
+            const int r = t / N, j = t - r * N;
+            int o = off[0], sl = slot[0];
+            bool tw = two[0];
+            _Pragma("unroll") for (int jj = 1; jj < N; ++jj) {
+                o = j == jj ? off[jj] : o;
+                sl = j == jj ? slot[jj] : sl;
+                tw = j == jj ? two[jj] : tw;
+            }
+            const int l = s_rl[r];
+            smp::ZSobol q;
+            q.morton = s_st[l];
+            q.hi = s_st[256 + l];
+            q.dimension = 0;
+            float v0, v1;
+            q.template draw_at<kW>(zp, s_st[512 + l] + (uint32_t)o, tw, &v0, &v1, dhash, dhash ? kDimHash : 0, zpt);
+            store(l, sl, v0);
+            if (tw) store(l, sl + 1, v1);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (req) s_st[512 + lane] += (uint32_t)adv;
+}
+
 __device__ __forceinline__ const float *base_of(const smp::FilterTables &t) { return t.f; }
 __device__ __forceinline__ float4 to4(V3 v) { return make_float4(v.x, v.y, v.z, 0.f); }
 __device__ __forceinline__ V3 from4(float4 v) { return {v.x, v.y, v.z}; }
@@ -1889,6 +1939,36 @@ __global__ void __launch_bounds__(256) k_bin_scatter(const int *__restrict__ que
 #ifndef AVR_PATHS_WAVES_SPEC
 #define AVR_PATHS_WAVES_SPEC 2   // 4-wavelength state: ~220 VGPRs without scratch
 #endif
+// The parked instantiations (kpaths_parked): 5 waves/SIMD, i.e. <= 96 VGPRs (512 / 5, in
+// allocation blocks of 8) and five 256-lane blocks per CU, <= 32 KiB of LDS each. Development
+// switches, one shipped configuration: AVR_KP_PARK=0 keeps the handler-only state in registers
+// and AVR_KP_BUFMAJ=0 the 16^3 majorant in LDS (either way the parent's 4 waves).
+#ifndef AVR_PATHS_WAVES_PARKED
+#define AVR_PATHS_WAVES_PARKED 5
+#endif
+#ifndef AVR_KP_PARK
+#define AVR_KP_PARK 1
+#endif
+#ifndef AVR_KP_BUFMAJ
+#define AVR_KP_BUFMAJ 1
+#endif
+// Gray GridMedium without emission or image light: the state that only the event handlers and
+// the refill touch (L, the wavelengths, the path direction, the sampler state, the record index
+// and the NEE light) lives in per-lane LDS arrays instead of registers, and the majorant grid
+// is read through a bounds-checked buffer (L2) instead of an LDS copy.
+template <bool kEmissive, bool kGray, int kMed, bool kImage> constexpr bool kpaths_parked() {
+    return AVR_KP_PARK != 0 && kGray && kMed == 0 && !kEmissive && !kImage;
+}
+template <bool kEmissive, bool kGray, int kMed, bool kImage> constexpr bool kpaths_bufmaj() {
+    return kMed == 3 || (AVR_KP_BUFMAJ != 0 && kGray && kMed == 0 && !kEmissive && !kImage);
+}
+// minimum waves per SIMD asked of an instantiation (DESIGN §4 lists what each one gets)
+template <bool kEmissive, bool kGray, int kMed, bool kImage> constexpr int kpaths_waves() {
+    if (kpaths_parked<kEmissive, kGray, kMed, kImage>() && kpaths_bufmaj<kEmissive, kGray, kMed, kImage>())
+        return AVR_PATHS_WAVES_PARKED;
+    if (!kGray) return AVR_PATHS_WAVES_SPEC;
+    return kMed == 1 ? 3 : AVR_PATHS_WAVES_GRAY;
+}
 // Lane events, deferred and handled in batches: a lane that reaches an event parks until
 // enough lanes of its wave need service, so each event handler runs once per batch
 // instead of once per tracking iteration (SQ_INSTS_VALU showed the per-iteration union
@@ -2028,7 +2108,7 @@ struct ProbeStats {
 // escapes); a separate instantiation so the other kernels keep their register budget.
 // kFast: the "fast" render mode (hardware transcendentals, statistical parity); replay otherwise.
 template <bool kEmissive, bool kGray, int kSmp, int kMed, bool kImage, bool kFast>
-__global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_GRAY) : AVR_PATHS_WAVES_SPEC) k_paths(Params Pk) {
+__global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kImage>())) k_paths(Params Pk) {
     const Params &P = Pk;
     // kMed 1: HomogeneousMedium or CloudMedium — dda_init gives their single
     // HomogeneousMajorantIterator segment over a 1^3 majorant of 1.0; properties from sample_point
@@ -2044,7 +2124,9 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
     using S = typename std::conditional<kGray, float, Spec>::type;
     // LDS: majorant grid (16 KiB at pbrt's 16^3) + the 471-entry spectral tables the path
     // samples at path start, NEE and escape (sigma_a, sigma_s, up to 4 light spectra).
-    __shared__ float s_maj[kVdb ? 1 : 4096];
+    // (kBufMaj: read from global memory through a bounds-checked buffer instead, as NanoVDB's is)
+    constexpr bool kBufMaj = kpaths_bufmaj<kEmissive, kGray, kMed, kImage>();
+    __shared__ float s_maj[kBufMaj ? 1 : 4096];
     // (a gray medium's sigma_a / sigma_s are one value each: the kernel takes them as scalars)
     constexpr int kSigTabs = kGray ? 0 : 2;
     constexpr int kLdsLights = 4;
@@ -2052,11 +2134,16 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
     // ImageInfiniteLight shadow rays (non-delta NEE): the sampled (u, v), p_l and the phase
     // value per lane, parked here while the lane traces its shadow ray (off the VGPR budget)
     __shared__ float4 s_img[kImage ? 256 : 1];
+    constexpr bool kParked = kpaths_parked<kEmissive, kGray, kMed, kImage>();
     // ZSobol: the requesters' sampler state for the cooperative draws (coop_draws_lds), 64 per wave
-    __shared__ uint3 s_zst[kSmp != 0 ? 256 : 1];
+    // (parked: the state lives in s_pk, and the draws need the wave's rank -> lane bytes)
+    __shared__ uint3 s_zst[kSmp != 0 && !kParked ? 256 : 1];
+    __shared__ uint8_t s_rl[kSmp != 0 && kParked ? 256 : 1];
     // NEE toward a delta light: the light's spectrum at the path's wavelengths and the phase
     // value f_hat, computed when the shadow ray is spawned and read back when it finishes
-    // (SampleLd evaluates them once, integrators.cpp:1311-1331)
+    // (SampleLd evaluates them once, integrators.cpp:1311-1331). A lane in EV_PHASE traces no
+    // shadow ray: the parked instantiations' cooperative draws put its five phase / segment
+    // results into these slots instead of an s_res of their own
     __shared__ float4 s_ls[256];
     __shared__ float s_fhat[256];
     // ZSobol: Hash(d, seed) of the first kDimHash dimensions — each draw's FastOwen seeds,
@@ -2077,8 +2164,8 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
     // ahead with the previous bounce's cooperative phase draws (or by the camera stage)
     __shared__ float s_ul[kSmp != 0 ? 256 : 1];
     // the host routes GridMedium majorant grids of more than 4096 cells to the wavefront kernels
-    if constexpr (!kVdb) stage_majorant(P.med, s_maj);
-    const float *__restrict__ majp = kVdb ? P.med.majorant : s_maj;
+    if constexpr (!kBufMaj) stage_majorant(P.med, s_maj);
+    const float *__restrict__ majp = kBufMaj ? P.med.majorant : s_maj;
     // NanoVDB: the majorant's coarse occupancy level (one bit per cell pair, 16 KiB at 64^3;
     // 33 + 16 KiB per block keeps three blocks of 256 lanes per CU)
     __shared__ unsigned s_occ[kVdb ? kOccWords : 1];
@@ -2137,8 +2224,37 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
     // ZSobol: the phase handler's draws evaluated cooperatively by the whole wave with their
     // results in LDS (coop_draws_lds), including the next light-pick draw (s_ul)
     constexpr bool kCoopLds = kZSobol;
-    __shared__ float s_res[kCoopLds ? 256 * 6 : 1];
+    __shared__ float s_res[kCoopLds && !kParked ? 256 * 6 : 1];
     PathSampler<kSmp> smp{};
+    // Parked state, [field][lane] (a wave's accesses are conflict-free): a handler loads what it
+    // reads at its top and stores what it changed; between handlers the registers are free.
+    // Sampler state: ZSobol {morton, hi, dimension} (PK_Z), the independent sampler's PCG32
+    // {state, inc} (PK_RNG).
+    enum : int { PK_L = 0, PK_LAM = 4, PK_PD = 8, PK_G = 11, PK_LIGHT = 12, PK_Z = 13, PK_RNG = 13, PK_N = kZSobol ? 16 : 17 };
+    __shared__ float s_pk[kParked ? PK_N * 256 : 1];
+    float *const pk = s_pk + threadIdx.x;
+    [[maybe_unused]] uint32_t *const pkz = reinterpret_cast<uint32_t *>(s_pk) + PK_Z * 256;
+    auto pk_ld4 = [&](int f) { return Spec{pk[f * 256], pk[(f + 1) * 256], pk[(f + 2) * 256], pk[(f + 3) * 256]}; };
+    auto pk_st4 = [&](int f, const Spec &v) {
+        pk[f * 256] = v.v0; pk[(f + 1) * 256] = v.v1; pk[(f + 2) * 256] = v.v2; pk[(f + 3) * 256] = v.v3;
+    };
+    auto pk_ld3 = [&](int f) { return V3{pk[f * 256], pk[(f + 1) * 256], pk[(f + 2) * 256]}; };
+    auto pk_st3 = [&](int f, const V3 &v) { pk[f * 256] = v.x; pk[(f + 1) * 256] = v.y; pk[(f + 2) * 256] = v.z; };
+    auto pk_ldi = [&](int f) { return __float_as_int(pk[f * 256]); };
+    auto pk_sti = [&](int f, int v) { pk[f * 256] = __int_as_float(v); };
+    // the independent sampler's PCG32: state and increment loaded, the state stored back
+    auto pk_ld_rng = [&]() {
+        if constexpr (kParked && !kZSobol) {
+            smp.rng.state = ((uint64_t)(uint32_t)pk_ldi(PK_RNG + 1) << 32) | (uint32_t)pk_ldi(PK_RNG);
+            smp.rng.inc = ((uint64_t)(uint32_t)pk_ldi(PK_RNG + 3) << 32) | (uint32_t)pk_ldi(PK_RNG + 2);
+        }
+    };
+    auto pk_st_rng = [&]() {
+        if constexpr (kParked && !kZSobol) {
+            pk_sti(PK_RNG, (int)(uint32_t)smp.rng.state);
+            pk_sti(PK_RNG + 1, (int)(uint32_t)(smp.rng.state >> 32));
+        }
+    };
     int depth = 0;
     V3 po{}, pd{};         // segment origin (== the path vertex) and the path's ray direction
     // segment state (SampleT_maj)
@@ -2179,11 +2295,18 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             [[maybe_unused]] const DevMedium &m = P.med;
             if (ev == EV_SCATTER) {
                 // SampleLd: light pick (BVH infinite-light branch) + shadow-ray spawn (1282-1338)
+                if constexpr (kParked) {
+                    pd = pk_ld3(PK_PD);
+                    lam = pk_ld4(PK_LAM);
+                    pk_ld_rng();
+                }
                 const V3 wo = -pd;
                 float ul;
                 if constexpr (kZSobol) {
                     ul = s_ul[threadIdx.x];   // drawn ahead (same sampler dimension)
-                    smp.z.dimension += 1;
+                    // (parked: the light pick and uLight in one step, no image light there)
+                    if constexpr (kParked) pkz[512 + threadIdx.x] += 3;
+                    else smp.z.dimension += 1;
                 } else {
                     ul = smp.get1d(P);
                 }
@@ -2191,9 +2314,12 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                 // uLight: read by the image light only; the other instantiations just step the
                 // ZSobol dimension past it (the independent sampler's PCG32 still draws twice)
                 if constexpr (kImage || !kZSobol) smp.get2d(P, &uL0, &uL1);
-                else smp.z.dimension += 2;
+                else if constexpr (!kParked) smp.z.dimension += 2;
+                pk_st_rng();
                 ev = EV_PHASE;                       // unless a shadow ray is spawned
-                L = L + Spec::c(0.f);                // L += SampleLd(...) == 0 if nothing spawns
+                // L += SampleLd(...) == 0 if nothing spawns. (Parked: L stays where it is. The sum
+                // of +0 and round-to-nearest additions is never -0, so adding +0 keeps its bits.)
+                if constexpr (!kParked) L = L + Spec::c(0.f);
                 const int nl = P.lights.n;
                 if (nl > 0) {
                     float pmf = 0.f;
@@ -2237,6 +2363,7 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                                 const V3 pOut = po + wi * (2 * P.lights.scene_radius);
                                 const V3 d = pOut - po;
                                 light = idx;
+                                if constexpr (kParked) pk_sti(PK_LIGHT, idx);
                                 T_ray = sr_l = sr_u = sconst<S>(1.f);
                                 // shadow-ray RNG (integrators.cpp:1338); u is its first draw
                                 seqA = hash_3u32(f2u(po.x), f2u(po.y), f2u(po.z));
@@ -2257,6 +2384,10 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             [[maybe_unused]] const Params &P = fresh_params();
             [[maybe_unused]] const DevMedium &m = P.med;
             if (ev == EV_SHADOW_DONE) {
+                if constexpr (kParked) {
+                    light = pk_ldi(PK_LIGHT);
+                    L = pk_ld4(PK_L);
+                }
                 // finish SampleLd (1379-1398); SampleT_maj returned 1 if the callback stopped
                 const S Tm = shadowStopped ? sconst<S>(1.f) : T_maj;
                 if constexpr (kGray) {
@@ -2290,6 +2421,7 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                     }
                 }
                 L = L + contrib;
+                if constexpr (kParked) pk_st4(PK_L, L);
                 ev = EV_PHASE;
             }
         }
@@ -2301,7 +2433,20 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             // EV_PHASE, evaluated cooperatively by the whole wave
             // (and, at offset 5, the next bounce's light-pick draw, parked in s_ul)
             [[maybe_unused]] const float *qr = nullptr;   // this lane's results in s_res (kCoopLds)
-            if constexpr (kCoopLds) {
+            if constexpr (kCoopLds && kParked) {
+                // [u0, u1] phase 2D, [h0, h1, u] the next segment, [ul] the next light pick:
+                // results 0-3 in the lane's s_ls slot, 4 in s_fhat (both dead while in EV_PHASE), 5 in s_ul
+                constexpr int off[5] = {0, 2, 3, 4, 5};
+                constexpr bool two[5] = {true, false, false, false, false};
+                constexpr int slot[5] = {0, 2, 3, 4, 5};
+                const unsigned wb = threadIdx.x & ~63u;
+                float *const r03 = reinterpret_cast<float *>(s_ls + wb);
+                float *const r4 = s_fhat + wb, *const r5 = s_ul + wb;
+                coop_draws_parked<PathSampler<kSmp>::kW, 5>(
+                    P.zs, ev == EV_PHASE, off, two, slot, 5,
+                    [&](int l, int sl, float v) { *(sl < 4 ? r03 + l * 4 + sl : (sl == 4 ? r4 : r5) + l) = v; },
+                    pkz + wb, s_rl + wb, s_dh, kZpt ? s_zpt : nullptr);
+            } else if constexpr (kCoopLds) {
                 // [u0, u1] phase 2D, [h0, h1, u] the next segment, [ul] the next light pick
                 constexpr int off[5] = {0, 2, 3, 4, 5};
                 constexpr bool two[5] = {true, false, false, false, false};
@@ -2316,8 +2461,17 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             if (ev == EV_PHASE) {
                 // phase-function sampling (integrators.cpp:1046-1061), then the next segment
                 AVR_COUNT(nPhase, 2);
+                if constexpr (kParked) {
+                    pd = pk_ld3(PK_PD);
+                    pk_ld_rng();
+                }
                 float up0, up1;
-                if constexpr (kCoopLds) {
+                [[maybe_unused]] float4 q03{};   // parked: results 0-3
+                if constexpr (kCoopLds && kParked) {
+                    q03 = s_ls[threadIdx.x];
+                    up0 = q03.x;
+                    up1 = q03.y;
+                } else if constexpr (kCoopLds) {
                     up0 = qr[0];
                     up1 = qr[1];
                 } else {
@@ -2331,11 +2485,20 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                     beta = beta * unit_quot(phPdf);
                     r_l = r_u / phPdf;
                     pd = wi;
-                    const float h0 = kCoopLds ? qr[2] : smp.get1d(P);
-                    const float h1 = kCoopLds ? qr[3] : smp.get1d(P);
+                    if constexpr (kParked) pk_st3(PK_PD, pd);
+                    float h0, h1;
+                    if constexpr (kCoopLds && kParked) {
+                        h0 = q03.z;
+                        h1 = q03.w;
+                    } else {
+                        h0 = kCoopLds ? qr[2] : smp.get1d(P);
+                        h1 = kCoopLds ? qr[3] : smp.get1d(P);
+                    }
                     seqA = hash_u32(f2u(h0));
                     seqB = hash_u32(f2u(h1));
-                    u = kCoopLds ? qr[4] : smp.get1d(P);
+                    if constexpr (kCoopLds && kParked) u = s_fhat[threadIdx.x];
+                    else u = kCoopLds ? qr[4] : smp.get1d(P);
+                    pk_st_rng();
                     sd = pd;
                     segPending = true;
                     mode = M_MEDIUM;
@@ -2348,6 +2511,10 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             [[maybe_unused]] const Params &P = fresh_params();
             [[maybe_unused]] const DevMedium &m = P.med;
             if (ev == EV_ESCAPE) {
+                if constexpr (kParked) {
+                    L = pk_ld4(PK_L);
+                    lam = pk_ld4(PK_LAM);
+                }
                 // escaped (integrators.cpp:1078-1107)
                 if constexpr (kGray) {
                     const float q = unit_quot(T_maj);
@@ -2379,6 +2546,7 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                         L = L + smul(Le, beta) / savg(r_u + r_l);
                     }
                 }
+                if constexpr (kParked) pk_st4(PK_L, L);
                 ev = EV_END;
             }
         }
@@ -2386,6 +2554,10 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             [[maybe_unused]] const Params &P = fresh_params();
             [[maybe_unused]] const DevMedium &m = P.med;
             if (ev == EV_END) {
+                if constexpr (kParked) {
+                    L = pk_ld4(PK_L);
+                    g = pk_ldi(PK_G);
+                }
                 // the per-sample record: L (k_film takes the rest from the camera stage)
                 P.ps.rec[g] = to4(L);
                 mode = M_FETCH;
@@ -2422,8 +2594,15 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
             base = __shfl(base, leader);
             granted = __shfl(granted, leader);
             exhausted = __shfl(exhausted, leader);
-            const uint64_t lt = lane == 0 ? 0ull : (needMask & ((~0ull) >> (64 - lane)));
-            const int k = __popcll(lt);
+            // (parked: v_mbcnt, no lane mask carried in registers; the other instantiations keep
+            // the mask their register allocation was tuned with)
+            int k;
+            if constexpr (kParked) {
+                k = mask_rank(needMask);
+            } else {
+                const uint64_t lt = lane == 0 ? 0ull : (needMask & ((~0ull) >> (64 - lane)));
+                k = __popcll(lt);
+            }
             const bool fresh = mode == M_FETCH && k < granted;
             if (mode == M_FETCH) {
                 if (fresh) {
@@ -2442,7 +2621,10 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                         // the sample's ZSobol state past the camera draws and the first segment's three
                         // (hardware-sequence divisions: FastDiv splits here measured 1.2 % slower in
                         // k_paths, profiles/r05_ab_unit_quot_fastdiv.json; the camera stage keeps them)
-                        const int slot = g % npix, sIdx = g / npix;
+                        // (parked: the pixel count re-read here, so that its reciprocal is not
+                        // carried in a register through the whole kernel)
+                        const int np = kParked ? P.pass_pixels : npix;
+                        const int slot = g % np, sIdx = g / np;
                         const int pix = P.pix_order ? P.pix_order[slot] : slot;
                         smp.start(P, pix % P.film.width, pix / P.film.width, P.sample_base + sIdx);
                         s_ul[threadIdx.x] = ul5;
@@ -2469,6 +2651,21 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                         if (kEmissive && (kMed == 0 || kMed == 1)) Le_l = sample_table(m.Le, li);
                     }
                     sd = pd;
+                    if constexpr (kParked) {
+                        pk_st4(PK_L, L);
+                        pk_st4(PK_LAM, lam);
+                        pk_st3(PK_PD, pd);
+                        pk_sti(PK_G, g);
+                        if constexpr (kZSobol) {
+                            pkz[threadIdx.x] = smp.z.morton;
+                            pkz[256 + threadIdx.x] = smp.z.hi;
+                            pkz[512 + threadIdx.x] = smp.z.dimension;
+                        } else {
+                            pk_st_rng();
+                            pk_sti(PK_RNG + 2, (int)(uint32_t)smp.rng.inc);
+                            pk_sti(PK_RNG + 3, (int)(uint32_t)(smp.rng.inc >> 32));
+                        }
+                    }
                     segPending = true;
                     mode = M_MEDIUM;
                 } else if (exhausted) {
@@ -2549,10 +2746,13 @@ __global__ void __launch_bounds__(256, kGray ? (kMed == 1 ? 3 : AVR_PATHS_WAVES_
                 nStepsW += __popcll(__ballot(stepped));
                 // unconditional (all busy lanes): in flight during the candidate test below
                 // (the next cell's index is unclamped: LDS for the 16^3 majorants, a bounds-checked
-                // buffer for NanoVDB's — +0.9 % grid, +2.2 % NanoVDB, profiles/r06_ab_walk.json)
+                // buffer for NanoVDB's and the parked instantiations' — +0.9 % grid, +2.2 % NanoVDB,
+                // profiles/r06_ab_walk.json)
                 if constexpr (kVdb) {
                     if (useOcc) ddal_prefetch_occ_buf(it, majr, s_occ, maj_n);
                     else ddal_prefetch_buf(it, majr);
+                } else if constexpr (kBufMaj) {
+                    ddal_prefetch_buf(it, majr);
                 } else {
                     ddal_prefetch(it, majp);
                 }

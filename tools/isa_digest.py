@@ -63,7 +63,7 @@ def main():
     defs += ["-I" + os.path.join(root, "include")]
     units = [(src, ["-DAVR_KP_SPLIT"] + defs, "capi")]
     for med, fast in B.KP_UNITS:
-        units.append((kpaths, B.KP_FLAGS + [f"-DAVR_KP_MED={med}", f"-DAVR_KP_FAST={fast}"] + defs, f"kp_m{med}_f{fast}"))
+        units.append((kpaths, B.kp_unit_flags(med) + [f"-DAVR_KP_MED={med}", f"-DAVR_KP_FAST={fast}"] + defs, f"kp_m{med}_f{fast}"))
     with tempfile.TemporaryDirectory(prefix="avr_isa_") as tmp:
         with ThreadPoolExecutor(min(len(units), os.cpu_count() or 4)) as ex:
             res = list(ex.map(unit_asm, [(s, f, t, tmp) for s, f, t in units]))
