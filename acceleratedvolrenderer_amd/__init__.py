@@ -16,6 +16,7 @@ from .integrator import VolPathIntegrator, shard_samples, INTEGRATOR_NAMES
 from . import capi
 from . import scenes
 from . import graph
+from . import graph_io
 from .capi import GraphIndex
 from .graph import GraphIntegrator
 
@@ -23,4 +24,4 @@ __all__ = ["spectra", "transform", "GridMedium", "DistantLight", "UniformInfinit
            "PerspectiveCamera", "RGBFilm", "Scene", "film_rgb", "VolPathIntegrator", "shard_samples",
            "INTEGRATOR_NAMES", "capi", "scenes", "HomogeneousMedium", "CloudMedium", "NanoVDBMedium", "NanoVDBGrid", "RGBGridMedium", "RGBToSpectrumTable",
            "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler",
-           "graph", "GraphIndex", "GraphIntegrator"]
+           "graph", "graph_io", "GraphIndex", "GraphIntegrator"]

@@ -213,6 +213,10 @@ SIGNATURES = {
     "avr_graph_index_connect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p, c_int_p]),
     "avr_graph_connect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p,
                                          c_int_p]),
+    "avr_graph_index_knn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_float_p]),
+    "avr_graph_index_search_ranges": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p]),
+    "avr_graph_knn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_int_p, c_float_p]),
+    "avr_graph_search_ranges": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_float_p]),
     "avr_graph_render": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int]),
     "avr_graph_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int_p,
@@ -609,6 +613,21 @@ class Context:
         _check(self.lib.avr_graph_connect(self.h, index.h, len(p), _fp(p), _fp(light), counts.ctypes.data_as(c_int_p)))
         return light, counts
 
+    def graph_knn(self, index, k):
+        """GetNClosest for every vertex on the device: (ids, d2), (n, k) each, row = vertex id;
+        bitwise GraphIndex.knn's."""
+        ids = np.zeros((index.num_vertices, max(int(k), 0)), np.int32)
+        d2 = np.zeros(ids.shape, np.float32)
+        _check(self.lib.avr_graph_knn(self.h, index.h, int(k), ids.ctypes.data_as(c_int_p), _fp(d2)))
+        return ids, d2
+
+    def graph_search_ranges(self, index, k):
+        """ComputeSearchRanges on the device: renderSearchRange per vertex id, bitwise
+        GraphIndex.search_ranges'."""
+        out = np.zeros(index.num_vertices, np.float32)
+        _check(self.lib.avr_graph_search_ranges(self.h, index.h, int(k), _fp(out)))
+        return out
+
     def graph_render(self, index, spp_begin, spp_end, seed, graph_from_render=None):
         """GraphIntegrator::Li (free graph) for sample indices [spp_begin, spp_end) into the film."""
         m = None if graph_from_render is None else np.ascontiguousarray(graph_from_render, np.float32).reshape(16)
@@ -770,6 +789,20 @@ class GraphIndex:
         counts = np.zeros(len(p), np.int32)
         _check(self.lib.avr_graph_index_connect(self.h, len(p), _fp(p), _fp(light), counts.ctypes.data_as(c_int_p)))
         return light, counts
+
+    def knn(self, k):
+        """GetNClosest for every vertex on the host: the k nearest other vertices in ascending
+        (d2, id), as (ids, d2), (n, k) each, row = vertex id."""
+        ids = np.zeros((self.num_vertices, max(int(k), 0)), np.int32)
+        d2 = np.zeros(ids.shape, np.float32)
+        _check(self.lib.avr_graph_index_knn(self.h, int(k), ids.ctypes.data_as(c_int_p), _fp(d2)))
+        return ids, d2
+
+    def search_ranges(self, k):
+        """ComputeSearchRanges on the host: renderSearchRange per vertex id."""
+        out = np.zeros(self.num_vertices, np.float32)
+        _check(self.lib.avr_graph_index_search_ranges(self.h, int(k), _fp(out)))
+        return out
 
     def close(self):
         if self.h:

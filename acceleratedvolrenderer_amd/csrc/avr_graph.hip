@@ -18,6 +18,9 @@
 //                  previous bounce's vector is added to the total in the same pass.
 //  k_graph_connect GraphIntegrator::ConnectToGraph (graph_integrator.cpp:249-280) for a batch
 //                  of graph-space points: index_connect (avr_graph_index.h), one lane per point.
+//  k_graph_knn     FreeGraphBuilder::ComputeSearchRanges (free_graph_builder.cpp:473-548):
+//  k_graph_range_average  index_knn per vertex (one lane per sorted slot) with the first
+//                  Averager level, then the second level over each vertex's neighbours.
 //  k_graph_render  GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247): one
 //                  lane per camera record of the pass; delta tracking to the first real
 //                  scatter, then the same index_connect.
@@ -373,6 +376,30 @@ __global__ void __launch_bounds__(256) k_graph_connect(graph::IndexView ix, long
         light[i] = graph::index_connect(ix, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], buf, &cnt, &stage);
         count[i] = cnt;
     }
+}
+
+// GetNClosest for every vertex (avr_graph_knn, avr_graph_search_ranges): index_knn, one lane
+// per sorted slot, so that the lanes of a wave scan the same cells; row id[slot] of ids / d2
+// (k each) gets the result, and avg[id[slot]] (when given) the first Averager level over the
+// row this lane has just written. The sorted buffer is index_connect's, in LDS.
+__global__ void __launch_bounds__(256) k_graph_knn(graph::IndexView ix, int n, int k, int *__restrict__ ids,
+                                                   float *__restrict__ d2, float *__restrict__ avg) {
+    __shared__ float s_d2[graph::kConnectBuf * 256];
+    __shared__ int s_slot[graph::kConnectBuf * 256];
+    ConnectBufLds buf{s_d2 + threadIdx.x, s_slot + threadIdx.x};
+    for (long long s = blockIdx.x * (long long)blockDim.x + threadIdx.x; s < n; s += (long long)gridDim.x * blockDim.x) {
+        const int id = ix.id[s];
+        float *row = d2 + (size_t)id * (size_t)k;
+        (void)graph::index_knn(ix, (int)s, k, buf, ids + (size_t)id * (size_t)k, row);
+        if (avg) avg[id] = graph::index_knn_average(row, k);
+    }
+}
+
+// ComputeSearchRanges' second Averager level: one lane per vertex gathers its neighbours' avg
+__global__ void __launch_bounds__(256) k_graph_range_average(int n, int k, const int *__restrict__ ids,
+                                                             const float *__restrict__ avg, float *__restrict__ range) {
+    for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < n; v += (long long)gridDim.x * blockDim.x)
+        range[v] = graph::index_range_average(avg, (int)v, ids + (size_t)v * (size_t)k, k);
 }
 
 // GraphIntegrator::Li, free graph (graph_integrator.cpp:180-247), after k_camera: the camera

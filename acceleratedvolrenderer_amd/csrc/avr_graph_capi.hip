@@ -463,6 +463,98 @@ int avr_graph_connect(avr_context *c, const avr_graph_index *idx, long long n, c
     return AVR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// k <= kConnectBuf - 1 (the vertex itself takes one buffer entry) and k <= n - 1
+int knn_arguments(const avr_graph_index *idx, int k) {
+    if (!idx) return fail(AVR_ERR_ARG, "null graph index");
+    if (k < 1 || k > avr::graph::kConnectBuf - 1) return fail(AVR_ERR_ARG, "graph knn: k must be 1..15");
+    if ((size_t)k > idx->ix.NumVertices() - 1)
+        return fail(AVR_ERR_ARG, "graph knn: Graph does not contain enough vertices (k <= n - 1)");
+    return AVR_OK;
+}
+
+// k_graph_knn (+ k_graph_range_average when `ranges`) over the context's index copy
+int graph_knn_device(avr_context *c, const avr_graph_index *idx, int k, int *ids, float *d2, float *ranges) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_graph_index(c, idx);
+    if (rc) return rc;
+    const int n = (int)idx->ix.NumVertices();
+    const size_t szK = (size_t)n * (size_t)k * 4, szN = (size_t)n * 4;
+    char *buf = nullptr;
+    HIP_TRY(dalloc(&buf, 2 * szK + 2 * szN));
+    int *dIds = (int *)buf;
+    float *dD2 = (float *)(buf + szK), *dAvg = (float *)(buf + 2 * szK), *dRange = (float *)(buf + 2 * szK + szN);
+    const int blocks = blocks_for(n, 256, 256 * 64);
+    // the kernels' times go to avr_stats: k_graph_knn to ms_medium, k_graph_range_average to ms_film
+    int ev[3] = {-1, -1, -1};
+    rc = next_event(c, &ev[0]);
+    hipError_t e = hipSuccess;
+    if (rc == AVR_OK) {
+        hipLaunchKernelGGL(avr::k_graph_knn, dim3(blocks), dim3(256), 0, c->stream, c->gidx, n, k, dIds, dD2,
+                           ranges ? dAvg : nullptr);
+        e = hipGetLastError();
+    }
+    if (rc == AVR_OK && e == hipSuccess) rc = next_event(c, &ev[1]);
+    if (rc == AVR_OK && e == hipSuccess && ranges) {
+        hipLaunchKernelGGL(avr::k_graph_range_average, dim3(blocks), dim3(256), 0, c->stream, n, k, dIds, dAvg, dRange);
+        e = hipGetLastError();
+        if (e == hipSuccess) rc = next_event(c, &ev[2]);
+    }
+    if (rc != AVR_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(buf);
+        return rc;
+    }
+    if (e == hipSuccess) {
+        c->timed.push_back({ev[0], ev[1], &avr_stats::ms_medium, true});
+        if (ranges) c->timed.push_back({ev[1], ev[2], &avr_stats::ms_film, false});
+    }
+    if (e == hipSuccess && ids) e = hipMemcpyAsync(ids, dIds, szK, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && d2) e = hipMemcpyAsync(d2, dD2, szK, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && ranges) e = hipMemcpyAsync(ranges, dRange, szN, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph knn: ") + hipGetErrorString(e));
+    return AVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int avr_graph_index_knn(const avr_graph_index *idx, int k, int *ids, float *d2) {
+    int rc = knn_arguments(idx, k);
+    if (rc) return rc;
+    if (!ids && !d2) return fail(AVR_ERR_ARG, "null buffer");
+    idx->ix.Knn(k, ids, d2);
+    return AVR_OK;
+}
+int avr_graph_index_search_ranges(const avr_graph_index *idx, int k, float *ranges) {
+    int rc = knn_arguments(idx, k);
+    if (rc) return rc;
+    if (!ranges) return fail(AVR_ERR_ARG, "null buffer");
+    idx->ix.SearchRanges(k, ranges);
+    return AVR_OK;
+}
+int avr_graph_knn(avr_context *c, const avr_graph_index *idx, int k, int *ids, float *d2) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    int rc = knn_arguments(idx, k);
+    if (rc) return rc;
+    if (!ids && !d2) return fail(AVR_ERR_ARG, "null buffer");
+    return graph_knn_device(c, idx, k, ids, d2, nullptr);
+}
+int avr_graph_search_ranges(avr_context *c, const avr_graph_index *idx, int k, float *ranges) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    int rc = knn_arguments(idx, k);
+    if (rc) return rc;
+    if (!ranges) return fail(AVR_ERR_ARG, "null buffer");
+    return graph_knn_device(c, idx, k, nullptr, nullptr, ranges);
+}
+
 int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
                      int spp_end, int seed) {
     if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");

@@ -26,6 +26,11 @@
 // at most), with the monotone cell function the vertices were sorted by: no vertex whose
 // computed d2 qualifies is outside the cells visited, for queries outside the box and radii
 // beyond it too.
+//
+// k nearest neighbours: FreeGraphBuilder::ComputeSearchRanges (free_graph_builder.cpp:473-548)
+// over the same cells, buffer and key order: index_knn, for the host (avr_graph_index_knn,
+// avr_graph_index_search_ranges) and for the device (k_graph_knn), and the two Averager
+// levels that turn the distances into renderSearchRange.
 #pragma once
 
 #include <algorithm>
@@ -148,6 +153,61 @@ AVR_HD float index_connect(const IndexView &ix, float qx, float qy, float qz, Bu
     return average / totalWeight;
 }
 
+// FreeGraphBuilder::GetNClosest (free_graph_builder.cpp:473-496) for the vertex in sorted
+// slot `slot`: its k <= kConnectBuf - 1 nearest other vertices in ascending key (d2, id), ids
+// to ids_out[0..k) and squared distances to d2_out[0..k) (either may be null). The reference
+// queries k + 1, sorts and drops item 0, the vertex itself; here the vertex is left out by
+// id, which is the same unless another vertex coincides with it. The radius starts at the
+// cell edge and doubles until k + 1 vertices (the vertex included) have d2 < r2: every vertex
+// outside that radius is then farther than all of them, ties included. The loop ends when r2
+// overflows to +inf, where every finite d2 qualifies: an isolated vertex costs one scan per
+// doubling, and a radius beyond the grid's box scans the whole grid. Returns the neighbours
+// found: k, or fewer when squared distances overflow float (the rest: id -1, d2 +inf).
+template <typename Buf>
+AVR_HD int index_knn(const IndexView &ix, int slot, int k, Buf &buf, int *ids_out, float *d2_out) {
+    const IndexRec q = ix.rec[slot];
+    const int self = ix.id[slot];
+    const float edge = (float)(1.0 / ix.inv_cell);
+    float r2 = edge * edge;
+    if (!(r2 >= 1.17549435e-38f)) r2 = 1.17549435e-38f;   // a square that underflowed must still double
+    int m = 0;
+    while (true) {
+        (void)index_collect(ix, q.x, q.y, q.z, r2, false, -1.f, -1, buf, &m);
+        if (m >= k + 1 || !(r2 < INFINITY)) break;
+        r2 *= 4.f;
+    }
+    int found = 0;
+    for (int i = 0; i < m && found < k; ++i) {
+        const int id = ix.id[buf.slot(i)];
+        if (id == self) continue;
+        if (ids_out) ids_out[found] = id;
+        if (d2_out) d2_out[found] = buf.d2(i);
+        ++found;
+    }
+    for (int i = found; i < k; ++i) {
+        if (ids_out) ids_out[i] = -1;
+        if (d2_out) d2_out[i] = INFINITY;
+    }
+    return found;
+}
+
+// ComputeSearchRanges' first Averager level (free_graph_builder.cpp:521-529, graph/util.h:
+// 551-568): the float sum from 0 of sqrt(d2[i]), i ascending, over (float)k
+AVR_HD float index_knn_average(const float *d2, int k) {
+    float sum = 0.f;
+    for (int i = 0; i < k; ++i) sum += __builtin_sqrtf(d2[i]);
+    return sum / (float)k;
+}
+
+// ... and its second (:533-544): avg[v], then avg of v's neighbours in result order, over
+// (float)(k + 1). A neighbour that was not found (id -1) counts as +inf.
+AVR_HD float index_range_average(const float *avg, int v, const int *nb, int k) {
+    float sum = 0.f;
+    sum += avg[v];
+    for (int i = 0; i < k; ++i) sum += nb[i] >= 0 ? avg[nb[i]] : INFINITY;
+    return sum / (float)(k + 1);
+}
+
 // The sorted-key buffer in ordinary memory (the host's; the device keeps it in LDS)
 struct ConnectBufLocal {
     float d[kConnectBuf];
@@ -255,6 +315,27 @@ class Index {
             if (light) light[i] = l;
             if (count) count[i] = cnt;
         }
+    }
+
+    // GetNClosest for every vertex: row v of ids / d2 (k each) holds vertex v's neighbours
+    void Knn(int k, int *ids, float *d2) const {
+        const IndexView v = View();
+        const int n = (int)rec_.size();
+        for (int s = 0; s < n; ++s) {
+            ConnectBufLocal buf;
+            const size_t row = (size_t)id_[(size_t)s] * (size_t)k;
+            (void)index_knn(v, s, k, buf, ids ? ids + row : nullptr, d2 ? d2 + row : nullptr);
+        }
+    }
+
+    // ComputeSearchRanges (free_graph_builder.cpp:498-548): renderSearchRange per vertex id
+    void SearchRanges(int k, float *ranges) const {
+        const size_t n = rec_.size();
+        std::vector<int> nb(n * (size_t)k);
+        std::vector<float> d2(n * (size_t)k), avg(n);
+        Knn(k, nb.data(), d2.data());
+        for (size_t v = 0; v < n; ++v) avg[v] = index_knn_average(&d2[v * (size_t)k], k);
+        for (size_t v = 0; v < n; ++v) ranges[v] = index_range_average(avg.data(), (int)v, &nb[v * (size_t)k], k);
     }
 
     size_t NumVertices() const { return rec_.size(); }

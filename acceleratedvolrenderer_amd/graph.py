@@ -28,16 +28,22 @@ C++), and GraphIntegrator renders with it on the GPU: per camera sample the firs
 scatter in the medium is connected to the vertices within the vertex radius (or, with
 renderSearchRange active, within their search ranges), weighted by inverse squared distance
 (k_graph_render). build_graph -> LightingCalculator.compute_final_light -> index ->
-GraphIntegrator.render is the whole pipeline; the graph is handed over in memory.
+GraphIntegrator.render is the whole pipeline; the graph is handed over in memory, or through
+a file in the reference's format (FreeGraph.save, load_index, GraphIntegrator.from_file;
+graph_io.py), which the fork's graph_maker and `pbrt --graph` write and read too.
 
-Not mirrored: the graph's text file format, the uniform-graph branch, --graph-debug.
+ComputeSearchRanges (:473-548) has three forms: compute_search_ranges (a float64 k-d tree,
+the default), and compute_search_ranges_host / _device, which follow the reference's float
+arithmetic and order over the vertex index (k_graph_knn, k_graph_range_average on the GPU).
+
+Not mirrored: the uniform-graph branch, --graph-debug.
 """
 import json
 import math
 
 import numpy as np
 
-from . import capi
+from . import capi, graph_io
 from .integrator import FilmIntegrator
 from .scene import GBufferFilm
 
@@ -235,11 +241,37 @@ class FreeGraph:
         (useRenderSearchRange)."""
         return capi.GraphIndex(self.points, light_scalar, self.search_range, radius=self.radius)
 
+    def save(self, path, light_scalar, description="basic", precision=9, edges=False):
+        """Graph::WriteToDisk as graph_maker calls it (graph_io.write_graph): the vertices with
+        `light_scalar` and, when computed, their search ranges, in the reference's file format."""
+        graph_io.write_graph(path, self, light_scalar, description=description, precision=precision, edges=edges)
+
+
+def load_index(path):
+    """The render's vertex index from a graph file (FreeGraph::ReadFromDisk followed by
+    GraphIntegrator::Initialize): its points, lightScalar, renderSearchRange where present, and
+    vertex radius. Raises on a uniform graph and on a file written without lighting."""
+    g = graph_io.read_graph(path)
+    if g.kind != "free":
+        raise ValueError(f"{path}: a {g.kind} graph; the render takes free graphs")
+    if g.light_scalar is None:
+        raise ValueError(f"{path}: written without lighting (useLighting False): nothing to render")
+    if g.num_vertices == 0:
+        raise ValueError(f"{path}: no vertices")
+    return capi.GraphIndex(g.points, g.light_scalar, g.search_range, radius=g.radius)
+
 
 class FreeGraphBuilder:
     """FreeGraphBuilder (free/free_graph_builder.cpp): walks on the GPU, merge on the host."""
 
-    def __init__(self, ctx, medium_data, in_direction, sampling, config, node_radius=None, sample_index_offset=0):
+    def __init__(self, ctx, medium_data, in_direction, sampling, config, node_radius=None, sample_index_offset=0,
+                 search_ranges="scipy"):
+        """search_ranges: how ComputeSearchRanges runs: "scipy" (compute_search_ranges, the
+        float64 k-d tree), "host" or "device" (compute_search_ranges_host / _device: the
+        reference's float arithmetic over the vertex index; the two agree bitwise)."""
+        if search_ranges not in ("scipy", "host", "device"):
+            raise ValueError('search_ranges must be "scipy", "host" or "device"')
+        self.search_ranges = search_ranges
         self.ctx = ctx
         self.md = medium_data
         self.in_dir = np.asarray(in_direction, f32)
@@ -279,7 +311,9 @@ class FreeGraphBuilder:
         return (np.array(o, f32).reshape(n, 3), np.tile(d, (n, 1)).astype(f32), np.array(t, f32),
                 np.array(idx, np.int64))
 
-    def build_graph(self):
+    def build_graph(self, search_ranges=True):
+        """BuildGraph (:143-214). search_ranges=False leaves ComputeSearchRanges to a later
+        compute_search_ranges(graph) call (tools/graph_maker.py times the two apart)."""
         c = self.config
         o, d, t, idx = self.start_rays()
         pts, counts = self.ctx.graph_walks(self.sampling.struct(), o, d, t, idx, c.iterations_per_step,
@@ -288,9 +322,23 @@ class FreeGraphBuilder:
         g.add_walks(pts, counts, c.max_depth)
         self.reinforce_cycles = self.reinforce_sparse_vertices(g)
         graph = FreeGraph(g, self.radius)
-        if c.render_search_range.get("active"):
-            graph.search_range = compute_search_ranges(graph.points, int(c.render_search_range["neighboursToUse"]))
+        if search_ranges:
+            self.compute_search_ranges(graph)
         return graph
+
+    def compute_search_ranges(self, graph):
+        """ComputeSearchRanges (:498-548), BuildGraph's last step: sets graph.search_range when
+        renderSearchRange is active, in the form the constructor's `search_ranges` names."""
+        c = self.config
+        if not c.render_search_range.get("active"):
+            return
+        k = int(c.render_search_range["neighboursToUse"])
+        if self.search_ranges == "device":
+            graph.search_range = compute_search_ranges_device(self.ctx, graph.points, self.radius, k)
+        elif self.search_ranges == "host":
+            graph.search_range = compute_search_ranges_host(graph.points, self.radius, k)
+        else:
+            graph.search_range = compute_search_ranges(graph.points, k)
 
 
     def _reinforce(self, g, ids, cfg, cycle):
@@ -364,9 +412,39 @@ class FreeGraphBuilder:
     max_reinforce_cycles = 64
 
 
+def _search_range_index(points, radius, n_closest):
+    points = np.ascontiguousarray(points, f32).reshape(-1, 3)
+    if n_closest > len(points):
+        raise ValueError("Graph does not contain enough vertices")
+    return capi.GraphIndex(points, np.zeros(len(points), f32), None, radius=radius)
+
+
+def compute_search_ranges_host(points, radius, n_closest):
+    """FreeGraphBuilder::ComputeSearchRanges (:473-548) in the reference's float arithmetic
+    and order, on the host: a vertex index over `points` (cell edge from `radius`, the vertex
+    radius; zero light) and avr_graph_index_search_ranges. n_closest <= min(15, n - 1)."""
+    idx = _search_range_index(points, radius, n_closest)
+    try:
+        return idx.search_ranges(int(n_closest))
+    finally:
+        idx.close()
+
+
+def compute_search_ranges_device(ctx, points, radius, n_closest):
+    """compute_search_ranges_host on the GPU (k_graph_knn, k_graph_range_average), with
+    bitwise its values."""
+    idx = _search_range_index(points, radius, n_closest)
+    try:
+        return ctx.graph_search_ranges(idx, int(n_closest))
+    finally:
+        idx.close()
+
+
 def compute_search_ranges(points, n_closest):
     """FreeGraphBuilder::ComputeSearchRanges (:486-548): the average distance to the
-    n closest other vertices, averaged again over the vertex and those neighbours."""
+    n closest other vertices, averaged again over the vertex and those neighbours. The
+    legacy form: a float64 k-d tree query with numpy means (compute_search_ranges_host /
+    _device follow the reference's float arithmetic and order)."""
     n = len(points)
     if n_closest > n:
         raise ValueError("Graph does not contain enough vertices")
@@ -434,6 +512,12 @@ class GraphIntegrator(FilmIntegrator):
         self.graph_from_render = None if graph_from_render is None else np.asarray(graph_from_render, f32).reshape(4, 4)
         self.ctx = capi.Context(device, max_paths)
         self.ctx.set_scene(scene)
+
+    @classmethod
+    def from_file(cls, scene, path, **kw):
+        """The integrator over a graph file (`pbrt --graph`): load_index(path), then the
+        constructor's keywords."""
+        return cls(scene, load_index(path), **kw)
 
     def _render_range(self, spp_begin, spp_end):
         self.ctx.graph_render(self.index, spp_begin, spp_end, self.seed, self.graph_from_render)

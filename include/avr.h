@@ -544,6 +544,31 @@ int avr_graph_index_connect(const avr_graph_index *idx, long long n, const float
  * or when another index is used. Host arrays, synchronous. */
 int avr_graph_connect(avr_context *ctx, const avr_graph_index *idx, long long n, const float *points,
                       float *light_out, int *count_out);
+/* FreeGraphBuilder::GetNClosest and ComputeSearchRanges (free_graph_builder.cpp:473-548) over
+ * the index; host code, no GPU needed (the index's light scalars and ranges play no part).
+ * avr_graph_index_knn: per vertex its k nearest other vertices, row = vertex id, k entries
+ * each of ids and d2, in ascending key (d2, id); d2 = ((dx^2 + dy^2) + dz^2) in float as above.
+ * The reference asks nanoflann for k + 1, sorts and drops item 0 (the vertex itself); here the
+ * vertex is left out by id, the same unless another vertex coincides with it exactly, and
+ * equal distances, which nanoflann leaves unspecified, go to the lower id. The search radius
+ * starts at the cell edge and doubles until k + 1 vertices lie strictly inside it, for
+ * isolated vertices and radii beyond the grid too. ids or d2 may be NULL where only the other
+ * is wanted. A neighbour whose float d2 overflows is not found (id -1, d2 +inf).
+ * avr_graph_index_search_ranges: renderSearchRange per vertex id (n floats) from two
+ * Averager levels (graph/util.h:551-568) in float: avg[v] = the sum from 0 of sqrtf(d2[v][i]),
+ * i ascending, over (float)k; range[v] = (avg[v] + avg[nb[v][0]] + ... + avg[nb[v][k-1]]),
+ * summed in that order from 0, over (float)(k + 1).
+ * AVR_ERR_ARG: k < 1, k > 15 (the sorted buffer holds 16 keys, the vertex included),
+ * k > n - 1, null buffers. The reference accepts k == n and then reads neighbours[-1];
+ * refusing it is a deviation. */
+int avr_graph_index_knn(const avr_graph_index *idx, int k, int *ids, float *d2);
+int avr_graph_index_search_ranges(const avr_graph_index *idx, int k, float *ranges);
+/* The same on the device (k_graph_knn: one lane per sorted vertex, the sorted buffer in LDS;
+ * k_graph_range_average: one lane per vertex), with bitwise the host's results. Reuses the
+ * context's cached copy of the index as avr_graph_connect does. Host arrays, synchronous.
+ * Kernel times: k_graph_knn adds to avr_stats ms_medium, k_graph_range_average to ms_film. */
+int avr_graph_knn(avr_context *ctx, const avr_graph_index *idx, int k, int *ids, float *d2);
+int avr_graph_search_ranges(avr_context *ctx, const avr_graph_index *idx, int k, float *ranges);
 /* GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247), for sample indices
  * [spp_begin, spp_end) of every pixel, added to the film: avr_render's wavefront pass loop
  * (k_camera, then k_graph_render instead of the path kernels, then k_film; passes of at most
