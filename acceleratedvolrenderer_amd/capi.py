@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AVR_LIB", os.path.join(_HERE, "libavr_hip.so"))
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int_p = ctypes.POINTER(ctypes.c_int)
+c_u64_p = ctypes.POINTER(ctypes.c_ulonglong)
 
 
 class AvrStats(ctypes.Structure):
@@ -221,6 +222,16 @@ SIGNATURES = {
                                         ctypes.c_int]),
     "avr_graph_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int_p,
                                            ctypes.c_longlong]),
+    "avr_graph_index_coverage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_int_p, c_int_p,
+                                                c_float_p]),
+    "avr_graph_coverage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_int_p,
+                                          c_int_p, c_float_p]),
+    "avr_graph_analyze": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "avr_graph_analysis_read": (ctypes.c_int, [ctypes.c_void_p, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_double_p]),
+    "avr_graph_analysis_clear": (ctypes.c_int, [ctypes.c_void_p]),
+    "avr_graph_analyze_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p,
+                                                   c_int_p, c_float_p, ctypes.c_longlong, ctypes.c_int]),
 }
 
 _lib = None
@@ -642,6 +653,50 @@ class Context:
         _check(self.lib.avr_graph_last_pass(self.h, _fp(o), _fp(d), _fp(pts), counts.ctypes.data_as(c_int_p), n))
         return o, d, pts, counts
 
+    def graph_coverage(self, index, points):
+        """IntegrationAnalyzer's Analyze on the device for (n, 3) graph-space points: (node,
+        in_range, range_sum), bitwise GraphIndex.coverage's."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        node = np.zeros(len(p), np.int32)
+        in_range = np.zeros(len(p), np.int32)
+        range_sum = np.zeros(len(p), np.float32)
+        _check(self.lib.avr_graph_coverage(self.h, index.h, len(p), _fp(p), node.ctypes.data_as(c_int_p),
+                                           in_range.ctypes.data_as(c_int_p), _fp(range_sum)))
+        return node, in_range, range_sum
+
+    def graph_analyze(self, index, spp_begin, spp_end, seed, max_depth, graph_from_render=None, detail=False):
+        """IntegrationAnalyzer::AnalyzeRay for sample indices [spp_begin, spp_end), added to the
+        per-pixel sums (graph_analysis_read); detail keeps the last pass's scatters too."""
+        m = None if graph_from_render is None else np.ascontiguousarray(graph_from_render, np.float32).reshape(16)
+        _check(self.lib.avr_graph_analyze(self.h, index.h, _fp(m), int(spp_begin), int(spp_end), int(seed),
+                                          int(max_depth), 1 if detail else 0))
+
+    def graph_analysis_read(self, npix):
+        """The analysis' per-pixel sums: (total, node, search, in_range) uint64 and range_sum fp64."""
+        out = [np.zeros(npix, np.uint64) for _ in range(4)]
+        rs = np.zeros(npix, np.float64)
+        _check(self.lib.avr_graph_analysis_read(self.h, *[a.ctypes.data_as(c_u64_p) for a in out],
+                                                rs.ctypes.data_as(c_double_p)))
+        return out[0], out[1], out[2], out[3], rs
+
+    def graph_analysis_clear(self):
+        _check(self.lib.avr_graph_analysis_clear(self.h))
+
+    def graph_analyze_last_pass(self, npix, max_samples, max_depth):
+        """The last analysis pass with detail (indexed as last_pass_samples): camera ray o, d
+        (n, 3), scatters analysed (n), and per sample max_depth entries of the scatter point
+        in render space (n, max_depth, 3), node, in_range and range_sum (n, max_depth)."""
+        n, md = npix * max_samples, int(max_depth)
+        o, d = (np.zeros((n, 3), np.float32) for _ in range(2))
+        counts = np.zeros(n, np.int32)
+        pts = np.zeros((n, md, 3), np.float32)
+        node, in_range = (np.zeros((n, md), np.int32) for _ in range(2))
+        range_sum = np.zeros((n, md), np.float32)
+        _check(self.lib.avr_graph_analyze_last_pass(self.h, _fp(o), _fp(d), counts.ctypes.data_as(c_int_p), _fp(pts),
+                                                    node.ctypes.data_as(c_int_p), in_range.ctypes.data_as(c_int_p),
+                                                    _fp(range_sum), n, md))
+        return o, d, counts, pts, node, in_range, range_sum
+
     def film_export_device(self, d_dst_ptr):
         _check(self.lib.avr_film_export_device(self.h, ctypes.c_void_p(d_dst_ptr)))
 
@@ -789,6 +844,18 @@ class GraphIndex:
         counts = np.zeros(len(p), np.int32)
         _check(self.lib.avr_graph_index_connect(self.h, len(p), _fp(p), _fp(light), counts.ctypes.data_as(c_int_p)))
         return light, counts
+
+    def coverage(self, points):
+        """IntegrationAnalyzer's Analyze on the host for (n, 3) graph-space points: node (a
+        vertex within the vertex radius), in_range (vertices within their own search range)
+        and range_sum (the float sum of their distances, nearest first)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        node = np.zeros(len(p), np.int32)
+        in_range = np.zeros(len(p), np.int32)
+        range_sum = np.zeros(len(p), np.float32)
+        _check(self.lib.avr_graph_index_coverage(self.h, len(p), _fp(p), node.ctypes.data_as(c_int_p),
+                                                 in_range.ctypes.data_as(c_int_p), _fp(range_sum)))
+        return node, in_range, range_sum
 
     def knn(self, k):
         """GetNClosest for every vertex on the host: the k nearest other vertices in ascending

@@ -200,6 +200,16 @@ struct avr_context {
     float4 *d_gside = nullptr;
     long long gside_cap = 0;
     bool last_graph = false;        // the last render was avr_graph_render's
+    // graph analysis (avr_graph_analyze): the pass's per-sample records, the per-pixel sums
+    // (made by the first analysis on a film, dropped with the film) and, only when a call asks
+    // for it, the pass's per-scatter detail (adetail_cap entries)
+    avr::graph::AnalyzeRec *d_arec = nullptr;
+    long long arec_cap = 0;
+    avr::graph::AnalyzeAcc *d_aacc = nullptr;
+    avr::graph::AnalyzeDetail *d_adetail = nullptr;
+    size_t adetail_cap = 0;
+    int last_analyze = 0;           // the last render was avr_graph_analyze's: 1 without, 2 with detail
+    int last_analyze_depth = 0;     // ... and its max_depth (the detail's stride)
 };
 
 namespace {
@@ -816,6 +826,9 @@ int avr_context_destroy(avr_context *c) {
     if (c->d_brick) (void)hipFree(c->d_brick);
     if (c->d_gidx) (void)hipFree(c->d_gidx);
     if (c->d_gside) (void)hipFree(c->d_gside);
+    if (c->d_arec) (void)hipFree(c->d_arec);
+    if (c->d_aacc) (void)hipFree(c->d_aacc);
+    if (c->d_adetail) (void)hipFree(c->d_adetail);
     free_pixel_order(c);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->h_count) (void)hipHostFree(c->h_count);
@@ -1559,6 +1572,9 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     if (c->film.w_sum) (void)hipFree(c->film.w_sum);
     if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
     free_pixel_order(c);   // an order is for one film resolution
+    if (c->d_aacc) (void)hipFree(c->d_aacc);   // the analysis' per-pixel sums go with the film
+    c->d_aacc = nullptr;
+    c->last_analyze = 0;
     c->film = {};
     c->film.width = width;
     c->film.height = height;
@@ -1998,6 +2014,7 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
         c->last_persistent = persistent;
         c->last_fast = persistent && c->render_mode == 1;
         c->last_graph = false;
+        c->last_analyze = 0;
         if (persistent) {
             // PCG32 Advance(s*65536) as an affine map state' = A*state + inc*H (rng.h:132-146:
             // every step is linear in inc, so H = accPlus computed with inc = 1).

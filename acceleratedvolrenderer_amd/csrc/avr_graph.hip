@@ -24,6 +24,11 @@
 //  k_graph_render  GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247): one
 //                  lane per camera record of the pass; delta tracking to the first real
 //                  scatter, then the same index_connect.
+//  k_graph_coverage  IntegrationAnalyzer's Analyze (analysis/integration_analyzer.cpp:56-83)
+//                  for a batch of graph-space points: index_coverage, one lane per point.
+//  k_graph_analyze IntegrationAnalyzer::AnalyzeRay (:55-163): one lane per camera record walks
+//  k_graph_analyze_reduce  on as k_graph_walks does and analyses up to maxDepth scatters;
+//                  then one lane per pixel adds the pass's records to the pixel's sums.
 //
 // Geometry model (shared with the oracle): the medium's boundary primitive is
 // its bounds box (medium-space slab test, ray mapped without error offsets); spheres solve
@@ -69,6 +74,64 @@ struct DiskRec {
 
 }  // namespace graph
 
+// The medium walk of FreeGraphBuilder::TracePath (free_graph_builder.cpp:19-141), which
+// IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:85-162) repeats for a camera ray:
+// per segment RNG(Hash(Get1D()), Hash(Get1D())), SampleT_maj with the next Get1D and the
+// 3-way event choice on channel 0; the first segment ends at tFirst, a later one where the
+// ray from the scatter point leaves the box (box_hits). Every real scatter point goes to
+// onScatter(k, p), up to maxDepth of them; between two the direction comes from the HG
+// Sample_p(-d, Get2D()). Absorption, leaving the medium and the maxDepth-th scatter end the
+// walk (draws after that scatter cannot reach a result). Returns the scatters seen.
+template <typename Sampler, typename F>
+__device__ __forceinline__ int graph_walk(const Params &P, const float *maj, Sampler &smp, V3 ro, V3 rd, float tFirst,
+                                          int maxDepth, const Spec &sig_a, const Spec &sig_s, const Spec &lam,
+                                          unsigned long long &nLookup, unsigned long long &nSteps, F onScatter) {
+    bool usedTHit = false;
+    int k = 0;
+    while (k < maxDepth) {
+        const float h0 = smp.get1d(P);
+        const float h1 = smp.get1d(P);
+        Pcg32 rng;
+        rng.set_sequence(hash_u32(f2u(h0)), hash_u32(f2u(h1)));
+        float tMax;
+        if (!usedTHit) {
+            tMax = tFirst;
+            usedTHit = true;
+        } else {
+            const graph::Hits h = graph::box_hits(P.med, ro, rd);
+            if (h.type == graph::kOutsideZeroHits) break;
+            tMax = h.t0;
+        }
+        bool scattered = false;
+        V3 pS = {0.f, 0.f, 0.f};
+        const float u = smp.get1d(P);
+        auto cb = [&](V3 p, const MediumSample &ms, const Spec &sigma_maj, const Spec &) -> bool {
+            const float pAbsorb = ms.sigma_a.v0 / sigma_maj.v0;
+            const float pScat = ms.sigma_s.v0 / sigma_maj.v0;
+            const float pNull = fmaxf_(0.f, 1 - pAbsorb - pScat);
+            const int mode = sample_discrete3(pAbsorb, pScat, pNull, rng.uniform());
+            if (mode == 0) return false;
+            if (mode == 1) {
+                scattered = true;
+                pS = p;
+                return false;
+            }
+            return true;
+        };
+        sample_t_maj(P.med, maj, Ray{ro, rd}, tMax, u, rng, sig_a, sig_s, Spec::c(0.f), lam, nLookup, nSteps, cb);
+        if (!scattered) break;
+        onScatter(k, pS);
+        ++k;
+        if (k == maxDepth) break;
+        float u0, u1, pdf;
+        smp.get2d(P, &u0, &u1);
+        const V3 wi = hg_sample(-rd, P.med.g, u0, u1, &pdf);
+        ro = pS;
+        rd = wi;
+    }
+    return k;
+}
+
 // skipDims: sampler dimensions already drawn after StartPixelSample before TracePath (the
 // reinforcement rays' phase sample, free_graph_builder.cpp:448-451)
 template <bool kZSobol>
@@ -93,54 +156,14 @@ __global__ void __launch_bounds__(256) k_graph_walks(Params P, long long nPaths,
         PathSampler<kZSobol> smp;
         smp.start(P, px, py, sampleIndex);
         for (int k = 0; k < skipDims; ++k) (void)smp.get1d(P);
-        V3 ro = {o[3 * r], o[3 * r + 1], o[3 * r + 2]}, rd = {d[3 * r], d[3 * r + 1], d[3 * r + 2]};
-        bool usedTHit = false;
-        int k = 0;
-        while (k < maxDepth) {
-            const float h0 = smp.get1d(P);
-            const float h1 = smp.get1d(P);
-            Pcg32 rng;
-            rng.set_sequence(hash_u32(f2u(h0)), hash_u32(f2u(h1)));
-            float tMax;
-            if (!usedTHit) {
-                tMax = tFirst[r];
-                usedTHit = true;
-            } else {
-                const graph::Hits h = graph::box_hits(P.med, ro, rd);
-                if (h.type == graph::kOutsideZeroHits) break;
-                tMax = h.t0;
-            }
-            bool scattered = false;
-            V3 pS = {0.f, 0.f, 0.f};
-            const float u = smp.get1d(P);
-            auto cb = [&](V3 p, const MediumSample &ms, const Spec &sigma_maj, const Spec &) -> bool {
-                const float pAbsorb = ms.sigma_a.v0 / sigma_maj.v0;
-                const float pScat = ms.sigma_s.v0 / sigma_maj.v0;
-                const float pNull = fmaxf_(0.f, 1 - pAbsorb - pScat);
-                const int mode = sample_discrete3(pAbsorb, pScat, pNull, rng.uniform());
-                if (mode == 0) return false;
-                if (mode == 1) {
-                    scattered = true;
-                    pS = p;
-                    return false;
-                }
-                return true;
-            };
-            sample_t_maj(P.med, maj, Ray{ro, rd}, tMax, u, rng, sig_a, sig_s, Spec::c(0.f), lam, nLookup, nSteps, cb);
-            if (!scattered) break;
-            float *dst = points + 3 * (path * maxDepth + k);
-            dst[0] = pS.x;
-            dst[1] = pS.y;
-            dst[2] = pS.z;
-            ++k;
-            if (k == maxDepth) break;
-            float u0, u1, pdf;
-            smp.get2d(P, &u0, &u1);
-            const V3 wi = hg_sample(-rd, P.med.g, u0, u1, &pdf);
-            ro = pS;
-            rd = wi;
-        }
-        counts[path] = k;
+        const V3 ro = {o[3 * r], o[3 * r + 1], o[3 * r + 2]}, rd = {d[3 * r], d[3 * r + 1], d[3 * r + 2]};
+        counts[path] = graph_walk(P, maj, smp, ro, rd, tFirst[r], maxDepth, sig_a, sig_s, lam, nLookup, nSteps,
+                                  [&](int k, V3 pS) {
+                                      float *dst = points + 3 * (path * maxDepth + k);
+                                      dst[0] = pS.x;
+                                      dst[1] = pS.y;
+                                      dst[2] = pS.z;
+                                  });
     }
     flush_stat(P.stats, 3, nLookup);
     flush_stat(P.stats, 4, nIn);
@@ -475,6 +498,117 @@ __global__ void __launch_bounds__(256) k_graph_render(Params P, graph::IndexView
     flush_stat(P.stats, 3, nLookup);
     flush_stat(P.stats, 4, nIn);
     flush_stat(P.stats, 6, nSteps);
+}
+
+// IntegrationAnalyzer's Analyze for n points already in graph space (avr_graph_coverage)
+__global__ void __launch_bounds__(256) k_graph_coverage(graph::IndexView ix, long long n, const float *__restrict__ pts,
+                                                        int *__restrict__ node, int *__restrict__ inRange,
+                                                        float *__restrict__ rangeSum) {
+    __shared__ float s_d2[graph::kConnectBuf * 256];
+    __shared__ int s_slot[graph::kConnectBuf * 256];
+    ConnectBufLds buf{s_d2 + threadIdx.x, s_slot + threadIdx.x};
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        int nd = 0;
+        float sum = 0.f;
+        inRange[i] = graph::index_coverage(ix, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], buf, &nd, &sum);
+        node[i] = nd;
+        rangeSum[i] = sum;
+    }
+}
+
+namespace graph {
+
+// One sample of the analysis: scatters analysed, those with a vertex within the vertex radius,
+// those with a vertex in its search range, the vertices in range and the sum over the scatters,
+// in order, of (double)range_sum
+struct AnalyzeRec {
+    int total, node, search, in_range;
+    double range;
+};
+// One analysed scatter (avr_graph_analyze_last_pass): the point in render space, index_coverage's answer
+struct AnalyzeDetail {
+    float x, y, z;
+    int node, in_range;
+    float range_sum;
+};
+// One pixel's sums over every sample analysed since the last clear
+struct AnalyzeAcc {
+    unsigned long long total, node, search, in_range;
+    double range;
+};
+
+}  // namespace graph
+
+// IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:55-163) after k_camera, one lane
+// per camera record: the ray starts as k_graph_render's does (box_hits; a miss analyses
+// nothing) and continues as k_graph_walks' (graph_walk), with the medium's coefficients at the
+// sample's own wavelengths; each of at most maxDepth real scatters p is analysed by
+// index_coverage(graphFromRender(p)). rec[id] gets the sample's record, detail (when given)
+// entry id * maxDepth + k for scatter k.
+template <bool kZSobol>
+__global__ void __launch_bounds__(256) k_graph_analyze(Params P, graph::IndexView ix, Xf graphFromRender, int maxDepth,
+                                                       graph::AnalyzeRec *__restrict__ rec,
+                                                       graph::AnalyzeDetail *__restrict__ detail) {
+    __shared__ float s_maj[4096];
+    const float *maj = stage_majorant(P.med, s_maj);
+    __shared__ float s_d2[graph::kConnectBuf * 256];
+    __shared__ int s_slot[graph::kConnectBuf * 256];
+    ConnectBufLds buf{s_d2 + threadIdx.x, s_slot + threadIdx.x};
+    unsigned long long nLookup = 0, nSteps = 0, nIn = 0;
+    const int n = P.pass_pixels * P.pass_samples;
+    for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
+        ++nIn;
+        const V3 o = from4(P.ps.o[id]), d = from4(P.ps.d[id]);
+        const Spec lam = spec4(P.ps.lambda[id]);
+        PathSampler<kZSobol> smp;
+        smp.load(P, id);
+        graph::AnalyzeRec r = {0, 0, 0, 0, 0.0};
+        const graph::Hits h = graph::box_hits(P.med, o, d);
+        if (h.type != graph::kOutsideZeroHits) {
+            V3 ro = o;
+            float tMax = h.t0;
+            if (h.type == graph::kOutsideTwoHits) {
+                ro = o + d * h.t0;
+                tMax = h.t1 - h.t0;
+            }
+            const LambdaIdx li = lambda_index(lam);
+            const Spec sig_a = sample_table(P.med.sigma_a, li), sig_s = sample_table(P.med.sigma_s, li);
+            r.total = graph_walk(P, maj, smp, ro, d, tMax, maxDepth, sig_a, sig_s, lam, nLookup, nSteps, [&](int k, V3 pS) {
+                const V3 q = xf_point_lr(graphFromRender, pS);
+                int node = 0;
+                float sum = 0.f;
+                const int inRange = graph::index_coverage(ix, q.x, q.y, q.z, buf, &node, &sum);
+                r.node += node;
+                r.search += inRange > 0 ? 1 : 0;
+                r.in_range += inRange;
+                r.range = r.range + (double)sum;
+                if (detail) detail[(size_t)id * (size_t)maxDepth + (size_t)k] = {pS.x, pS.y, pS.z, node, inRange, sum};
+            });
+        }
+        rec[id] = r;
+    }
+    flush_stat(P.stats, 3, nLookup);
+    flush_stat(P.stats, 4, nIn);
+    flush_stat(P.stats, 6, nSteps);
+}
+
+// The pass's records added to the per-pixel sums, one lane per pixel, in sample-index order:
+// a sample range split into passes or calls gives the same bits
+__global__ void __launch_bounds__(256) k_graph_analyze_reduce(int pixels, int samples,
+                                                              const graph::AnalyzeRec *__restrict__ rec,
+                                                              graph::AnalyzeAcc *__restrict__ acc) {
+    for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < pixels; pix += gridDim.x * blockDim.x) {
+        graph::AnalyzeAcc a = acc[pix];
+        for (int s = 0; s < samples; ++s) {
+            const graph::AnalyzeRec r = rec[(size_t)s * (size_t)pixels + (size_t)pix];
+            a.total += (unsigned long long)r.total;
+            a.node += (unsigned long long)r.node;
+            a.search += (unsigned long long)r.search;
+            a.in_range += (unsigned long long)r.in_range;
+            a.range = a.range + r.range;
+        }
+        acc[pix] = a;
+    }
 }
 
 }  // namespace avr

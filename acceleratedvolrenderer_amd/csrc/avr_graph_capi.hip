@@ -1,4 +1,4 @@
-// avr_graph_capi.hip — C-ABI of the lighting-graph precompute and of the graph render
+// avr_graph_capi.hip — C-ABI of the lighting-graph precompute, the graph render and the analyzer
 // (include/avr.h, "Lighting graph"), included at the end of avr_capi.hip (shares avr_context,
 // fail(), HIP_TRY, the render calls' sampler setup and path state).
 #include "avr_graph_host.h"
@@ -463,6 +463,43 @@ int avr_graph_connect(avr_context *c, const avr_graph_index *idx, long long n, c
     return AVR_OK;
 }
 
+int avr_graph_index_coverage(const avr_graph_index *idx, long long n, const float *points, int *node, int *in_range,
+                             float *range_sum) {
+    if (!idx || n < 0) return fail(AVR_ERR_ARG, "bad coverage arguments");
+    if (n > 0 && !points) return fail(AVR_ERR_ARG, "null buffer");
+    idx->ix.Coverage(n, points, node, in_range, range_sum);
+    return AVR_OK;
+}
+
+int avr_graph_coverage(avr_context *c, const avr_graph_index *idx, long long n, const float *points, int *node,
+                       int *in_range, float *range_sum) {
+    if (!c || !idx || n < 0) return fail(AVR_ERR_ARG, "bad coverage arguments");
+    if (n == 0) return AVR_OK;
+    if (!points || !node || !in_range || !range_sum) return fail(AVR_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_graph_index(c, idx);
+    if (rc) return rc;
+    char *buf = nullptr;
+    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
+    HIP_TRY(dalloc(&buf, szP + 3 * szL));
+    float *dP = (float *)buf, *dS = (float *)(buf + szP + 2 * szL);
+    int *dN = (int *)(buf + szP), *dR = (int *)(buf + szP + szL);
+    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_graph_coverage, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n,
+                           dP, dN, dR, dS);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(node, dN, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(in_range, dR, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(range_sum, dS, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph coverage: ") + hipGetErrorString(e));
+    return AVR_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -555,16 +592,20 @@ int avr_graph_search_ranges(avr_context *c, const avr_graph_index *idx, int k, f
     return graph_knn_device(c, idx, k, nullptr, nullptr, ranges);
 }
 
-int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
-                     int spp_end, int seed) {
-    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
-    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
-    if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
-    // GraphIntegrator::Create takes the scene's one DistantLight (lightSpectrum, lightDir)
-    if (c->lights.n != 1 || c->h_lights[0].type != 0)
-        return fail(AVR_ERR_STATE, "graph render: exactly one distant light required");
-    if (c->med.boundary != 0)
-        return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+}  // extern "C"
+
+namespace {
+
+// What ensure_paths allocates per path: the size policy of the wavefront path state, which
+// the analysis' optional detail buffer may not exceed (max_paths paths at most)
+constexpr size_t kPathStateBytes = 252;
+
+// The pass loop of avr_render's wavefront organisation for the graph integrators: k_camera,
+// then k_graph_render and k_film (analyze_depth < 0), or k_graph_analyze and
+// k_graph_analyze_reduce with the film left alone; passes of at most max_paths samples.
+int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                 int spp_end, int seed, int analyze_depth, int detail) {
+    const bool analyze = analyze_depth >= 0;
     static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     const float *gfr = graph_from_render ? graph_from_render : kIdentity;
     if (!affine(gfr)) return fail(AVR_ERR_ARG, "graph_from_render must be affine");
@@ -577,18 +618,46 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
     if (rc) return rc;
     const long long P = (long long)c->film.width * c->film.height;
     if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
-    // the pass loop of avr_render's wavefront organisation: k_camera, k_graph_render, k_film
     const long long Smax = std::max<long long>(1, c->max_paths / P);
     const long long need = P * std::min<long long>(Smax, std::max(1, spp_end - spp_begin));
+    if (analyze && detail) {
+        // asked for, never silent: pass samples x max_depth x 24 B, within the path state's policy
+        const unsigned long long entries = (unsigned long long)need * (unsigned long long)std::max(analyze_depth, 1);
+        const unsigned long long limit = (unsigned long long)std::max<long long>(c->max_paths, need) * kPathStateBytes;
+        if (entries > limit / sizeof(avr::graph::AnalyzeDetail))
+            return fail(AVR_ERR_ARG, "graph analyze: the detail buffer (" + std::to_string(need) + " pass samples x max_depth " +
+                                         std::to_string(analyze_depth) + " x 24 B) exceeds the path state's " +
+                                         std::to_string(limit) + " B (max_paths x 252 B): lower max_depth or max_paths, or pass detail = 0");
+        if ((size_t)entries > c->adetail_cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->d_adetail) (void)hipFree(c->d_adetail);
+            c->d_adetail = nullptr;
+            c->adetail_cap = 0;
+            HIP_TRY(dalloc(&c->d_adetail, (size_t)entries));
+            c->adetail_cap = (size_t)entries;
+        }
+    }
     rc = ensure_paths(c, need);
     if (rc) return rc;
-    if (need > c->gside_cap) {
+    if (!analyze && need > c->gside_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->d_gside) (void)hipFree(c->d_gside);
         c->d_gside = nullptr;
         c->gside_cap = 0;
         HIP_TRY(dalloc(&c->d_gside, (size_t)need));
         c->gside_cap = need;
+    }
+    if (analyze && need > c->arec_cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->d_arec) (void)hipFree(c->d_arec);
+        c->d_arec = nullptr;
+        c->arec_cap = 0;
+        HIP_TRY(dalloc(&c->d_arec, (size_t)need));
+        c->arec_cap = need;
+    }
+    if (analyze && !c->d_aacc) {
+        HIP_TRY(dalloc(&c->d_aacc, (size_t)P));
+        HIP_TRY(hipMemsetAsync(c->d_aacc, 0, (size_t)P * sizeof(avr::graph::AnalyzeAcc), c->stream));
     }
     EV_MARK(evStart);
     for (long long base = spp_begin; base < spp_end; base += Smax) {
@@ -615,7 +684,9 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
         const long long n0 = P * S;
         c->last_persistent = false;
         c->last_fast = false;
-        c->last_graph = true;
+        c->last_graph = !analyze;
+        c->last_analyze = analyze ? (detail ? 2 : 1) : 0;
+        c->last_analyze_depth = analyze_depth;
         EV_MARK(c0);
         if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
         else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
@@ -624,15 +695,27 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
         c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});
         // one lane per camera record, as many blocks as records up to 64 per CU's worth
         const int nb = blocks_for(n0, 256, 256 * 64);
-        if (c->sampler_kind)
+        if (analyze) {
+            avr::graph::AnalyzeDetail *det = detail ? c->d_adetail : nullptr;
+            if (c->sampler_kind)
+                hipLaunchKernelGGL(avr::k_graph_analyze<true>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf,
+                                   analyze_depth, c->d_arec, det);
+            else
+                hipLaunchKernelGGL(avr::k_graph_analyze<false>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf,
+                                   analyze_depth, c->d_arec, det);
+        } else if (c->sampler_kind)
             hipLaunchKernelGGL(avr::k_graph_render<true>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
         else
             hipLaunchKernelGGL(avr::k_graph_render<false>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
         HIP_TRY(hipGetLastError());
         EV_MARK(m1);
         c->timed.push_back({c1, m1, &avr_stats::ms_medium, true});
-        hipLaunchKernelGGL((c->film.nbuckets > 0 ? avr::k_film<true> : avr::k_film<false>), dim3(blocks_for(P)), dim3(256),
-                           avr::film_lds_bytes(c->film.nbuckets), c->stream, p);
+        if (analyze)
+            hipLaunchKernelGGL(avr::k_graph_analyze_reduce, dim3(blocks_for(P)), dim3(256), 0, c->stream, (int)P, S,
+                               c->d_arec, c->d_aacc);
+        else
+            hipLaunchKernelGGL((c->film.nbuckets > 0 ? avr::k_film<true> : avr::k_film<false>), dim3(blocks_for(P)), dim3(256),
+                               avr::film_lds_bytes(c->film.nbuckets), c->stream, p);
         HIP_TRY(hipGetLastError());
         EV_MARK(f1);
         c->timed.push_back({m1, f1, &avr_stats::ms_film, false});
@@ -641,6 +724,109 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
     }
     EV_MARK(evEnd);
     c->timed.push_back({evStart, evEnd, &avr_stats::ms_total, false});
+    return AVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                     int spp_end, int seed) {
+    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
+    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
+    if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
+    // GraphIntegrator::Create takes the scene's one DistantLight (lightSpectrum, lightDir)
+    if (c->lights.n != 1 || c->h_lights[0].type != 0)
+        return fail(AVR_ERR_STATE, "graph render: exactly one distant light required");
+    if (c->med.boundary != 0)
+        return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+    return graph_passes(c, idx, graph_from_render, spp_begin, spp_end, seed, -1, 0);
+}
+
+int avr_graph_analyze(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                      int spp_end, int seed, int max_depth, int detail) {
+    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
+    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
+    if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
+    if (max_depth < 0) return fail(AVR_ERR_ARG, "graph analyze: max_depth must not be negative");
+    if (c->med.boundary != 0)
+        return fail(AVR_ERR_STATE, "graph analyze: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+    return graph_passes(c, idx, graph_from_render, spp_begin, spp_end, seed, max_depth, detail);
+}
+
+int avr_graph_analysis_clear(avr_context *c) {
+    if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
+    if (!c->d_aacc) return AVR_OK;   // nothing analysed on this film yet: the sums start at zero
+    const size_t np = (size_t)c->film.width * c->film.height;
+    HIP_TRY(hipMemsetAsync(c->d_aacc, 0, np * sizeof(avr::graph::AnalyzeAcc), c->stream));
+    return AVR_OK;
+}
+
+int avr_graph_analysis_read(avr_context *c, unsigned long long *total, unsigned long long *node,
+                            unsigned long long *search, unsigned long long *in_range, double *range_sum) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
+    const size_t np = (size_t)c->film.width * c->film.height;
+    std::vector<avr::graph::AnalyzeAcc> h(np, avr::graph::AnalyzeAcc{0, 0, 0, 0, 0.0});
+    if (c->d_aacc) HIP_TRY(hipMemcpy(h.data(), c->d_aacc, np * sizeof(avr::graph::AnalyzeAcc), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < np; ++i) {
+        if (total) total[i] = h[i].total;
+        if (node) node[i] = h[i].node;
+        if (search) search[i] = h[i].search;
+        if (in_range) in_range[i] = h[i].in_range;
+        if (range_sum) range_sum[i] = h[i].range;
+    }
+    return AVR_OK;
+}
+
+int avr_graph_analyze_last_pass(avr_context *c, float *o, float *d, int *counts, float *points, int *node,
+                                int *in_range, float *range_sum, long long n_max, int max_depth) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
+    if (c->last_analyze != 2) return fail(AVR_ERR_STATE, "the last render was not avr_graph_analyze's with detail");
+    const long long n = (long long)c->film.width * c->film.height * c->last_S;
+    const int md = c->last_analyze_depth;
+    if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
+    if (max_depth != md) return fail(AVR_ERR_ARG, "max_depth differs from the analysis'");
+    if (n == 0) return AVR_OK;
+    if (o || d) {
+        std::vector<float4> h((size_t)n);
+        const float4 *src[2] = {c->ps.o, c->ps.d};
+        float *dst[2] = {o, d};
+        for (int k = 0; k < 2; ++k) {
+            if (!dst[k]) continue;
+            HIP_TRY(hipMemcpy(h.data(), src[k], (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+            for (long long i = 0; i < n; ++i) {
+                dst[k][3 * i] = h[(size_t)i].x;
+                dst[k][3 * i + 1] = h[(size_t)i].y;
+                dst[k][3 * i + 2] = h[(size_t)i].z;
+            }
+        }
+    }
+    std::vector<avr::graph::AnalyzeRec> rec((size_t)n);
+    HIP_TRY(hipMemcpy(rec.data(), c->d_arec, (size_t)n * sizeof(avr::graph::AnalyzeRec), hipMemcpyDeviceToHost));
+    if (counts)
+        for (long long i = 0; i < n; ++i) counts[i] = rec[(size_t)i].total;
+    if (md == 0 || (!points && !node && !in_range && !range_sum)) return AVR_OK;
+    const size_t entries = (size_t)n * (size_t)md;
+    std::vector<avr::graph::AnalyzeDetail> det(entries);
+    HIP_TRY(hipMemcpy(det.data(), c->d_adetail, entries * sizeof(avr::graph::AnalyzeDetail), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < n; ++i)
+        for (int k = 0; k < md; ++k) {
+            const size_t e = (size_t)i * (size_t)md + (size_t)k;
+            // entries past the sample's count were never written
+            const bool set = k < rec[(size_t)i].total;
+            const avr::graph::AnalyzeDetail z = set ? det[e] : avr::graph::AnalyzeDetail{0.f, 0.f, 0.f, 0, 0, 0.f};
+            if (points) {
+                points[3 * e] = z.x;
+                points[3 * e + 1] = z.y;
+                points[3 * e + 2] = z.z;
+            }
+            if (node) node[e] = z.node;
+            if (in_range) in_range[e] = z.in_range;
+            if (range_sum) range_sum[e] = z.range_sum;
+        }
     return AVR_OK;
 }
 

@@ -31,6 +31,15 @@
 // over the same cells, buffer and key order: index_knn, for the host (avr_graph_index_knn,
 // avr_graph_index_search_ranges) and for the device (k_graph_knn), and the two Averager
 // levels that turn the distances into renderSearchRange.
+//
+// Coverage: IntegrationAnalyzer's Analyze (graph/analysis/integration_analyzer.cpp:56-83) for
+// a point in graph space: index_coverage, for the host (avr_graph_index_coverage) and for the
+// device (k_graph_coverage, k_graph_analyze). node: radiusSearch(Sqr(vertexRadius)) returned a
+// vertex (d2 < r2). in_range: the vertices of radiusSearch(maxSquaredSearchRange) left after
+// those with d2 > Sqr(range[v]) are dropped, stage 2's search and filter; range_sum: the float
+// sum from 0 of sqrtf(d2) over them in ascending (d2, id), exact for any count by the same
+// rescans as Connect. An index without search ranges gives in_range = 0 and range_sum = 0 (the
+// reference would search maxSquaredSearchRange as Initialize left it, unset, there).
 #pragma once
 
 #include <algorithm>
@@ -151,6 +160,30 @@ AVR_HD float index_connect(const IndexView &ix, float qx, float qy, float qz, Bu
     }
     if (total == 0 || totalWeight == 0) return 0.f;
     return average / totalWeight;
+}
+
+// IntegrationAnalyzer's Analyze (integration_analyzer.cpp:56-83) for a point in graph space:
+// *node = 1 when a vertex lies within the vertex radius; returns the number of vertices within
+// the largest search range that are not beyond their own, and in *range_sum the float sum of
+// their distances sqrtf(d2) in ascending key (d2, id). Without search ranges: 0 and 0.
+template <typename Buf>
+AVR_HD int index_coverage(const IndexView &ix, float qx, float qy, float qz, Buf &buf, int *node, float *range_sum) {
+    int m = 0;
+    *node = index_collect(ix, qx, qy, qz, ix.r2, false, -1.f, -1, buf, &m) > 0 ? 1 : 0;
+    *range_sum = 0.f;
+    if (!ix.range2) return 0;
+    const int total = index_collect(ix, qx, qy, qz, ix.max_r2, true, -1.f, -1, buf, &m);
+    float sum = 0.f;
+    for (int left = total; left > 0;) {
+        for (int i = 0; i < m; ++i) sum += __builtin_sqrtf(buf.d2(i));
+        left -= m;
+        if (left <= 0 || m == 0) break;
+        const float lastD2 = buf.d2(m - 1);
+        const int lastId = ix.id[buf.slot(m - 1)];
+        (void)index_collect(ix, qx, qy, qz, ix.max_r2, true, lastD2, lastId, buf, &m);
+    }
+    *range_sum = sum;
+    return total;
 }
 
 // FreeGraphBuilder::GetNClosest (free_graph_builder.cpp:473-496) for the vertex in sorted
@@ -314,6 +347,19 @@ class Index {
             const float l = index_connect(v, points[3 * i], points[3 * i + 1], points[3 * i + 2], buf, &cnt, &stage);
             if (light) light[i] = l;
             if (count) count[i] = cnt;
+        }
+    }
+
+    void Coverage(long long n, const float *points, int *node, int *in_range, float *range_sum) const {
+        const IndexView v = View();
+        for (long long i = 0; i < n; ++i) {
+            ConnectBufLocal buf;
+            int nd = 0;
+            float sum = 0.f;
+            const int cnt = index_coverage(v, points[3 * i], points[3 * i + 1], points[3 * i + 2], buf, &nd, &sum);
+            if (node) node[i] = nd;
+            if (in_range) in_range[i] = cnt;
+            if (range_sum) range_sum[i] = sum;
         }
     }
 

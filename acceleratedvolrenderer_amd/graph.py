@@ -36,6 +36,12 @@ ComputeSearchRanges (:473-548) has three forms: compute_search_ranges (a float64
 the default), and compute_search_ranges_host / _device, which follow the reference's float
 arithmetic and order over the vertex index (k_graph_knn, k_graph_range_average on the GPU).
 
+IntegrationAnalyzer (graph/analysis/integration_analyzer.cpp, the fork's "analyzer"
+integrator) tells whether a graph serves a camera: the camera paths are followed for maxdepth
+real scatters and each scatter point is looked up in the vertex index (k_graph_analyze,
+capi.GraphIndex.coverage): a vertex within the vertex radius? vertices within their own search
+range, and how far? GraphAnalysis holds the per-pixel counters and the reference's figures.
+
 Not mirrored: the uniform-graph branch, --graph-debug.
 """
 import json
@@ -534,3 +540,146 @@ class GraphIntegrator(FilmIntegrator):
         o, d, p, count = self.ctx.graph_last_pass(npix, ms)
         n = npix * ns
         return dict(first=first, samples=ns, L=L, lam=lam, pdf=pdf, o=o[:n], d=d[:n], p=p[:n], count=count[:n])
+
+
+# ---------------------------------------------------------------------------
+# The analyzer (graph/analysis/integration_analyzer.cpp)
+
+class GraphAnalysis:
+    """IntegrationAnalyzer's counters for every pixel: (H, W) maps of the scatters analysed
+    (total), those with a vertex within the vertex radius (node), those with a vertex within
+    its own search range (search), the vertices in range (in_range) and the sum of their
+    distances (range_sum, fp64)."""
+
+    def __init__(self, width, height, maxdepth, spp, total, node, search, in_range, range_sum):
+        self.width, self.height, self.maxdepth, self.spp = int(width), int(height), int(maxdepth), int(spp)
+        shape = (self.height, self.width)
+        self.total, self.node, self.search, self.in_range = (np.asarray(a, np.uint64).reshape(shape)
+                                                             for a in (total, node, search, in_range))
+        self.range_sum = np.asarray(range_sum, np.float64).reshape(shape)
+
+    @staticmethod
+    def _figures(total, node, search, in_range, range_sum):
+        # the reference prints float ratios (0 / 0 is its NaN) and Averager::GetAverage (0 when empty)
+        with np.errstate(all="ignore"):
+            return dict(total=int(total), node=int(node), search=int(search), in_range=int(in_range),
+                        node_ratio=float(f32(node) / f32(total)), search_ratio=float(f32(search) / f32(total)),
+                        mean_range=float(f32(range_sum / in_range)) if in_range else 0.0)
+
+    def pixel(self, x, y):
+        """The reference's figures for pixel (x, y) over the samples analysed: nodeScatters,
+        searchScatters, totalScatters, their ratios and rangeAverager.GetAverage()."""
+        return self._figures(self.total[y, x], self.node[y, x], self.search[y, x], self.in_range[y, x],
+                             self.range_sum[y, x])
+
+    def summary(self):
+        """pixel()'s figures over the whole frame (range_sum added in row-major pixel order)."""
+        return self._figures(self.total.sum(), self.node.sum(), self.search.sum(), self.in_range.sum(),
+                             float(np.add.reduce(self.range_sum.ravel())))
+
+    @staticmethod
+    def _line(where, f):
+        return (f"{where}, {f['node']} / {f['total']} ({f['node_ratio']:g}) | {f['search']} / {f['total']} "
+                f"({f['search_ratio']:g}), {f['mean_range']:g}")
+
+    def format_line(self, x, y):
+        """IntegrationAnalyzer::Render's line for one pixel (integration_analyzer.cpp:40-44)."""
+        return self._line(f"[ {int(x)}, {int(y)} ]", self.pixel(x, y))
+
+    def format_summary(self):
+        return self._line("frame", self.summary())
+
+    def ratio_maps(self):
+        """(node ratio, search ratio, mean range) as float32 (H, W) images; 0 where a pixel
+        analysed no scatter (or found no vertex in range)."""
+        with np.errstate(all="ignore"):
+            t = self.total.astype(np.float64)
+            nr = np.where(self.total > 0, self.node / t, 0.0)
+            sr = np.where(self.total > 0, self.search / t, 0.0)
+            mr = np.where(self.in_range > 0, self.range_sum / self.in_range.astype(np.float64), 0.0)
+        return nr.astype(f32), sr.astype(f32), mr.astype(f32)
+
+
+class IntegrationAnalyzer:
+    """IntegrationAnalyzer (graph/analysis/integration_analyzer.cpp), the fork's "analyzer"
+    integrator: it follows the camera paths through the medium for up to `maxdepth` real
+    scatters and asks at each whether a graph vertex lies within the vertex radius and whether
+    any lies within its own render search range, and how far those are (k_graph_analyze,
+    avr_graph_analyze): how well a graph serves this camera. The reference prints the figures
+    for a hard-coded pixel list; here every pixel is analysed. `graph_index`, `graph_from_render`
+    and the scene's limits are GraphIntegrator's, except that no light is needed. Nothing is
+    rendered: the film is not touched."""
+
+    def __init__(self, scene, graph_index, maxdepth=1, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0):
+        if int(maxdepth) < 0:
+            raise ValueError("maxdepth must not be negative")
+        self.scene = scene
+        self.index = graph_index
+        self.maxdepth = int(maxdepth)
+        self.spp = int(spp)
+        self.seed = int(seed)
+        self.device = int(device)
+        self.graph_from_render = None if graph_from_render is None else np.asarray(graph_from_render, f32).reshape(4, 4)
+        self.ctx = capi.Context(device, max_paths)
+        self.ctx.set_scene(scene)
+
+    @classmethod
+    def from_file(cls, scene, path, **kw):
+        """The analyzer over a graph file (`pbrt --graph`): load_index(path), then the
+        constructor's keywords."""
+        return cls(scene, load_index(path), **kw)
+
+    @staticmethod
+    def create_params(name, params, maxdepth_override=None):
+        """Constructor arguments of IntegrationAnalyzer::Create (integration_analyzer.cpp:165-174):
+        "maxdepth" from the scene file (default 1), replaced by the --maxdepth option whenever
+        it is given (a std::optional: 0 counts), as the fork's volpathcustom does; pixelsamples
+        and seed are the sampler's."""
+        if name != "analyzer":
+            raise ValueError(f"{name}: integrator type unknown.")
+        maxdepth = int(params.get("maxdepth", 1))
+        if maxdepth_override is not None:
+            maxdepth = int(maxdepth_override)
+        return dict(maxdepth=maxdepth, spp=int(params.get("pixelsamples", 16)), seed=int(params.get("seed", 0)))
+
+    @classmethod
+    def create(cls, name, params, scene, graph_index=None, device=0, maxdepth_override=None, **kw):
+        """Integrator::Create-style factory (cpu/integrators.cpp:3695-3700, name "analyzer")."""
+        return cls(scene, graph_index, device=device, **cls.create_params(name, params, maxdepth_override), **kw)
+
+    def analyze(self, spp_begin=0, spp_end=None, clear=True, detail=False):
+        """Analyse sample indices [spp_begin, spp_end) of every pixel; returns the GraphAnalysis
+        of everything analysed since the last clear. detail=True keeps the last pass's
+        scatters for last_pass()."""
+        if spp_end is None:
+            spp_end = self.spp
+        if clear:
+            self.ctx.graph_analysis_clear()
+        self.ctx.graph_analyze(self.index, spp_begin, spp_end, self.seed, self.maxdepth, self.graph_from_render,
+                               detail=detail)
+        return self.result()
+
+    def result(self):
+        f = self.scene.film
+        return GraphAnalysis(f.width, f.height, self.maxdepth, self.spp, *self.ctx.graph_analysis_read(f.width * f.height))
+
+    def last_pass(self, max_samples=None):
+        """The last pass of analyze(detail=True) per sample: dict of first sample index, sample
+        count, camera ray o, d (n, 3), scatters analysed (count, n) and per sample `maxdepth`
+        entries of the scatter point p (n, maxdepth, 3, render space), node, in_range and
+        range_sum (n, maxdepth; zero past count); n = pixels x samples of that pass, element
+        s * pixels + pixel."""
+        f = self.scene.film
+        npix = f.width * f.height
+        ms = self.spp if max_samples is None else int(max_samples)
+        o, d, count, p, node, in_range, range_sum = self.ctx.graph_analyze_last_pass(npix, ms, self.maxdepth)
+        first, ns, _, lam, _ = self.ctx.last_pass_samples(npix, ms)
+        n = npix * ns
+        return dict(first=first, samples=ns, lam=lam, o=o[:n], d=d[:n], count=count[:n], p=p[:n], node=node[:n],
+                    in_range=in_range[:n], range_sum=range_sum[:n])
+
+    def stats(self):
+        return self.ctx.stats()
+
+    def close(self):
+        self.ctx.close()

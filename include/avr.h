@@ -591,8 +591,65 @@ int avr_graph_render(avr_context *ctx, const avr_graph_index *idx, const float g
  * avr_last_pass_weights, returns that pass's L, wavelengths, pdfs and filter weights): the
  * camera ray o, d (n*3 each), the scatter point in render space (n*3) and the number of
  * vertices averaged, -1 when the sample did not scatter. Any output may be NULL.
- * AVR_ERR_STATE when the last render was avr_render's. */
+ * AVR_ERR_STATE when the last render was avr_render's or avr_graph_analyze's. */
 int avr_graph_last_pass(avr_context *ctx, float *o, float *d, float *points, int *counts, long long n_max);
+
+/* IntegrationAnalyzer's Analyze (graph/analysis/integration_analyzer.cpp:56-83) for n points
+ * already in graph space; host code, no GPU needed. node[i] = 1 when radiusSearch(point,
+ * Sqr(vertex_radius)) returns a vertex (d2 < r2 strictly, d2 as avr_graph_index_connect's).
+ * in_range[i]: the vertices of radiusSearch(point, the largest squared search range) left
+ * after those with d2 > Sqr(range[v]) are dropped (stage 2's search and filter); non-zero
+ * counts one search scatter. range_sum[i]: the float sum from 0 of sqrtf(d2) over them in
+ * ascending (d2, id), nanoflann's result order with ties to the lower id; exact for any
+ * count. The reference adds every distance of every sample to one float Averager; here the
+ * sum is per point, so that it can be checked bit for bit. An index without search ranges
+ * gives in_range = 0 and range_sum = 0 (the reference would search its unset
+ * maxSquaredSearchRange). Any output may be NULL. */
+int avr_graph_index_coverage(const avr_graph_index *idx, long long n, const float *points, int *node, int *in_range,
+                             float *range_sum);
+/* avr_graph_index_coverage on the device (k_graph_coverage, one lane per point) with bitwise
+ * the host's results, over the context's cached copy of the index as avr_graph_connect's.
+ * Host arrays, synchronous. */
+int avr_graph_coverage(avr_context *ctx, const avr_graph_index *idx, long long n, const float *points, int *node,
+                       int *in_range, float *range_sum);
+/* IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:55-163) for sample indices
+ * [spp_begin, spp_end) of every pixel: avr_graph_render's pass loop with k_graph_analyze in
+ * place of k_graph_render and k_graph_analyze_reduce in place of k_film; the film is not
+ * touched. Per sample the camera ray crosses the medium's bounds box as avr_graph_render's
+ * does (a miss analyses nothing) and then walks on as avr_graph_walks' paths do: per segment
+ * RNG(Hash(Get1D), Hash(Get1D)) and SampleT_maj with the next Get1D, coefficients at the
+ * sample's own wavelengths, the 3-way event choice on channel 0; absorption and leaving the
+ * medium end the path; each of the first max_depth real scatters p is analysed by
+ * avr_graph_index_coverage(graph_from_render(p)) and followed by the HG Sample_p(-d, Get2D);
+ * the path stops right after the max_depth-th (the reference's further draws reach no
+ * result). Per pixel five sums grow, in sample-index then scatter order: scatters analysed,
+ * those with node = 1, those with in_range > 0, in_range, and (double)range_sum added in
+ * double, so that a sample range split into passes or calls gives the same bits. The
+ * reference's figures for a pixel: node / total, search / total and range_sum / in_range
+ * (its float Averager chain differs from the last by rounding only). Requires medium, camera
+ * and film (no light) and no interface sphere / convex (AVR_ERR_STATE); max_depth < 0 or a
+ * bad sample range: AVR_ERR_ARG; max_depth 0 analyses nothing. graph_from_render, sampler,
+ * ZSobol limits and seeds as avr_graph_render. detail != 0 also keeps the last pass's
+ * scatters (avr_graph_analyze_last_pass) in a buffer of pass samples x max_depth x 24 B,
+ * allocated only then; AVR_ERR_ARG when it would exceed the wavefront path state's own bound,
+ * max_paths x 252 B. Work counters and kernel time as avr_graph_render (ms_medium;
+ * k_graph_analyze_reduce in ms_film). */
+int avr_graph_analyze(avr_context *ctx, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                      int spp_end, int seed, int max_depth, int detail);
+/* The per-pixel sums of the analyses since the last clear (W*H entries each, row-major; any
+ * may be NULL): scatters analysed, node scatters, search scatters, vertices in range and the
+ * sum of their distances. avr_graph_analysis_clear zeroes them; a new avr_film does too. */
+int avr_graph_analysis_read(avr_context *ctx, unsigned long long *total, unsigned long long *node,
+                            unsigned long long *search, unsigned long long *in_range, double *range_sum);
+int avr_graph_analysis_clear(avr_context *ctx);
+/* The last pass of the last avr_graph_analyze called with detail != 0, samples indexed as
+ * avr_graph_last_pass: the camera ray o, d (n*3 each), counts (n, scatters analysed) and per
+ * sample max_depth entries (the analysis' max_depth) of the scatter point in render space
+ * (points, n*max_depth*3) and avr_graph_index_coverage's answer for it (node, in_range,
+ * range_sum, n*max_depth each); entries past a sample's count are zero. Any output may be
+ * NULL. AVR_ERR_STATE when the last render was not an analysis with detail. */
+int avr_graph_analyze_last_pass(avr_context *ctx, float *o, float *d, int *counts, float *points, int *node,
+                                int *in_range, float *range_sum, long long n_max, int max_depth);
 
 /* Per-sample radiance of the LAST wavefront pass of the last avr_render (replay checks;
  * pbrt's --debugstart analogue, integrators.cpp:74-102). Element id = s*W*H + pixel,
