@@ -50,6 +50,10 @@ class AvrGraphSampling(ctypes.Structure):
                 ("film_width", ctypes.c_int), ("film_height", ctypes.c_int), ("resolution_x", ctypes.c_int)]
 
 
+# avr_graph_set_geometry's values by the names graph.MediumData(primitive=...) uses
+GRAPH_GEOMETRY = {"box": 0, "interface": 1}
+
+
 class AvrVdbGrid(ctypes.Structure):
     """avr_vdb_grid (include/avr.h): one NanoVDB FloatGrid's tree."""
     _fields_ = [
@@ -177,6 +181,9 @@ SIGNATURES = {
     "avr_film_reduce_rccl": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     "avr_last_pass_samples": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_longlong,
                                              c_int_p, c_int_p]),
+    "avr_graph_set_geometry": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "avr_graph_start_rays": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_float, c_float_p, ctypes.c_int,
+                                            c_int_p, c_float_p, c_float_p]),
     "avr_graph_walks": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AvrGraphSampling), ctypes.c_longlong, c_float_p,
                                        c_float_p, c_float_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, c_float_p, c_int_p]),
@@ -563,6 +570,29 @@ class Context:
         return out
 
     # ---- lighting graph (src/graph) ----
+    def set_graph_geometry(self, geometry):
+        """The graph tools' primitive for this context: 0 the medium's bounds box (the default),
+        1 the medium's interface sphere or mesh (the box when the scene has neither); also
+        "box" / "interface". Every graph_* call of the context follows it."""
+        geometry = GRAPH_GEOMETRY.get(geometry, geometry)
+        if isinstance(geometry, bool) or not isinstance(geometry, (int, np.integer)):
+            raise ValueError('graph geometry must be 0 / "box" or 1 / "interface"')
+        _check(self.lib.avr_graph_set_geometry(self.h, int(geometry)))
+
+    def graph_start_rays(self, bounds_center, max_dist_to_center, in_dir, steps):
+        """BuildGraph's steps x steps ray grid on the device: per grid ray (x outer) the hit
+        type (0 OutsideTwoHits, 2 no hit, 3 InsideOneHit), the origin after SkipIntersection
+        (n, 3) and the first segment's tMax."""
+        ctr = np.ascontiguousarray(bounds_center, np.float32).reshape(3)
+        dr = np.ascontiguousarray(in_dir, np.float32).reshape(3)
+        n = int(steps) * int(steps)
+        ty = np.zeros(n, np.int32)
+        o = np.zeros((n, 3), np.float32)
+        t = np.zeros(n, np.float32)
+        _check(self.lib.avr_graph_start_rays(self.h, _fp(ctr), float(max_dist_to_center), _fp(dr), int(steps),
+                                             ty.ctypes.data_as(c_int_p), _fp(o), _fp(t)))
+        return ty, o, t
+
     def graph_walks(self, sampling, o, d, t_first, index0, iterations, sample_index, max_depth, skip_dims=0):
         """FreeGraphBuilder::TracePath walks: (points (n_rays*iterations, max_depth, 3), counts)."""
         o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)

@@ -200,6 +200,8 @@ struct avr_context {
     float4 *d_gside = nullptr;
     long long gside_cap = 0;
     bool last_graph = false;        // the last render was avr_graph_render's
+    // the graph tools' primitive (avr_graph_set_geometry): 0 the bounds box, 1 the interface
+    int graph_geometry = 0;
     // graph analysis (avr_graph_analyze): the pass's per-sample records, the per-pixel sums
     // (made by the first analysis on a film, dropped with the film) and, only when a call asks
     // for it, the pass's per-scatter detail (adetail_cap entries)

@@ -29,10 +29,15 @@
 //  k_graph_analyze IntegrationAnalyzer::AnalyzeRay (:55-163): one lane per camera record walks
 //  k_graph_analyze_reduce  on as k_graph_walks does and analyses up to maxDepth scatters;
 //                  then one lane per pixel adds the pass's records to the pixel's sums.
+//  k_graph_start_rays  BuildGraph's ray grid (free_graph_builder.cpp:143-199): one lane per
+//                  grid ray, its crossing of the primitive and SkipIntersection.
 //
 // Geometry model (shared with the oracle): the medium's boundary primitive is
-// its bounds box (medium-space slab test, ray mapped without error offsets); spheres solve
-// Sphere::BasicIntersect's interval quadric once for both roots.
+// its bounds box (medium-space slab test, ray mapped without error offsets), kGeom 0, or, on
+// request (avr_graph_set_geometry, kGeom 1), the medium's interface: the sphere or the convex
+// polyhedron of avr_medium_boundary_*, solved once from the ray's own origin. Spheres solve
+// Sphere::BasicIntersect's interval quadric once for both roots. The geometry is a template
+// parameter: the kGeom 0 instantiations are the box-only kernels' code.
 #include "avr_graph_index.h"
 
 namespace avr {
@@ -50,6 +55,17 @@ __device__ __forceinline__ Hits box_hits(const DevMedium &m, V3 o, V3 d) {
     return {kInsideOneHit, t1, 0.f};
 }
 
+// GetHits(primitive) of the graph geometry kGeom: 0 the bounds box; 1 the medium's interface
+// (the sphere for boundary 1, the convex polyhedron for boundary 2, the box without one).
+// One solve from o, no surface offset: OutsideTwoHits {t0, t1}, InsideOneHit {exit}.
+template <int kGeom>
+__device__ __forceinline__ Hits primitive_hits(const DevMedium &m, V3 o, V3 d) {
+    if constexpr (kGeom != 0) {
+        if (m.boundary == 1) return sphere_hits(V3{m.sph[0], m.sph[1], m.sph[2]}, m.sph[3], o, d);
+        if (m.boundary == 2) return convex_hits(m.planes, m.n_planes, o, d);
+    }
+    return box_hits(m, o, d);
+}
 
 __device__ __forceinline__ void coordinate_system(V3 v1, V3 *v2, V3 *v3) {   // vecmath.h:1007-1013
     const float sign = __builtin_copysignf(1.f, v1.z);
@@ -78,11 +94,11 @@ struct DiskRec {
 // IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:85-162) repeats for a camera ray:
 // per segment RNG(Hash(Get1D()), Hash(Get1D())), SampleT_maj with the next Get1D and the
 // 3-way event choice on channel 0; the first segment ends at tFirst, a later one where the
-// ray from the scatter point leaves the box (box_hits). Every real scatter point goes to
+// ray from the scatter point leaves the primitive (primitive_hits). Every real scatter point goes to
 // onScatter(k, p), up to maxDepth of them; between two the direction comes from the HG
 // Sample_p(-d, Get2D()). Absorption, leaving the medium and the maxDepth-th scatter end the
 // walk (draws after that scatter cannot reach a result). Returns the scatters seen.
-template <typename Sampler, typename F>
+template <int kGeom, typename Sampler, typename F>
 __device__ __forceinline__ int graph_walk(const Params &P, const float *maj, Sampler &smp, V3 ro, V3 rd, float tFirst,
                                           int maxDepth, const Spec &sig_a, const Spec &sig_s, const Spec &lam,
                                           unsigned long long &nLookup, unsigned long long &nSteps, F onScatter) {
@@ -98,7 +114,7 @@ __device__ __forceinline__ int graph_walk(const Params &P, const float *maj, Sam
             tMax = tFirst;
             usedTHit = true;
         } else {
-            const graph::Hits h = graph::box_hits(P.med, ro, rd);
+            const graph::Hits h = graph::primitive_hits<kGeom>(P.med, ro, rd);
             if (h.type == graph::kOutsideZeroHits) break;
             tMax = h.t0;
         }
@@ -134,7 +150,7 @@ __device__ __forceinline__ int graph_walk(const Params &P, const float *maj, Sam
 
 // skipDims: sampler dimensions already drawn after StartPixelSample before TracePath (the
 // reinforcement rays' phase sample, free_graph_builder.cpp:448-451)
-template <bool kZSobol>
+template <bool kZSobol, int kGeom>
 __global__ void __launch_bounds__(256) k_graph_walks(Params P, long long nPaths, int iterations, const float *__restrict__ o,
                                                      const float *__restrict__ d, const float *__restrict__ tFirst,
                                                      const long long *__restrict__ index0, int sampleIndex, int skipDims,
@@ -157,7 +173,7 @@ __global__ void __launch_bounds__(256) k_graph_walks(Params P, long long nPaths,
         smp.start(P, px, py, sampleIndex);
         for (int k = 0; k < skipDims; ++k) (void)smp.get1d(P);
         const V3 ro = {o[3 * r], o[3 * r + 1], o[3 * r + 2]}, rd = {d[3 * r], d[3 * r + 1], d[3 * r + 2]};
-        counts[path] = graph_walk(P, maj, smp, ro, rd, tFirst[r], maxDepth, sig_a, sig_s, lam, nLookup, nSteps,
+        counts[path] = graph_walk<kGeom>(P, maj, smp, ro, rd, tFirst[r], maxDepth, sig_a, sig_s, lam, nLookup, nSteps,
                                   [&](int k, V3 pS) {
                                       float *dst = points + 3 * (path * maxDepth + k);
                                       dst[0] = pS.x;
@@ -175,9 +191,9 @@ __global__ void __launch_bounds__(256) k_graph_walks(Params P, long long nPaths,
 // GetSphereVolumePointsRandom (util.h:238-252: rejection sampling in the cube; the three
 // Get1D of one Point3f are GCC-evaluated right to left, so the first draw is z; the
 // arithmetic is (double(u) - 0.5) * 2 * radius), then per point StartPixelSample(pixel(id *
-// nRays + point), cycle), the medium's HG Sample_p((1, 0, 0), Get2D()), GetHits(box) and
+// nRays + point), cycle), the medium's HG Sample_p((1, 0, 0), Get2D()), GetHits(primitive) and
 // SkipIntersection. valid = RayEntersVolume (OutsideTwoHits or InsideOneHit).
-template <bool kZSobol>
+template <bool kZSobol, int kGeom>
 __global__ void __launch_bounds__(256) k_graph_reinforce_rays(Params P, int n, const int *__restrict__ ids,
                                                               const float *__restrict__ pts, float radius, int nRays,
                                                               int cycle, int resX, float *__restrict__ o,
@@ -205,7 +221,7 @@ __global__ void __launch_bounds__(256) k_graph_reinforce_rays(Params P, int n, c
         float u0, u1, pdf;
         smp.get2d(P, &u0, &u1);
         const V3 dir = hg_sample(V3{1.f, 0.f, 0.f}, P.med.g, u0, u1, &pdf);
-        const graph::Hits h = graph::box_hits(P.med, sp, dir);
+        const graph::Hits h = graph::primitive_hits<kGeom>(P.med, sp, dir);
         V3 og = sp;
         float t = 0.f;
         int ok = 0;
@@ -225,9 +241,46 @@ __global__ void __launch_bounds__(256) k_graph_reinforce_rays(Params P, int n, c
     }
 }
 
+// BuildGraph's ray grid (free_graph_builder.cpp:143-199), one lane per grid ray (x, y) of the
+// steps x steps grid, x outer (ray = (x - 1) * steps + (y - 1)): the grid's corner is center -
+// inDir * maxDist * 2 - (xv + yv) * maxDist with (xv, yv) = CoordinateSystem(inDir), its step
+// maxDist * 2 / (steps + 1); ray (x, y) starts at (corner + xv * step * x) + yv * step * y, then
+// GetHits(primitive) and SkipIntersection (no offset). type = the hit kind, o the origin after
+// the skip (the grid point itself without a hit), tFirst the first segment's tMax (0 without).
+template <int kGeom>
+__global__ void __launch_bounds__(256) k_graph_start_rays(DevMedium m, V3 center, float maxDist, V3 dir, int steps,
+                                                          int *__restrict__ type, float *__restrict__ o,
+                                                          float *__restrict__ tFirst) {
+    const long long n = (long long)steps * steps;
+    for (long long ray = blockIdx.x * (long long)blockDim.x + threadIdx.x; ray < n;
+         ray += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(ray / steps) + 1, y = (int)(ray - (long long)(x - 1) * steps) + 1;
+        V3 xv, yv;
+        graph::coordinate_system(dir, &xv, &yv);
+        V3 origin = center - (dir * maxDist) * 2.f;
+        origin = origin - (xv + yv) * maxDist;
+        const float step = (maxDist * 2.f) / (float)(steps + 1);
+        xv = xv * step;
+        yv = yv * step;
+        V3 p = (origin + xv * (float)x) + yv * (float)y;
+        const graph::Hits h = graph::primitive_hits<kGeom>(m, p, dir);
+        float t = 0.f;
+        if (h.type == graph::kOutsideTwoHits) {
+            p = p + dir * h.t0;
+            t = h.t1 - h.t0;
+        } else if (h.type == graph::kInsideOneHit) {
+            t = h.t0;
+        }
+        type[ray] = h.type;
+        o[3 * ray] = p.x; o[3 * ray + 1] = p.y; o[3 * ray + 2] = p.z;
+        tFirst[ray] = t;
+    }
+}
+
 // Per vertex: disk points around vertex - inDir * maxDistToCenter * 2 (GetDiskPoints, util.h:179-204,
-// grid order x then y), the medium-box and sphere crossings of the ray along inDir from each,
+// grid order x then y), the primitive and vertex-sphere crossings of the ray along inDir from each,
 // GetStartEndT (util.h:484-503), SkipIntersection to the medium entry and SkipForward.
+template <int kGeom>
 __global__ void __launch_bounds__(256) k_graph_disk(DevMedium m, int nv, const float *__restrict__ verts, V3 dir,
                                                     float radius, int n, float maxDist, int maxPts,
                                                     graph::DiskRec *__restrict__ rec, int *__restrict__ npts) {
@@ -249,7 +302,7 @@ __global__ void __launch_bounds__(256) k_graph_disk(DevMedium m, int nv, const f
             r.valid = 0;
             r.dist = 0.f;
             r.o_start = make_float4(0.f, 0.f, 0.f, 0.f);
-            const graph::Hits mh = graph::box_hits(m, p, dir), sh = graph::sphere_hits(c, radius, p, dir);
+            const graph::Hits mh = graph::primitive_hits<kGeom>(m, p, dir), sh = graph::sphere_hits(c, radius, p, dir);
             if (mh.type == graph::kOutsideTwoHits && sh.type == graph::kOutsideTwoHits) {
                 const float startT = mh.t0, endT = graph::smin(mh.t1, sh.t1), startScatterT = graph::smax(mh.t0, sh.t0);
                 const float endScatterT = endT;
@@ -426,15 +479,15 @@ __global__ void __launch_bounds__(256) k_graph_range_average(int n, int k, const
 }
 
 // GraphIntegrator::Li, free graph (graph_integrator.cpp:180-247), after k_camera: the camera
-// record's ray crosses the medium's bounds box in the graph tools' geometry model (box_hits;
+// record's ray crosses the primitive of the graph tools' geometry model (primitive_hits;
 // a ray from outside starts at its entry point, as FreeGraphBuilder's rays do; a camera
-// inside the box, which the reference leaves commented out, tracks from its origin), hash0 and
+// inside it, which the reference leaves commented out, tracks from its origin), hash0 and
 // hash1 seed the RNG, SampleT_maj runs with the medium's coefficients at the sample's own
 // wavelengths and the 3-way event choice on channel 0; the first real scatter p gives
 // L = lightSpectrum.Sample(lambda) * ConnectToGraph(graphFromRender(p)), absorption or
-// leaving the box L = 0. L goes where k_film reads it; side[id] = {p, count} (render space;
+// leaving the primitive L = 0. L goes where k_film reads it; side[id] = {p, count} (render space;
 // count -1 without a scatter).
-template <bool kZSobol>
+template <bool kZSobol, int kGeom>
 __global__ void __launch_bounds__(256) k_graph_render(Params P, graph::IndexView ix, Xf graphFromRender,
                                                       float4 *__restrict__ side) {
     __shared__ float s_maj[4096];
@@ -455,7 +508,7 @@ __global__ void __launch_bounds__(256) k_graph_render(Params P, graph::IndexView
         Spec L = Spec::c(0.f);
         int count = -1;
         V3 pS = {0.f, 0.f, 0.f};
-        const graph::Hits h = graph::box_hits(P.med, o, d);
+        const graph::Hits h = graph::primitive_hits<kGeom>(P.med, o, d);
         if (h.type != graph::kOutsideZeroHits) {
             V3 ro = o;
             float tMax = h.t0;
@@ -540,12 +593,12 @@ struct AnalyzeAcc {
 }  // namespace graph
 
 // IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:55-163) after k_camera, one lane
-// per camera record: the ray starts as k_graph_render's does (box_hits; a miss analyses
+// per camera record: the ray starts as k_graph_render's does (primitive_hits; a miss analyses
 // nothing) and continues as k_graph_walks' (graph_walk), with the medium's coefficients at the
 // sample's own wavelengths; each of at most maxDepth real scatters p is analysed by
 // index_coverage(graphFromRender(p)). rec[id] gets the sample's record, detail (when given)
 // entry id * maxDepth + k for scatter k.
-template <bool kZSobol>
+template <bool kZSobol, int kGeom>
 __global__ void __launch_bounds__(256) k_graph_analyze(Params P, graph::IndexView ix, Xf graphFromRender, int maxDepth,
                                                        graph::AnalyzeRec *__restrict__ rec,
                                                        graph::AnalyzeDetail *__restrict__ detail) {
@@ -563,7 +616,7 @@ __global__ void __launch_bounds__(256) k_graph_analyze(Params P, graph::IndexVie
         PathSampler<kZSobol> smp;
         smp.load(P, id);
         graph::AnalyzeRec r = {0, 0, 0, 0, 0.0};
-        const graph::Hits h = graph::box_hits(P.med, o, d);
+        const graph::Hits h = graph::primitive_hits<kGeom>(P.med, o, d);
         if (h.type != graph::kOutsideZeroHits) {
             V3 ro = o;
             float tMax = h.t0;
@@ -573,7 +626,7 @@ __global__ void __launch_bounds__(256) k_graph_analyze(Params P, graph::IndexVie
             }
             const LambdaIdx li = lambda_index(lam);
             const Spec sig_a = sample_table(P.med.sigma_a, li), sig_s = sample_table(P.med.sigma_s, li);
-            r.total = graph_walk(P, maj, smp, ro, d, tMax, maxDepth, sig_a, sig_s, lam, nLookup, nSteps, [&](int k, V3 pS) {
+            r.total = graph_walk<kGeom>(P, maj, smp, ro, d, tMax, maxDepth, sig_a, sig_s, lam, nLookup, nSteps, [&](int k, V3 pS) {
                 const V3 q = xf_point_lr(graphFromRender, pS);
                 int node = 0;
                 float sum = 0.f;

@@ -37,6 +37,27 @@ int graph_params(avr_context *c, const avr_graph_sampling *s, unsigned long long
     return AVR_OK;
 }
 
+// The kernels' geometry instantiation (avr_graph_set_geometry): the interface one only for a
+// context that has an interface; without one geometry 1 is the bounds box, geometry 0's code
+bool graph_interface(const avr_context *c) { return c->graph_geometry == 1 && c->med.boundary != 0; }
+
+// kernel<zsobol, geometry> / kernel<geometry> on the context's stream, 256 lanes per block
+#define AVR_GRAPH_LAUNCH_ZG(kernel, zs, geom, blocks, ...)                                                        \
+    do {                                                                                                           \
+        if (zs) {                                                                                                  \
+            if (geom) hipLaunchKernelGGL((kernel<true, 1>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);   \
+            else hipLaunchKernelGGL((kernel<true, 0>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);        \
+        } else {                                                                                                   \
+            if (geom) hipLaunchKernelGGL((kernel<false, 1>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);  \
+            else hipLaunchKernelGGL((kernel<false, 0>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);       \
+        }                                                                                                          \
+    } while (0)
+#define AVR_GRAPH_LAUNCH_G(kernel, geom, blocks, ...)                                                     \
+    do {                                                                                                   \
+        if (geom) hipLaunchKernelGGL((kernel<1>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kernel<0>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);          \
+    } while (0)
+
 }  // namespace
 
 // The host vertex index (avr_graph_index.h) and the id its device copies are cached under
@@ -88,6 +109,40 @@ int ensure_graph_index(avr_context *c, const avr_graph_index *idx) {
 
 extern "C" {
 
+int avr_graph_set_geometry(avr_context *c, int geometry) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    if (geometry != 0 && geometry != 1) return fail(AVR_ERR_ARG, "graph geometry must be 0 (bounds box) or 1 (interface)");
+    c->graph_geometry = geometry;
+    return AVR_OK;
+}
+
+int avr_graph_start_rays(avr_context *c, const float bounds_center[3], float max_dist_to_center, const float in_dir[3],
+                         int steps, int *type, float *o, float *t_first) {
+    if (!c || steps < 0 || steps > 32768) return fail(AVR_ERR_ARG, "bad start ray arguments");
+    if (!c->has_medium) return fail(AVR_ERR_STATE, "medium required");
+    if (steps == 0) return AVR_OK;
+    if (!bounds_center || !in_dir || !type || !o || !t_first) return fail(AVR_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    const long long n = (long long)steps * steps;
+    char *buf = nullptr;
+    const size_t szT = (size_t)n * 4, szO = (size_t)n * 12;
+    HIP_TRY(dalloc(&buf, 2 * szT + szO));
+    int *dTy = (int *)buf;
+    float *dT = (float *)(buf + szT), *dO = (float *)(buf + 2 * szT);
+    const avr::V3 ctr = {bounds_center[0], bounds_center[1], bounds_center[2]}, dir = {in_dir[0], in_dir[1], in_dir[2]};
+    AVR_GRAPH_LAUNCH_G(avr::k_graph_start_rays, graph_interface(c), blocks_for(n, 256, 256 * 64), c->med, ctr,
+                       max_dist_to_center, dir, steps, dTy, dO, dT);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(type, dTy, szT, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(o, dO, szO, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_first, dT, szT, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph start rays: ") + hipGetErrorString(e));
+    return AVR_OK;
+}
+
 int avr_graph_walks(avr_context *c, const avr_graph_sampling *s, long long n_rays, const float *o, const float *d,
                     const float *t_first, const long long *index0, int iterations, int sample_index, int max_depth,
                     float *points, int *counts) {
@@ -129,12 +184,8 @@ int avr_graph_walks_from(avr_context *c, const avr_graph_sampling *s, long long 
     if (e == hipSuccess) e = hipMemcpyAsync(dI, index0, szI, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         const int blocks = blocks_for(nPaths, 256, 256 * 64);
-        if (p.sampler_kind == 1)
-            hipLaunchKernelGGL(avr::k_graph_walks<true>, dim3(blocks), dim3(256), 0, c->stream, p, nPaths, iterations,
-                               dO, dD, dT, dI, sample_index, skip_dims, s->resolution_x, max_depth, dP, dC);
-        else
-            hipLaunchKernelGGL(avr::k_graph_walks<false>, dim3(blocks), dim3(256), 0, c->stream, p, nPaths, iterations,
-                               dO, dD, dT, dI, sample_index, skip_dims, s->resolution_x, max_depth, dP, dC);
+        AVR_GRAPH_LAUNCH_ZG(avr::k_graph_walks, p.sampler_kind == 1, graph_interface(c), blocks, p, nPaths, iterations, dO,
+                            dD, dT, dI, sample_index, skip_dims, s->resolution_x, max_depth, dP, dC);
         e = hipGetLastError();
     }
     if (e == hipSuccess && max_depth > 0) e = hipMemcpyAsync(points, dP, szP, hipMemcpyDeviceToHost, c->stream);
@@ -173,12 +224,8 @@ int avr_graph_reinforce_rays(avr_context *c, const avr_graph_sampling *s, int n,
     hipError_t e = hipMemcpyAsync(dId, vertex_ids, szI, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dPt, points, szP, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        if (p.sampler_kind == 1)
-            hipLaunchKernelGGL(avr::k_graph_reinforce_rays<true>, dim3((n + 255) / 256), dim3(256), 0, c->stream, p, n,
-                               dId, dPt, vertex_radius, n_rays, cycle, s->resolution_x, dO, dD, dT, dV);
-        else
-            hipLaunchKernelGGL(avr::k_graph_reinforce_rays<false>, dim3((n + 255) / 256), dim3(256), 0, c->stream, p, n,
-                               dId, dPt, vertex_radius, n_rays, cycle, s->resolution_x, dO, dD, dT, dV);
+        AVR_GRAPH_LAUNCH_ZG(avr::k_graph_reinforce_rays, p.sampler_kind == 1, graph_interface(c), (n + 255) / 256, p, n, dId,
+                            dPt, vertex_radius, n_rays, cycle, s->resolution_x, dO, dD, dT, dV);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(o, dO, szR, hipMemcpyDeviceToHost, c->stream);
@@ -219,8 +266,8 @@ int avr_graph_light(avr_context *c, const avr_graph_sampling *s, int n_vertices,
     if (e == hipSuccess) e = hipMemcpyAsync(dV, vertices, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
     const avr::V3 dir = {in_dir[0], in_dir[1], in_dir[2]};
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_graph_disk, dim3((n_vertices + 255) / 256), dim3(256), 0, c->stream, c->med, n_vertices,
-                           dV, dir, sphere_radius, points_on_radius, max_dist_to_center, maxPts, dRec, dN);
+        AVR_GRAPH_LAUNCH_G(avr::k_graph_disk, graph_interface(c), (n_vertices + 255) / 256, c->med, n_vertices, dV, dir,
+                           sphere_radius, points_on_radius, max_dist_to_center, maxPts, dRec, dN);
         e = hipGetLastError();
     }
     for (int v0 = 0; e == hipSuccess && v0 < n_vertices; v0 += chunk) {
@@ -688,8 +735,12 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
         c->last_analyze = analyze ? (detail ? 2 : 1) : 0;
         c->last_analyze_depth = analyze_depth;
         EV_MARK(c0);
-        if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
+        // the record keeps the camera's own ray: the graph kernels solve the primitive once from
+        // it (k_camera would move it to the interface entry, as the path kernels want it)
+        avr::Params pc = p;
+        pc.med.boundary = 0;
+        if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, pc);
+        else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, pc);
         HIP_TRY(hipGetLastError());
         EV_MARK(c1);
         c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});
@@ -697,16 +748,12 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
         const int nb = blocks_for(n0, 256, 256 * 64);
         if (analyze) {
             avr::graph::AnalyzeDetail *det = detail ? c->d_adetail : nullptr;
-            if (c->sampler_kind)
-                hipLaunchKernelGGL(avr::k_graph_analyze<true>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf,
-                                   analyze_depth, c->d_arec, det);
-            else
-                hipLaunchKernelGGL(avr::k_graph_analyze<false>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf,
-                                   analyze_depth, c->d_arec, det);
-        } else if (c->sampler_kind)
-            hipLaunchKernelGGL(avr::k_graph_render<true>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
-        else
-            hipLaunchKernelGGL(avr::k_graph_render<false>, dim3(nb), dim3(256), 0, c->stream, p, c->gidx, xf, c->d_gside);
+            AVR_GRAPH_LAUNCH_ZG(avr::k_graph_analyze, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
+                                analyze_depth, c->d_arec, det);
+        } else {
+            AVR_GRAPH_LAUNCH_ZG(avr::k_graph_render, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
+                                c->d_gside);
+        }
         HIP_TRY(hipGetLastError());
         EV_MARK(m1);
         c->timed.push_back({c1, m1, &avr_stats::ms_medium, true});
@@ -739,8 +786,8 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
     // GraphIntegrator::Create takes the scene's one DistantLight (lightSpectrum, lightDir)
     if (c->lights.n != 1 || c->h_lights[0].type != 0)
         return fail(AVR_ERR_STATE, "graph render: exactly one distant light required");
-    if (c->med.boundary != 0)
-        return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+    if (c->med.boundary != 0 && c->graph_geometry == 0)
+        return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex; avr_graph_set_geometry(ctx, 1) takes the interface as the primitive)");
     return graph_passes(c, idx, graph_from_render, spp_begin, spp_end, seed, -1, 0);
 }
 
@@ -750,8 +797,8 @@ int avr_graph_analyze(avr_context *c, const avr_graph_index *idx, const float gr
     if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
     if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
     if (max_depth < 0) return fail(AVR_ERR_ARG, "graph analyze: max_depth must not be negative");
-    if (c->med.boundary != 0)
-        return fail(AVR_ERR_STATE, "graph analyze: the graph's geometry model is the medium's bounds box (no interface sphere or convex)");
+    if (c->med.boundary != 0 && c->graph_geometry == 0)
+        return fail(AVR_ERR_STATE, "graph analyze: the graph's geometry model is the medium's bounds box (no interface sphere or convex; avr_graph_set_geometry(ctx, 1) takes the interface as the primitive)");
     return graph_passes(c, idx, graph_from_render, spp_begin, spp_end, seed, max_depth, detail);
 }
 

@@ -17,7 +17,9 @@ k_graph_tr / k_graph_average) and the sparse bounce iteration (k_graph_spmv) run
 through include/avr.h; the order-dependent vertex merge runs in C++ on the host
 (avr_graph_add_walks). Names, parameters and error behaviour follow the reference. All
 geometry is in the scene's render space; the medium's boundary primitive is its bounds box
-(DESIGN.md §9).
+or, with primitive="interface", the scene's interface sphere or mesh:
+MediumData(scene, primitive) carries the choice, and FreeGraphBuilder, LightingCalculator,
+GraphIntegrator and IntegrationAnalyzer set it on their context (capi.Context.set_graph_geometry).
 
 ReinforceSparseVertices (:280-475) runs its rays and walks on the GPU and its sparse-vertex
 checks on the host graph.
@@ -169,13 +171,40 @@ def coordinate_system(v):
     return x, y
 
 
-class MediumData:
-    """util::MediumData / PrimitiveData (util.h:45-91): the medium's boundary box in render
-    space, its center and maxDistToCenter = |Diagonal / 2|."""
+PRIMITIVES = ("box", "interface")
 
-    def __init__(self, scene):
+
+def parse_interface_sphere(text):
+    """The tools' --interface-sphere CX,CY,CZ,R (world space) as Scene's interface_sphere
+    argument ((cx, cy, cz), r); ValueError unless four finite numbers with r > 0."""
+    parts = [v.strip() for v in str(text).split(",")]
+    if len(parts) != 4:
+        raise ValueError(f"interface sphere {text!r}: expected CX,CY,CZ,R")
+    cx, cy, cz, r = (float(v) for v in parts)
+    if not all(math.isfinite(v) for v in (cx, cy, cz, r)) or not r > 0:
+        raise ValueError(f"interface sphere {text!r}: finite centre and a radius > 0 required")
+    return (cx, cy, cz), r
+
+
+def _check_primitive(primitive):
+    if primitive not in PRIMITIVES:
+        raise ValueError('primitive must be "box" or "interface"')
+    return primitive
+
+
+class MediumData:
+    """util::MediumData / PrimitiveData (util.h:45-91): the bounds of the medium's boundary
+    primitive in render space (pmin, pmax), their center and maxDistToCenter = |Diagonal / 2|.
+    primitive="box": the medium's bounds box. primitive="interface": the scene's interface, as
+    the reference takes the scene's primitive: the sphere's bounds c -+ r (Sphere::Bounds of a
+    translated sphere) or the bounds of the mesh's vertices; the box when the scene has no
+    interface. `geometry` is the value avr_graph_set_geometry takes (0 box, 1 interface)."""
+
+    def __init__(self, scene, primitive="box"):
         med = scene.medium
         self.scene = scene
+        self.primitive = _check_primitive(primitive)
+        self.geometry = capi.GRAPH_GEOMETRY[primitive]
         self.mfr = np.asarray(scene.medium_from_render, f32)
         b = np.asarray(med.bounds, f32)
         self.bmin, self.bmax = b[:3], b[3:]
@@ -184,6 +213,18 @@ class MediumData:
                    for z in (b[2], b[5])]
         self.pmin = np.min(corners, axis=0).astype(f32)
         self.pmax = np.max(corners, axis=0).astype(f32)
+        sph = getattr(scene, "interface_sphere_render", None)
+        verts = getattr(scene, "interface_vertices_render", None)
+        # what the device intersects (primitive_hits): the sphere, the mesh's planes, or the box
+        self.shape = "box"
+        if primitive == "interface" and sph is not None:
+            c, r = np.asarray(sph[:3], f32), f32(sph[3])
+            self.pmin, self.pmax = (c - r).astype(f32), (c + r).astype(f32)
+            self.shape = "sphere"
+        elif primitive == "interface" and verts is not None:
+            v = np.asarray(verts, f32).reshape(-1, 3)
+            self.pmin, self.pmax = v.min(axis=0).astype(f32), v.max(axis=0).astype(f32)
+            self.shape = "mesh"
         diag = (self.pmax - self.pmin).astype(f32)
         half = (diag / f32(2)).astype(f32)
         self.bounds_center = (self.pmin + half).astype(f32)
@@ -286,22 +327,50 @@ class FreeGraphBuilder:
         r = node_radius if node_radius is not None else f32(same_spot_radius(medium_data) * f32(config.radius_modifier))
         self.radius = f32(r)
         self.sample_index_offset = int(sample_index_offset)
+        if ctx is not None and medium_data is not None:
+            ctx.set_graph_geometry(medium_data.geometry)
 
-    def start_rays(self):
-        """BuildGraph's ray grid (:143-199): origins, directions, first-segment tMax (the
-        medium exit after SkipIntersection) and the first sampling index per ray."""
-        c = self.config
-        md = self.md
-        d = self.in_dir
+    def _start_rays_device(self):
+        c, md, d = self.config, self.md, self.in_dir
+        ty, o, t = self.ctx.graph_start_rays(md.bounds_center, md.max_dist_to_center, d, c.dimension_steps)
+        sel = ty != 2
+        idx = np.arange(c.dimension_steps ** 2, dtype=np.int64)[sel] * c.iterations_per_step
+        n = int(sel.sum())
+        return o[sel].reshape(n, 3), np.tile(d, (n, 1)).astype(f32), t[sel], idx
+
+    def grid_points(self):
+        """The ray grid's points before the primitive's crossing, (dimension_steps^2, 3) float32
+        in the loop's order (x outer): BuildGraph :143-165 in its float operation order, from
+        the primitive's bounds_center and max_dist_to_center."""
+        c, md, d = self.config, self.md, self.in_dir
         xv, yv = coordinate_system(d)
         origin = (md.bounds_center - (d * md.max_dist_to_center) * f32(2)).astype(f32)
         origin = (origin - ((xv + yv).astype(f32) * md.max_dist_to_center)).astype(f32)
         step = f32(f32(md.max_dist_to_center * f32(2)) / f32(c.dimension_steps + 1))
         xv, yv = (xv * step).astype(f32), (yv * step).astype(f32)
+        return np.array([((origin + (xv * f32(x)).astype(f32)).astype(f32) + (yv * f32(y)).astype(f32)).astype(f32)
+                         for x in range(1, c.dimension_steps + 1) for y in range(1, c.dimension_steps + 1)],
+                        f32).reshape(-1, 3)
+
+    def start_rays(self, device=None):
+        """BuildGraph's ray grid (:143-199): origins, directions, first-segment tMax (the
+        primitive's exit after SkipIntersection) and the first sampling index per ray.
+        device=True runs the grid on the GPU (avr_graph_start_rays; for the box bitwise the
+        host loop), which an interface sphere or mesh always does (device=False raises there)."""
+        c = self.config
+        md = self.md
+        d = self.in_dir
+        if device is None:
+            device = md.shape != "box"
+        if device:
+            return self._start_rays_device()
+        if md.shape != "box":
+            raise ValueError("the ray grid of an interface primitive runs on the device (start_rays(device=True))")
+        grid = self.grid_points()
         o, t, idx = [], [], []
         for x in range(1, c.dimension_steps + 1):
             for y in range(1, c.dimension_steps + 1):
-                p = ((origin + (xv * f32(x)).astype(f32)).astype(f32) + (yv * f32(y)).astype(f32)).astype(f32)
+                p = grid[(y - 1) + (x - 1) * c.dimension_steps]
                 ty, t0, t1 = md.box_hits(p, d)
                 if ty == 2:
                     continue
@@ -466,9 +535,13 @@ class LightingCalculator:
     """LightingCalculator (lighting_calculator.cpp): light vector and bounce propagation
     on the GPU."""
 
-    def __init__(self, ctx, graph, medium_data, in_direction, sampling, config):
+    def __init__(self, ctx, graph, medium_data, in_direction, sampling, config, primitive=None):
+        """primitive: None takes `medium_data`'s; "box" or "interface" must agree with it
+        (max_dist_to_center is that primitive's)."""
         if config.light_iterations <= 0:
             raise ValueError("Must have at least one light ray iteration")
+        if primitive is not None and _check_primitive(primitive) != medium_data.primitive:
+            raise ValueError(f'primitive "{primitive}" differs from the MediumData\'s "{medium_data.primitive}"')
         self.ctx, self.graph, self.md = ctx, graph, medium_data
         self.in_dir = np.asarray(in_direction, f32)
         self.sampling, self.config = sampling, config
@@ -476,6 +549,7 @@ class LightingCalculator:
 
     def get_light_vector(self):
         c = self.config
+        self.ctx.set_graph_geometry(self.md.geometry)
         return self.ctx.graph_light(self.sampling.struct(), self.graph.points, self.in_dir, self.graph.radius,
                                     c.points_on_radius_light, c.light_iterations, self.md.max_dist_to_center)
 
@@ -502,14 +576,19 @@ class GraphIntegrator(FilmIntegrator):
     capi.GraphIndex over any vertices. `graph_from_render` (4x4, affine) maps a render-space
     scatter point into the graph's space: the identity by default, since the graph tools here
     work in the scene's render space; a graph made in world space, as the reference's
-    graph_maker makes them, takes inv(scene.render_from_world). The scene needs exactly one
-    DistantLight, no interface sphere or mesh, and not a GBufferFilm (its geometric channels
-    have no meaning here). render(), film_sums(), image(), get_image() and write_image()
-    are VolPathIntegrator's."""
+    graph_maker makes them, takes inv(scene.render_from_world). `primitive` is the geometry
+    model's primitive, which should be the one the graph was made with: "box" (the default), the
+    medium's bounds box, which refuses a scene with an interface sphere or mesh; "interface",
+    the scene's interface sphere or mesh (the box for a scene without one). The scene needs
+    exactly one DistantLight and not a GBufferFilm (its geometric channels have no meaning
+    here). render(), film_sums(), image(), get_image() and write_image() are
+    VolPathIntegrator's."""
 
-    def __init__(self, scene, graph_index, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0):
+    def __init__(self, scene, graph_index, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0,
+                 primitive="box"):
         if isinstance(scene.film, GBufferFilm):
             raise ValueError("GraphIntegrator does not render into a GBufferFilm")
+        self.primitive = _check_primitive(primitive)
         self.scene = scene
         self.index = graph_index
         self.spp = int(spp)
@@ -518,6 +597,7 @@ class GraphIntegrator(FilmIntegrator):
         self.graph_from_render = None if graph_from_render is None else np.asarray(graph_from_render, f32).reshape(4, 4)
         self.ctx = capi.Context(device, max_paths)
         self.ctx.set_scene(scene)
+        self.ctx.set_graph_geometry(self.primitive)
 
     @classmethod
     def from_file(cls, scene, path, **kw):
@@ -606,13 +686,15 @@ class IntegrationAnalyzer:
     scatters and asks at each whether a graph vertex lies within the vertex radius and whether
     any lies within its own render search range, and how far those are (k_graph_analyze,
     avr_graph_analyze): how well a graph serves this camera. The reference prints the figures
-    for a hard-coded pixel list; here every pixel is analysed. `graph_index`, `graph_from_render`
-    and the scene's limits are GraphIntegrator's, except that no light is needed. Nothing is
-    rendered: the film is not touched."""
+    for a hard-coded pixel list; here every pixel is analysed. `graph_index`, `graph_from_render`,
+    `primitive` and the scene's limits are GraphIntegrator's, except that no light is needed.
+    Nothing is rendered: the film is not touched."""
 
-    def __init__(self, scene, graph_index, maxdepth=1, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0):
+    def __init__(self, scene, graph_index, maxdepth=1, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0,
+                 primitive="box"):
         if int(maxdepth) < 0:
             raise ValueError("maxdepth must not be negative")
+        self.primitive = _check_primitive(primitive)
         self.scene = scene
         self.index = graph_index
         self.maxdepth = int(maxdepth)
@@ -622,6 +704,7 @@ class IntegrationAnalyzer:
         self.graph_from_render = None if graph_from_render is None else np.asarray(graph_from_render, f32).reshape(4, 4)
         self.ctx = capi.Context(device, max_paths)
         self.ctx.set_scene(scene)
+        self.ctx.set_graph_geometry(self.primitive)
 
     @classmethod
     def from_file(cls, scene, path, **kw):

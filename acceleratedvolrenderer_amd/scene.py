@@ -613,6 +613,7 @@ class Scene:
         self.scene_radius = _bounding_sphere_radius(rc.min(axis=0), rc.max(axis=0))
         self.interface_sphere_render = None
         self.interface_planes_render = None
+        self.interface_vertices_render = None   # the mesh's vertices, float32 (its bounds: graph.MediumData)
         if interface_mesh is not None:
             verts, tris = interface_mesh
             pw = convex_mesh_planes(verts, tris)
@@ -620,7 +621,8 @@ class Scene:
             pr = pw.copy()
             pr[:, 3] = pw[:, 3] + pw[:, :3] @ off
             self.interface_planes_render = pr.astype(np.float32)
-            vr = np.asarray(verts, np.float64) + off
+            vr = np.asarray(verts, np.float64).reshape(-1, 3) + off
+            self.interface_vertices_render = vr.astype(np.float32)
             self.scene_radius = _bounding_sphere_radius(vr.min(axis=0), vr.max(axis=0))
         if interface_sphere is not None:
             cw, r = interface_sphere

@@ -429,7 +429,13 @@ int avr_flip(avr_context *ctx, const float *test_rgb, const float *reference_rgb
  * the boundary primitive. Sampling follows the reference's graph tools
  * (cmd/graph_maker.cpp:97-104): the scene sampler at its film resolution with
  * Options->pixelSamples, sampling index i -> pixel (i % resolution_x, i / resolution_x)
- * (graph/util.h:816-817). */
+ * (graph/util.h:816-817).
+ * The primitive of the geometry model is chosen per context with avr_graph_set_geometry: the
+ * bounds box (the default) or the medium's interface. avr_graph_start_rays,
+ * avr_graph_walks[_from], avr_graph_reinforce_rays, avr_graph_light, avr_graph_render and
+ * avr_graph_analyze all follow it. bounds_center and max_dist_to_center (avr_graph_start_rays,
+ * avr_graph_light) are the caller's, from the bounds of that primitive (PrimitiveData,
+ * graph/util.h:45-59: bounds centre and |Diagonal / 2|). */
 typedef struct avr_graph_sampling {
     int sampler;             /* 0 IndependentSampler, 1 ZSobolSampler                     */
     int seed;                /* sampler seed (Options->seed)                              */
@@ -437,6 +443,28 @@ typedef struct avr_graph_sampling {
     int film_width, film_height; /* the sampler's full resolution (ZSobol Morton layout)  */
     int resolution_x;        /* Options->graph.samplingResolution.x                       */
 } avr_graph_sampling;
+
+/* The graph tools' primitive for this context: geometry 0 = the medium's bounds box (the
+ * default), 1 = the medium's interface: the sphere of avr_medium_boundary_sphere, the convex
+ * polyhedron of avr_medium_boundary_convex, or, with neither set, the bounds box with exactly
+ * geometry 0's results. Every hit is one solve from the ray's own origin (GetHits, util.h:
+ * 419-458): OutsideTwoHits {t0, t1} starts the ray at o + d t0 with tMax = t1 - t0,
+ * InsideOneHit {exit} tracks from o to the exit, no hit sees no medium; no surface offset.
+ * SampleT_maj still clips to the medium's bounds box, so an interface may stick out of it.
+ * Any other value: AVR_ERR_ARG. The setting persists across avr_medium_* calls. */
+int avr_graph_set_geometry(avr_context *ctx, int geometry);
+
+/* FreeGraphBuilder::BuildGraph's ray grid (free/free_graph_builder.cpp:143-199): steps x steps
+ * rays along in_dir, ray r = (x - 1) * steps + (y - 1) for x, y in 1..steps, from the grid
+ * point ((corner + xv * step * x) + yv * step * y) with (xv, yv) = CoordinateSystem(in_dir),
+ * corner = bounds_center - in_dir * max_dist_to_center * 2 - (xv + yv) * max_dist_to_center
+ * and step = max_dist_to_center * 2 / (steps + 1). Per ray: type (0 OutsideTwoHits, 2
+ * OutsideZeroHits, 3 InsideOneHit: the primitive's GetHits), o (r*3: the origin after
+ * SkipIntersection; the grid point when the ray misses) and t_first (the first segment's
+ * tMax; 0 on a miss). The sampling index of ray r's first walk is r * iterationsPerStep.
+ * steps: 0..32768 (0 does nothing). Host arrays, synchronous. */
+int avr_graph_start_rays(avr_context *ctx, const float bounds_center[3], float max_dist_to_center,
+                         const float in_dir[3], int steps, int *type, float *o, float *t_first);
 
 /* FreeGraphBuilder::TracePath (free/free_graph_builder.cpp:19-141), the medium walk: for
  * each of n_rays rays (origin o, direction d, first segment end t_first = the medium exit
@@ -457,8 +485,8 @@ int avr_graph_walks_from(avr_context *ctx, const avr_graph_sampling *smp, long l
 /* FreeGraphBuilder::ReinforceSparseVertices' rays (free_graph_builder.cpp:434-475): for each of
  * n vertices (ids, points n*3), GetSphereVolumePointsRandom(vertex_radius, point, n_rays) with
  * the sampler at StartPixelSample({0, 0}, cycle), then per sphere point p the medium's HG
- * Sample_p((1,0,0), Get2D()) at StartPixelSample(pixel(id * n_rays + p), cycle) and the medium
- * box crossing: o/d (n*n_rays*3), t_first (medium exit after SkipIntersection), valid
+ * Sample_p((1,0,0), Get2D()) at StartPixelSample(pixel(id * n_rays + p), cycle) and the
+ * primitive's crossing (avr_graph_set_geometry; the medium box by default): o/d (n*n_rays*3), t_first (medium exit after SkipIntersection), valid
  * (RayEntersVolume). The walk from each valid ray: avr_graph_walks_from(.., index0 =
  * id * n_rays + p, iterations 1, sample_index cycle, skip_dims 2, max_depth - 1). */
 int avr_graph_reinforce_rays(avr_context *ctx, const avr_graph_sampling *smp, int n, const int *vertex_ids,
@@ -469,7 +497,8 @@ int avr_graph_reinforce_rays(avr_context *ctx, const avr_graph_sampling *smp, in
  * ComputeRaysToSphere (graph/util.h:814-840) and SampleTransmittance (util.h:344-366):
  * light[v] = Inv4Pi * average over the disk points of vertex v (GetDiskPoints(vertex -
  * in_dir * max_dist_to_center * 2, sphere_radius, points_on_radius, in_dir)) whose ray along
- * in_dir crosses the medium box and the vertex's sphere inside the medium, of the average of
+ * in_dir crosses the primitive (avr_graph_set_geometry; the medium box by default) and the
+ * vertex's sphere inside it, of the average of
  * `iterations` ratio-tracking transmittances to a uniform point of the sphere chord.
  * vertices: n_vertices*3 (ids 0..n-1 in order). Host arrays, synchronous. */
 int avr_graph_light(avr_context *ctx, const avr_graph_sampling *smp, int n_vertices, const float *vertices,
@@ -572,17 +601,19 @@ int avr_graph_search_ranges(avr_context *ctx, const avr_graph_index *idx, int k,
 /* GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247), for sample indices
  * [spp_begin, spp_end) of every pixel, added to the film: avr_render's wavefront pass loop
  * (k_camera, then k_graph_render instead of the path kernels, then k_film; passes of at most
- * max_paths samples). Per sample: the camera ray crosses the medium's bounds box (the graph
- * tools' geometry model, DESIGN.md §9: a ray from outside starts at its entry point and
- * ends at the exit; a camera inside the box, commented out in the reference, tracks from its
+ * max_paths samples). Per sample: the camera ray (as the camera generates it, not moved to an
+ * interface) crosses the primitive of avr_graph_set_geometry, the medium's bounds box by
+ * default (the graph tools' geometry model, DESIGN.md §9: a ray from outside starts at its
+ * entry point and ends at the exit; a camera inside, commented out in the reference, tracks from its
  * origin; a miss gives L = 0), RNG(Hash(Get1D), Hash(Get1D)), SampleT_maj with the next Get1D
  * and the medium's coefficients at the sample's own wavelengths, the 3-way event choice on
  * channel 0; the first real scatter p gives L = lightSpectrum.Sample(lambda) *
  * ConnectToGraph(graph_from_render(p)), lightSpectrum = the distant light's scale * Lemit;
- * absorption or leaving the box L = 0. graph_from_render: row-major affine 4x4 (the
+ * absorption or leaving the primitive L = 0. graph_from_render: row-major affine 4x4 (the
  * reference's worldFromRender for a graph in world space), NULL = identity (the graph tools
  * here work in render space). Requires medium, camera and film, exactly one light of type 0
- * and no interface sphere / convex (AVR_ERR_STATE otherwise); sample-range and ZSobol limits
+ * and, while the context's graph geometry is 0, no interface sphere / convex (AVR_ERR_STATE
+ * otherwise; avr_graph_set_geometry(ctx, 1) takes the interface); sample-range and ZSobol limits
  * as avr_render. Work counters: the avr_stats fields avr_graph_walks uses (shadow_lookups,
  * shadow_items, shadow_dda_steps); the kernel's time in ms_medium. */
 int avr_graph_render(avr_context *ctx, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
@@ -615,7 +646,7 @@ int avr_graph_coverage(avr_context *ctx, const avr_graph_index *idx, long long n
 /* IntegrationAnalyzer::AnalyzeRay (integration_analyzer.cpp:55-163) for sample indices
  * [spp_begin, spp_end) of every pixel: avr_graph_render's pass loop with k_graph_analyze in
  * place of k_graph_render and k_graph_analyze_reduce in place of k_film; the film is not
- * touched. Per sample the camera ray crosses the medium's bounds box as avr_graph_render's
+ * touched. Per sample the camera ray crosses the graph geometry's primitive as avr_graph_render's
  * does (a miss analyses nothing) and then walks on as avr_graph_walks' paths do: per segment
  * RNG(Hash(Get1D), Hash(Get1D)) and SampleT_maj with the next Get1D, coefficients at the
  * sample's own wavelengths, the 3-way event choice on channel 0; absorption and leaving the

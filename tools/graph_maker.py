@@ -7,6 +7,10 @@ fork's `pbrt --graph` read. PREFIX_stats.json holds the graph's sizes and the se
 
 usage: python tools/graph_maker.py [--scene s-cloud] [--n 64] [--config CONFIG.json] --out PREFIX
                                    [--precision 9] [--search-ranges device] [--sampler 0] [--seed 0]
+                                   [--interface-sphere CX,CY,CZ,R]
+
+--interface-sphere bounds the medium by a sphere (world space): the scene gets it as its
+interface and the graph is made with the sphere as the primitive (primitive="interface").
 
 CONFIG.json is the reference's graph config (graphBuilder / lightingCalculator, util.h:750-812);
 without one the defaults below are used.
@@ -30,8 +34,18 @@ DEFAULT_CONFIG = {
 SCENES = ("s-cloud", "s-uniform")
 
 
-def make_scene(name, n):
-    """The preset with its distant light alone (the graph tools take exactly one)."""
+def interface_sphere(text):
+    """argparse type of --interface-sphere CX,CY,CZ,R: ((cx, cy, cz), r), world space."""
+    from acceleratedvolrenderer_amd.graph import parse_interface_sphere
+    try:
+        return parse_interface_sphere(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def make_scene(name, n, sphere=None):
+    """The preset with its distant light alone (the graph tools take exactly one); `sphere`:
+    its interface sphere ((cx, cy, cz), r) in world space."""
     import torch
     from acceleratedvolrenderer_amd import capi, scenes
     from acceleratedvolrenderer_amd.scene import Scene
@@ -44,10 +58,10 @@ def make_scene(name, n):
         base = scenes.s_cloud(density)
     else:
         base = scenes.s_uniform(n=n, variant="scatter")
-    return Scene(base.camera, base.film, base.medium, base.lights[:1], sampler=base.sampler)
+    return Scene(base.camera, base.film, base.medium, base.lights[:1], sampler=base.sampler, interface_sphere=sphere)
 
 
-def main(argv=None):
+def parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--scene", choices=SCENES, default="s-cloud", help="scene preset")
     p.add_argument("--n", type=int, default=64, help="the preset's grid resolution (n^3)")
@@ -57,7 +71,14 @@ def main(argv=None):
     p.add_argument("--search-ranges", choices=("device", "host", "scipy"), default="device")
     p.add_argument("--sampler", type=int, choices=(0, 1), default=0, help="0 independent, 1 zsobol")
     p.add_argument("--seed", type=int, default=0)
-    a = p.parse_args(argv)
+    p.add_argument("--interface-sphere", type=interface_sphere, metavar="CX,CY,CZ,R",
+                   help="bound the medium by this sphere (world space) and use it as the graph tools' primitive")
+    return p
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    primitive = "interface" if a.interface_sphere else "box"
     from acceleratedvolrenderer_amd import capi, graph
     if a.config:
         with open(a.config) as fh:
@@ -68,10 +89,10 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     seconds = {}
     t0 = time.perf_counter()
-    scene = make_scene(a.scene, a.n)
+    scene = make_scene(a.scene, a.n, a.interface_sphere)
     ctx = capi.Context(0)
     ctx.set_scene(scene)
-    md = graph.MediumData(scene)
+    md = graph.MediumData(scene, primitive)
     in_dir = (-np.asarray(scene.light_w[0], np.float32)).astype(np.float32)   # the way the light travels
     smp = graph.GraphSampling.for_config(cfg, sampler=a.sampler, seed=a.seed)
     seconds["scene"] = time.perf_counter() - t0
@@ -117,6 +138,8 @@ def main(argv=None):
 
     stats = {
         "scene": f"{a.scene} {a.n}^3",
+        "primitive": primitive,
+        "interface_sphere": [*a.interface_sphere[0], a.interface_sphere[1]] if a.interface_sphere else None,
         "amounts": {"vertices": int(g.num_vertices), "edges": int(len(g.edge_from))},
         "in_node_path_length": {"avg": float(g.in_node_path_length), "count": int(g.in_node_path_count)},
         "render_search_range": {"avg": float(np.mean(g.search_range, dtype=np.float64)) if active else None,
