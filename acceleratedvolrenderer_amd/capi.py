@@ -102,6 +102,8 @@ SIGNATURES = {
     "avr_set_ray_binning": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_majorant_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_pass_table_ahead": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "avr_set_pass_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "avr_pass_overlap_active": (ctypes.c_int, [ctypes.c_void_p]),
     "avr_set_majorant_res": (ctypes.c_int, [ctypes.c_void_p, c_int_p]),
     "avr_medium_boundary_sphere": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_float]),
     "avr_medium_boundary_convex": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int]),
@@ -340,6 +342,14 @@ class Context:
 
     def set_pass_table_ahead(self, on):
         _check(self.lib.avr_set_pass_table_ahead(self.h, 1 if on else 0))
+
+    def set_pass_overlap(self, on):
+        """Run the next pass's camera stage on the side stream while k_paths runs (default on)."""
+        _check(self.lib.avr_set_pass_overlap(self.h, 1 if on else 0))
+
+    def pass_overlap_active(self):
+        """Whether the last pass took camera records made ahead."""
+        return bool(self.lib.avr_pass_overlap_active(self.h))
 
     def record_lookups(self, d_points, cap, d_count):
         """Trace the wavefront kernels' density fetches into device buffers (0 / None stops)."""

@@ -57,6 +57,10 @@ hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, std::max<size_
 
 }  // namespace
 
+#ifndef AVR_PASS_OVERLAP_DEFAULT
+#define AVR_PASS_OVERLAP_DEFAULT 1
+#endif
+
 struct avr_context {
     int device = 0;
     // paths per pass: max_paths when the caller set one, else 16M for the wavefront kernels
@@ -173,6 +177,22 @@ struct avr_context {
     hipStream_t tstream = nullptr;
     hipEvent_t ev_cam = nullptr, ev_tab = nullptr;
     long long prev_call_begin = -1;   // avr_render's previous spp_begin (the call stride)
+    // Pass overlap (avr_set_pass_overlap): behind the table built ahead, tstream also runs the
+    // next pass's camera stage, into the other set of camera buffers, records and work heads
+    // (alt / d_heads_alt; ps and d_heads always name the set of the last rendered pass), while
+    // this pass's k_paths runs. The pass that follows takes those records when its camera
+    // stage's kernel arguments equal spec_params byte for byte and no setup call or readback
+    // came between (cfg_gen, bumped by AVR_QUIESCE); otherwise it runs its own camera stage.
+    int pass_overlap = AVR_PASS_OVERLAP_DEFAULT;
+    bool last_overlap = false;        // the last pass took camera records made ahead
+    int num_cus = 0;
+    avr::PathSoA alt{};               // rec, cam0..cam5, camw only
+    int *d_heads_alt = nullptr;
+    long long alt_cap = 0;            // samples the other set holds (rec_cap, or 0: none)
+    long long alt_failed_cap = 0;     // the rec_cap at which its allocation failed (not retried)
+    bool cam_spec_valid = false;      // tstream holds (or is making) camera records for spec_params
+    avr::Params spec_params{};
+    unsigned long long cfg_gen = 0, spec_gen = 0;
     // Level-A pass table (the same table for plo + 2, shared by four consecutive passes);
     // zs_akey names the build it holds (rebuilt when any field changes), zs_two_level 0 = off
     uint64_t *d_zs_atab = nullptr;
@@ -263,7 +283,20 @@ void free_pixel_order(avr_context *c) {
     c->h_pix_slot.clear();
 }
 
+// The other set of records, camera buffers and work heads (pass overlap)
+void free_alt(avr_context *c) {
+    for (void *p : {(void *)c->alt.rec, (void *)c->alt.cam0, (void *)c->alt.cam1, (void *)c->alt.cam2, (void *)c->alt.cam3,
+                    (void *)c->alt.cam4, (void *)c->alt.cam5, (void *)c->alt.camw, (void *)c->d_heads_alt})
+        if (p) (void)hipFree(p);
+    c->alt = {};
+    c->d_heads_alt = nullptr;
+    c->alt_cap = 0;
+}
+
 void free_records(avr_context *c) {
+    // camera records made ahead may still be written: let the side stream finish, and drop them
+    if (c->tstream && c->alt_cap) (void)hipStreamSynchronize(c->tstream);
+    c->cam_spec_valid = false;
     for (void *p : {(void *)c->ps.rec, (void *)c->ps.cam0, (void *)c->ps.cam1, (void *)c->ps.cam2, (void *)c->ps.cam3,
                     (void *)c->ps.cam4, (void *)c->ps.cam5, (void *)c->ps.camw})
         if (p) (void)hipFree(p);
@@ -271,6 +304,24 @@ void free_records(avr_context *c) {
     c->ps.cam3 = c->ps.cam5 = nullptr;
     c->ps.camw = nullptr;
     c->rec_cap = 0;
+    free_alt(c);
+}
+
+// ... as large as the first set. Without room for it the passes keep the serial chain (no error).
+void ensure_alt(avr_context *c) {
+    if (c->alt_cap == c->rec_cap || c->alt_failed_cap == c->rec_cap) return;
+    const size_t n = (size_t)c->rec_cap;
+    if (dalloc(&c->alt.rec, n) == hipSuccess && dalloc(&c->alt.cam0, n) == hipSuccess &&
+        dalloc(&c->alt.cam1, n) == hipSuccess && dalloc(&c->alt.cam2, n) == hipSuccess &&
+        dalloc(&c->alt.cam3, n) == hipSuccess && dalloc(&c->alt.cam4, n) == hipSuccess &&
+        dalloc(&c->alt.cam5, n) == hipSuccess && dalloc(&c->alt.camw, n) == hipSuccess &&
+        dalloc(&c->d_heads_alt, 9) == hipSuccess && hipMemset(c->d_heads_alt, 0xff, 9 * sizeof(int)) == hipSuccess) {
+        c->alt_cap = c->rec_cap;
+        return;
+    }
+    (void)hipGetLastError();
+    free_alt(c);
+    c->alt_failed_cap = c->rec_cap;
 }
 
 // k_paths' per-sample records (L, 16 B) and its camera stage (k_paths_camera: 6 x 16 B + the
@@ -651,6 +702,7 @@ const char *avr_last_error(void) { return g_err.c_str(); }
 // non-blocking stream: both first drain the context's stream.
 #define AVR_QUIESCE(c)                                                                              \
     do {                                                                                            \
+        if (c) ++(c)->cfg_gen;   /* camera records made ahead are not taken across this call */      \
         if ((c) && (c)->stream) {                                                                   \
             hipError_t qe_ = hipStreamSynchronize((c)->stream);                                     \
             if (qe_ == hipSuccess && (c)->tstream) qe_ = hipStreamSynchronize((c)->tstream);        \
@@ -682,12 +734,12 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
     c->stream = c->own_stream;
     if (dalloc(&c->d_counts, 4) != hipSuccess || dalloc(&c->d_stats, avr::kNumStats + 8) != hipSuccess ||
         hipHostMalloc((void **)&c->h_count, sizeof(int) * 4) != hipSuccess) {
-        delete c;
+        (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
     }
     if (dalloc(&c->d_heads, 9) != hipSuccess || hipMemset(c->d_heads, 0xff, 9 * sizeof(int)) != hipSuccess ||
         hipMemset(c->d_stats, 0, sizeof(unsigned long long) * (avr::kNumStats + 8)) != hipSuccess) {
-        delete c;
+        (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
     }
     {
@@ -697,9 +749,10 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
         // its own grid.
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-            delete c;
+            (void)avr_context_destroy(c);
             return fail(AVR_ERR_HIP, "device query failed");
         }
+        c->num_cus = prop.multiProcessorCount;
         // slot 32*image + 8*medium(0 grid, 1 vdb, 2 rgb, 3 homogeneous/cloud) + 4*zsobol + 2*emissive + gray; RGB grids
         // are never gray (their gray slots hold the 4-wavelength kernel)
 #define AVR_KP(em, gr, zs, med, im, fa) avr::k_paths<em, (med == 4 ? false : gr), zs, med, im, fa>
@@ -717,7 +770,7 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
         for (int k = 0; k < avr_context::kNumPaths; ++k) {
             int blocksPerCU = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kerns[k], 256, 0) != hipSuccess) {
-                delete c;
+                (void)avr_context_destroy(c);
                 return fail(AVR_ERR_HIP, "occupancy query failed");
             }
             c->paths_grid[k] = prop.multiProcessorCount * std::max(1, blocksPerCU);
@@ -768,8 +821,20 @@ int avr_set_pass_table_ahead(avr_context *c, int on) {
     if (!c || (on != 0 && on != 1)) return fail(AVR_ERR_ARG, "pass table ahead must be 0 or 1");
     c->ptab_spec = on;
     c->spec_valid = false;   // (the side stream is idle after the quiesce)
+    c->cam_spec_valid = false;
     return AVR_OK;
 }
+
+int avr_set_pass_overlap(avr_context *c, int on) {
+    AVR_QUIESCE(c);
+    if (!c || (on != 0 && on != 1)) return fail(AVR_ERR_ARG, "pass overlap must be 0 or 1");
+    c->pass_overlap = on;
+    c->spec_valid = false;
+    c->cam_spec_valid = false;
+    return AVR_OK;
+}
+
+int avr_pass_overlap_active(avr_context *c) { return c && c->last_overlap ? 1 : 0; }
 
 int avr_set_majorant_occupancy(avr_context *c, int on) {
     AVR_QUIESCE(c);
@@ -844,7 +909,11 @@ int avr_context_destroy(avr_context *c) {
 }
 
 int avr_set_stream(avr_context *c, void *s) {
+    // work built ahead on the side stream is ordered against the stream it was enqueued beside
+    AVR_QUIESCE(c);
     if (!c) return fail(AVR_ERR_ARG, "null context");
+    c->spec_valid = false;
+    c->cam_spec_valid = false;
     c->stream = s ? (hipStream_t)s : c->own_stream;
     return AVR_OK;
 }
@@ -1754,6 +1823,7 @@ int avr_film_spectral(avr_context *c, int n_buckets, float lambda_min, float lam
 static int fold_stats(avr_context *c) {
     if (c->timed.empty()) return AVR_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->tstream) HIP_TRY(hipStreamSynchronize(c->tstream));   // (a camera stage run ahead is timed there)
     for (const auto &t : c->timed) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, c->evpool[t.a], c->evpool[t.b]));
@@ -1879,8 +1949,15 @@ static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParam
     return AVR_OK;
 }
 
+// Pass overlap: whether k_paths is held to four blocks per CU while a camera stage runs beside
+// it, and the dynamic LDS that keeps a fifth block off a CU: 4 x (k_paths' 31.5 KB + pad) + the
+// camera block's 28.3 KB fit the 160 KiB, 5 x (31.5 KB + pad) do not (tests/test_overlap_resources.py)
+#ifndef AVR_OVERLAP_HOLD
+#define AVR_OVERLAP_HOLD 1
+#endif
+constexpr int kOverlapLdsPad = 1536;
 // next free pool event (folds first when the pool is full)
-static int next_event(avr_context *c, int *idx) {
+static int next_event(avr_context *c, int *idx, hipStream_t s = nullptr) {
     if (c->ev_used >= 512) {
         int rc = fold_stats(c);
         if (rc) return rc;
@@ -1891,7 +1968,7 @@ static int next_event(avr_context *c, int *idx) {
         c->evpool.push_back(e);
     }
     *idx = (int)c->ev_used++;
-    HIP_TRY(hipEventRecord(c->evpool[*idx], c->stream));
+    HIP_TRY(hipEventRecord(c->evpool[*idx], s ? s : c->stream));
     return AVR_OK;
 }
 #define EV_MARK(var)                      \
@@ -1928,6 +2005,7 @@ static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobo
             // a table built ahead reads the pixel table: let it finish, and drop it
             if (c->tstream) HIP_TRY(hipStreamSynchronize(c->tstream));
             c->spec_valid = false;
+            c->cam_spec_valid = false;
             if (c->d_zs_table) (void)hipFree(c->d_zs_table);
             c->d_zs_table = nullptr;
             for (int k = 0; k < 3; ++k) c->zs_key[k] = key[k];
@@ -1963,10 +2041,17 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
     if (c->image_lights_ready < c->n_image_lights) return fail(AVR_ERR_STATE, "image light without avr_light_image");
     if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
         return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
-    avr::smp::ZSobolParams zs{};
+    // (padding bytes zeroed too, here and in the Params below: a pass takes camera records made
+    // ahead only when its camera stage's arguments equal theirs byte for byte)
+    avr::smp::ZSobolParams zs;
+    std::memset(&zs, 0, sizeof zs);
     {
-        int rc = render_sampler(c, spp_end, seed, &zs);
+        avr::smp::ZSobolParams z{};
+        int rc = render_sampler(c, spp_end, seed, &z);
         if (rc) return rc;
+        zs.log2spp = z.log2spp; zs.nBase4Digits = z.nBase4Digits; zs.seed = z.seed;
+        zs.upper = z.upper; zs.dmax = z.dmax;
+        zs.ptab = z.ptab; zs.pdims = z.pdims; zs.plo = z.plo; zs.ctab = z.ctab;
     }
     const long long P = (long long)c->film.width * c->film.height;
     if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
@@ -1983,6 +2068,14 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
     const long long need = P * std::min<long long>(Smax, std::max(1, spp_end - spp_begin));
     int rc = persistent ? ensure_records(c, need) : ensure_paths(c, need);
     if (rc) return rc;
+    // Pass overlap: only the parked k_paths instantiations (gray non-emissive GridMedium without
+    // image lights) leave a block of the camera stage room beside four of their own on a CU;
+    // only on the context's own stream (the side stream is ordered against it by events), and
+    // only behind the ZSobol pass table built ahead
+    const bool overlap_ok = persistent && c->pass_overlap && c->ptab_spec && c->sampler_kind == 1 &&
+                            c->stream == c->own_stream && c->gray && c->med.type == 0 && !c->med.emissive &&
+                            c->n_image_lights == 0 && !c->lights.power;
+    if (overlap_ok) ensure_alt(c);
     EV_MARK(evStart);
     // the stride between consecutive calls' first sample indices (S for pbrt's pass loop and the
     // one-GPU bench, N x S for a rank of an N-GPU sample shard): where the pass after this call's
@@ -1992,8 +2085,10 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
     for (long long base = spp_begin; base < spp_end; base += Smax) {
         const int S = (int)std::min<long long>(Smax, spp_end - base);
         bool spec_next = false;   // build the next pass's ZSobol table ahead (ptab_spec)
-        avr::smp::ZSobolParams spec_zs{};
-        avr::Params p{};
+        avr::smp::ZSobolParams spec_zs;
+        std::memset(&spec_zs, 0, sizeof spec_zs);
+        avr::Params p;
+        std::memset(&p, 0, sizeof p);
         p.med = c->med;
         p.lights = c->lights;
         p.cam = c->cam;
@@ -2037,6 +2132,10 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
             // makes the stats readback fail (stats[7])
             p.heads = c->d_heads;
             p.pass_gen = ++c->pass_gen & 0x7fffffff;
+            bool cam_taken = false, cam_next = false;
+            avr::Params pcam{};   // the camera stage's arguments of this pass
+            void (*kcam_next)(avr::Params) = nullptr;
+            int cgrid_next = 0;
             // the camera stage: one lane per sample (k_paths_camera)
             {
                 const int sv = c->sampler_kind == 0 ? 0 : (avr::smp::zsobol_wide(p.zs) ? 2 : 1);
@@ -2063,6 +2162,7 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
                     long long key[kPtabKey];
                     ptab_key(c, zs, base, plo, key);
                     int buf = -1;
+                    bool cam_ahead = false;   // tstream made (or is making) camera records beside that table
                     if (c->spec_valid) {
                         // the table the previous pass built ahead on the side stream (ptab_build's
                         // caller below): this stream waits for it, whether it is used or not, so
@@ -2071,7 +2171,9 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
                         bool same = true;
                         for (int k = 0; k < kPtabKey; ++k) same = same && key[k] == c->spec_key[k];
                         if (same) buf = c->spec_buf;
+                        cam_ahead = same && c->cam_spec_valid && c->spec_gen == c->cfg_gen && overlap_ok;
                         c->spec_valid = false;
+                        c->cam_spec_valid = false;
                     }
                     if (buf < 0) {
                         buf = 1 - c->tab_buf;
@@ -2087,17 +2189,47 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
                         p.zs.plo = plo;
                         spec_next = c->ptab_spec != 0;
                         spec_zs = zs;
+                        if (cam_ahead) {
+                            // the records made ahead are this pass's when the camera stage would be
+                            // launched with the very arguments they were made with
+                            avr::Params t = p;
+                            t.ps.rec = c->alt.rec;
+                            t.ps.cam0 = c->alt.cam0; t.ps.cam1 = c->alt.cam1; t.ps.cam2 = c->alt.cam2;
+                            t.ps.cam3 = c->alt.cam3; t.ps.cam4 = c->alt.cam4; t.ps.cam5 = c->alt.cam5;
+                            t.ps.camw = c->alt.camw;
+                            t.heads = c->d_heads_alt;
+                            if (std::memcmp(&t, &c->spec_params, sizeof t) == 0) {
+                                std::swap(c->ps.rec, c->alt.rec);
+                                std::swap(c->ps.cam0, c->alt.cam0); std::swap(c->ps.cam1, c->alt.cam1);
+                                std::swap(c->ps.cam2, c->alt.cam2); std::swap(c->ps.cam3, c->alt.cam3);
+                                std::swap(c->ps.cam4, c->alt.cam4); std::swap(c->ps.cam5, c->alt.cam5);
+                                std::swap(c->ps.camw, c->alt.camw);
+                                std::swap(c->d_heads, c->d_heads_alt);
+                                p = t;
+                                cam_taken = true;
+                            }
+                        }
                     }
                 }
                 // 16384 blocks (64 per CU, ~14 samples per thread at the bench's pass): the measured optimum
                 // between one round of resident blocks and one sample per thread
                 // (profiles/r06_ab_camera_grid.json)
                 const int cgrid = blocks_for(n0, 256, 256 * 64);
-                hipLaunchKernelGGL(kcam[c->render_mode ? 1 : 0][sv], dim3(cgrid), dim3(256), 0, c->stream, p);
-                HIP_TRY(hipGetLastError());
-                EV_MARK(ec1);
-                c->timed.push_back({ec, ec1, &avr_stats::ms_camera, false});
+                pcam = p;
+                if (!cam_taken) {
+                    hipLaunchKernelGGL(kcam[c->render_mode ? 1 : 0][sv], dim3(cgrid), dim3(256), 0, c->stream, p);
+                    HIP_TRY(hipGetLastError());
+                    EV_MARK(ec1);
+                    c->timed.push_back({ec, ec1, &avr_stats::ms_camera, false});
+                }
                 if (spec_next) HIP_TRY(hipEventRecord(c->ev_cam, c->stream));
+                c->last_overlap = cam_taken;
+                // the next pass's camera stage follows its table on the side stream
+                cam_next = spec_next && overlap_ok && c->alt_cap >= n0 && c->alt_cap == c->rec_cap;
+                if (cam_next) {
+                    kcam_next = kcam[c->render_mode ? 1 : 0][sv];
+                    cgrid_next = cgrid;
+                }
             }
             EV_MARK(e0);
             // gray medium: sigma_a and sigma_s tables constant over all 471 wavelengths
@@ -2107,7 +2239,12 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
             const bool general_lights = c->n_image_lights > 0 || c->lights.power;
             const int kv = ((((c->render_mode * 2 + (general_lights ? 1 : 0)) * 4 + mk) * 3 + sv) * 2 +
                             (c->med.emissive ? 1 : 0)) * 2 + (c->gray && c->med.type != 4 ? 1 : 0);
-            hipLaunchKernelGGL(c->kpaths[kv], dim3(c->paths_grid[kv]), dim3(256), 0, c->stream, p);
+            // With a camera stage beside it, k_paths is launched as four blocks per CU (the grid,
+            // and kOverlapLdsPad bytes of dynamic LDS nobody uses so that a fifth block does not
+            // fit a CU): the fifth wave slot of every SIMD and the LDS left take a camera block
+            const bool hold = cam_next && AVR_OVERLAP_HOLD != 0 && c->paths_grid[kv] > 4 * c->num_cus;
+            hipLaunchKernelGGL(c->kpaths[kv], dim3(hold ? 4 * c->num_cus : c->paths_grid[kv]), dim3(256),
+                               hold ? kOverlapLdsPad : 0, c->stream, p);
             HIP_TRY(hipGetLastError());
             {
                 const int kmed = c->med.type == 3 ? 3 : (c->med.type == 4 ? 4 : (c->med.type == 1 || c->med.type == 2 ? 1 : 0));
@@ -2145,11 +2282,42 @@ int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_dep
                 const int tb = 1 - c->tab_buf;
                 // (not timed: events around it would measure its wait for the drain too)
                 { int rc2 = ptab_build(c, c->tstream, spec_zs, nb, nplo, tb, in_call || call_stride == S); if (rc2) return rc2; }
+                bool cam_spec = false;
+                if (cam_next && c->d_zs_ptab[tb]) {
+                    // ... and that pass's camera stage behind it, into the other set: its last
+                    // readers, the previous pass's k_paths and k_film, came before ev_cam on the
+                    // main stream. The pass is assumed to have this one's size and arguments;
+                    // the pass itself checks that (spec_params).
+                    avr::Params q = pcam;
+                    q.sample_base = (int)nb;
+                    q.pass_gen = (c->pass_gen + 1) & 0x7fffffff;
+                    q.cam_quad = (nb % 4 == 0 && S % 4 == 0 && q.zs.log2spp <= 16) ? 1 : 0;
+                    q.zs = spec_zs;
+                    q.zs.ptab = c->d_zs_ptab[tb];
+                    q.zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[tb] : nullptr;
+                    q.zs.pdims = c->zs_pdims;
+                    q.zs.plo = nplo;
+                    q.ps.rec = c->alt.rec;
+                    q.ps.cam0 = c->alt.cam0; q.ps.cam1 = c->alt.cam1; q.ps.cam2 = c->alt.cam2;
+                    q.ps.cam3 = c->alt.cam3; q.ps.cam4 = c->alt.cam4; q.ps.cam5 = c->alt.cam5;
+                    q.ps.camw = c->alt.camw;
+                    q.heads = c->d_heads_alt;
+                    int sc0, sc1;
+                    { int rc2 = next_event(c, &sc0, c->tstream); if (rc2) return rc2; }
+                    hipLaunchKernelGGL(kcam_next, dim3(cgrid_next), dim3(256), 0, c->tstream, q);
+                    HIP_TRY(hipGetLastError());
+                    { int rc2 = next_event(c, &sc1, c->tstream); if (rc2) return rc2; }
+                    c->timed.push_back({sc0, sc1, &avr_stats::ms_camera, false});
+                    c->spec_params = q;
+                    c->spec_gen = c->cfg_gen;
+                    cam_spec = true;
+                }
                 HIP_TRY(hipEventRecord(c->ev_tab, c->tstream));
                 if (c->d_zs_ptab[tb]) {
                     ptab_key(c, spec_zs, nb, nplo, c->spec_key);
                     c->spec_buf = tb;
                     c->spec_valid = true;
+                    c->cam_spec_valid = cam_spec;
                 }
             }
             c->last_base = (int)base;
@@ -2292,6 +2460,7 @@ int avr_transmittance(avr_context *c, long long n, const float *p0, const float 
 int avr_sync(avr_context *c) {
     if (!c) return fail(AVR_ERR_ARG, "null context");
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->tstream) HIP_TRY(hipStreamSynchronize(c->tstream));
     return AVR_OK;
 }
 

@@ -108,6 +108,18 @@ int avr_set_majorant_occupancy(avr_context *ctx, int on);
  * pass whose indices differ builds its table as before. 0 = build every table in front of its camera stage.
  * Results unchanged (a schedule of ZSobolSampler::GetSampleIndex's digits, samplers.h:225-330). */
 int avr_set_pass_table_ahead(avr_context *ctx, int on);
+/* Pass overlap (default 1): behind the table built ahead, the side stream also runs the next
+ * pass's camera stage, into a second set of camera buffers, records and work heads (+116 B
+ * per sample of the largest pass; without room for it the chain stays serial), while this
+ * pass's k_paths runs held to four blocks per CU. Active for the k_paths instantiations with
+ * a free wave slot (gray, non-emissive GridMedium without image lights or the power light
+ * sampler), the ZSobol sampler with its pass table ahead, and the context's own stream. The
+ * next pass is predicted like its table; it takes the records only if its camera stage would
+ * be launched with byte-identical arguments and no setup call or readback came between, and
+ * runs its own camera stage otherwise. Results do not depend on the setting.
+ * avr_pass_overlap_active: whether the last pass took records made ahead. */
+int avr_set_pass_overlap(avr_context *ctx, int on);
+int avr_pass_overlap_active(avr_context *ctx);
 /* k_paths: refill a wave's idle lanes with new samples once at least `lanes` (1..64)
  * are idle (or none is busy); larger values batch the per-event handlers across lanes.
  * 0 = default (the measured optima in both render modes: 32; 20 for a non-emissive
@@ -140,7 +152,9 @@ int avr_grid_layout_active(avr_context *ctx);
  * order; a new film resets it. Results are identical in any order (per-pixel sums still
  * add the pixel's samples in sampleIndex order). */
 int avr_set_pixel_order(avr_context *ctx, const int *order, long long n);
-/* Run all work of this context on `hip_stream` (a hipStream_t; NULL = the context's own stream). */
+/* Run all work of this context on `hip_stream` (a hipStream_t; NULL = the context's own stream).
+ * Drains the previous stream and the side stream first and drops what was built ahead; on a
+ * caller's stream every pass runs its stages in series (no pass overlap). */
 int avr_set_stream(avr_context *ctx, void *hip_stream);
 
 /* GridMedium (media.h:271-275, media.cpp:249-330). density is nx*ny*nz floats,
@@ -371,6 +385,7 @@ int avr_transmittance(avr_context *ctx, long long n, const float *p0, const floa
                       float *tr);
 int avr_transmittance_device(avr_context *ctx, long long n, const float *p0, const float *p1, const float *lambda,
                              float *tr);
+/* Waits for the context's stream and for its side stream (work built ahead for a next pass). */
 int avr_sync(avr_context *ctx);
 int avr_get_stats(avr_context *ctx, avr_stats *out);   /* waits for queued work */
 int avr_reset_stats(avr_context *ctx);
