@@ -50,6 +50,15 @@ class AvrGraphSampling(ctypes.Structure):
                 ("film_width", ctypes.c_int), ("film_height", ctypes.c_int), ("resolution_x", ctypes.c_int)]
 
 
+class AvrGraphMergeStats(ctypes.Structure):
+    """avr_graph_merge_stats (include/avr.h): one avr_graph_add_walks_device call."""
+    _fields_ = [("rounds", ctypes.c_int), ("points", ctypes.c_longlong), ("new_vertices", ctypes.c_longlong),
+                ("ms_sort", ctypes.c_double), ("ms_rounds", ctypes.c_double), ("ms_replay", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # avr_graph_set_geometry's values by the names graph.MediumData(primitive=...) uses
 GRAPH_GEOMETRY = {"box": 0, "interface": 1}
 
@@ -197,6 +206,14 @@ SIGNATURES = {
                                                 c_float_p, c_float_p, c_float_p, c_int_p]),
     "avr_graph_add_walks_from": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, c_float_p, c_int_p,
                                                 c_int_p]),
+    "avr_graph_merge_assign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, c_float_p, c_int_p,
+                                              c_int_p, c_int_p, c_int_p]),
+    "avr_graph_merge_assign_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                     c_float_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "avr_graph_add_walks_assigned": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, c_float_p,
+                                                    c_int_p, c_int_p, c_int_p]),
+    "avr_graph_add_walks_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                  c_float_p, c_int_p, c_int_p, ctypes.c_void_p]),
     "avr_graph_out_degrees": (ctypes.c_int, [ctypes.c_void_p, c_int_p]),
     "avr_graph_count_in_radius": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, ctypes.c_float, c_int_p]),
     "avr_graph_light": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AvrGraphSampling), ctypes.c_int, c_float_p,
@@ -807,6 +824,56 @@ class Graph:
         sv = np.ascontiguousarray(start_vertex, np.int32)
         _check(self.lib.avr_graph_add_walks_from(self.h, len(counts), int(max_depth), _fp(points),
                                                  counts.ctypes.data_as(c_int_p), sv.ctypes.data_as(c_int_p)))
+
+    @staticmethod
+    def _walks(points, counts, max_depth, start_vertex):
+        points = np.ascontiguousarray(points, np.float32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        if points.size != len(counts) * int(max_depth) * 3:
+            raise ValueError("points must hold n_walks x max_depth x 3 floats")
+        sv = None if start_vertex is None else np.ascontiguousarray(start_vertex, np.int32)
+        if sv is not None and len(sv) != len(counts):
+            raise ValueError("one start vertex per walk")
+        return points, counts, sv, (sv.ctypes.data_as(c_int_p) if sv is not None else None)
+
+    def merge_assign(self, points, counts, max_depth, start_vertex=None, ctx=None):
+        """The vertex merge in rounds (avr_graph_merge_assign; with a Context
+        avr_graph_merge_assign_device, the rounds on the GPU): (vertex_of_point (n_walks,
+        max_depth) int32, -1 past a walk's count, and the rounds run). The graph is unchanged;
+        the ids are the ones add_walks / add_walks_from would give these walks."""
+        points, counts, sv, svp = self._walks(points, counts, max_depth, start_vertex)
+        out = np.full((len(counts), int(max_depth)), -1, np.int32)
+        rounds = ctypes.c_int(0)
+        if ctx is None:
+            _check(self.lib.avr_graph_merge_assign(self.h, len(counts), int(max_depth), _fp(points),
+                                                   counts.ctypes.data_as(c_int_p), svp, out.ctypes.data_as(c_int_p),
+                                                   ctypes.byref(rounds)))
+        else:
+            _check(self.lib.avr_graph_merge_assign_device(ctx.h, self.h, len(counts), int(max_depth), _fp(points),
+                                                          counts.ctypes.data_as(c_int_p), svp,
+                                                          out.ctypes.data_as(c_int_p), ctypes.byref(rounds)))
+        return out, rounds.value
+
+    def merge_assign_device(self, ctx, points, counts, max_depth, start_vertex=None):
+        return self.merge_assign(points, counts, max_depth, start_vertex, ctx=ctx)
+
+    def add_walks_assigned(self, points, counts, max_depth, vertex_of_point, start_vertex=None):
+        """add_walks / add_walks_from with every point's vertex given (merge_assign's ids)."""
+        points, counts, sv, svp = self._walks(points, counts, max_depth, start_vertex)
+        vop = np.ascontiguousarray(vertex_of_point, np.int32)
+        if vop.size != len(counts) * int(max_depth):
+            raise ValueError("vertex_of_point must hold n_walks x max_depth ids")
+        _check(self.lib.avr_graph_add_walks_assigned(self.h, len(counts), int(max_depth), _fp(points),
+                                                     counts.ctypes.data_as(c_int_p), svp, vop.ctypes.data_as(c_int_p)))
+
+    def add_walks_device(self, ctx, points, counts, max_depth, start_vertex=None):
+        """add_walks / add_walks_from with the merge on the GPU (avr_graph_add_walks_device):
+        the same graph; returns the call's avr_graph_merge_stats as a dict."""
+        points, counts, sv, svp = self._walks(points, counts, max_depth, start_vertex)
+        stats = AvrGraphMergeStats()
+        _check(self.lib.avr_graph_add_walks_device(ctx.h, self.h, len(counts), int(max_depth), _fp(points),
+                                                   counts.ctypes.data_as(c_int_p), svp, ctypes.byref(stats)))
+        return stats.as_dict()
 
     def out_degrees(self):
         nv, _ = self.size()

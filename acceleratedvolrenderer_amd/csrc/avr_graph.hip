@@ -31,6 +31,10 @@
 //                  then one lane per pixel adds the pass's records to the pixel's sums.
 //  k_graph_start_rays  BuildGraph's ray grid (free_graph_builder.cpp:143-199): one lane per
 //                  grid ray, its crossing of the primitive and SkipIntersection.
+//  k_graph_merge_round  the vertex merge of TracePath (:71-93) in rounds (avr_graph_merge.h):
+//  k_graph_merge_flags  one lane per unfinalised scatter point runs merge_step; then the
+//  k_graph_merge_scan   id scan over the final states (new-vertex flags per wave, their
+//  k_graph_merge_ids    prefix sums, vertex_of_point).
 //
 // Geometry model (shared with the oracle): the medium's boundary primitive is
 // its bounds box (medium-space slab test, ray mapped without error offsets), kGeom 0, or, on
@@ -39,6 +43,7 @@
 // Sphere::BasicIntersect's interval quadric once for both roots. The geometry is a template
 // parameter: the kGeom 0 instantiations are the box-only kernels' code.
 #include "avr_graph_index.h"
+#include "avr_graph_merge.h"
 
 namespace avr {
 namespace graph {
@@ -661,6 +666,126 @@ __global__ void __launch_bounds__(256) k_graph_analyze_reduce(int pixels, int sa
             a.range = a.range + r.range;
         }
         acc[pix] = a;
+    }
+}
+
+// merge_step's states in device memory: relaxed atomics at agent scope, so that a sweep sees
+// what other lanes of the same launch have already decided (a stale read only costs a round)
+struct MergeStateDev {
+    int *s;
+    __device__ __forceinline__ int load(int i) const {
+        return __hip_atomic_load(s + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void store(int i, int v) {
+        __hip_atomic_store(s + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// One round of the vertex merge (avr_graph_merge.h): one lane per unfinalised point, work[0 ..
+// nwork) in cell order, AVR_MERGE_SWEEPS steps at most per point (a fixed number: later steps
+// see what the wave's own lanes and its neighbours decided in the earlier ones). No lane
+// waits: a point that cannot be finalised yet goes to next[], appended with one atomic per
+// wave on *nleft, which is also the count the host reads. Measured with 4 steps
+// (tools/graph_merge_profile.py, radius modifier 20): 93 rounds for 166, 63.0 ms for 64.9 ms
+// of rounds: the time is the early rounds' scans, not the number of rounds, so 1 stays.
+#ifndef AVR_MERGE_SWEEPS
+#define AVR_MERGE_SWEEPS 1
+#endif
+__global__ void __launch_bounds__(256) k_graph_merge_round(graph::MergeView mv, int *state, const int *__restrict__ work,
+                                                           int nwork, int *__restrict__ next, int *__restrict__ nleft) {
+    MergeStateDev st{state};
+    for (long long base = blockIdx.x * 256ll; base < nwork; base += gridDim.x * 256ll) {
+        const long long idx = base + threadIdx.x;
+        const int i = idx < nwork ? work[idx] : -1;
+        bool left = i >= 0;
+        for (int sweep = 0; sweep < AVR_MERGE_SWEEPS && left; ++sweep) left = !graph::merge_step(mv, i, st);
+        const unsigned long long m = __ballot(left);
+        if (m == 0) continue;
+        const int lane = __lane_id(), leader = __ffsll(m) - 1;
+        int b = 0;
+        if (lane == leader) b = atomicAdd(nleft, __popcll(m));
+        b = __shfl(b, leader);
+        if (left) next[b + __popcll(m & ((1ull << lane) - 1ull))] = i;
+    }
+}
+
+// The same round with one wave per point, for the rounds with few points left, where a round
+// lasts as long as one lane's scan: the wave's lanes share the scan (consecutive records,
+// coalesced), join their parts by butterfly, and lane 0 decides and appends.
+__global__ void __launch_bounds__(256) k_graph_merge_round_wave(graph::MergeView mv, int *state,
+                                                                const int *__restrict__ work, int nwork,
+                                                                int *__restrict__ next, int *__restrict__ nleft) {
+    MergeStateDev st{state};
+    const int lane = __lane_id();
+    for (long long w = (blockIdx.x * 256ll + threadIdx.x) >> 6; w < nwork; w += (gridDim.x * 256ll) >> 6) {
+        const int i = work[w];
+        const int cur = __shfl(st.load(i), 0);   // one value for the wave
+        if (cur >= 0) continue;
+        const graph::MergeRec q = mv.ent[mv.v0 + i];
+        graph::MergeScan r = graph::merge_scan(mv, mv.v0 + i, q, st, lane, 64);
+        for (int off = 32; off > 0; off >>= 1) {
+            graph::MergeScan o;
+            o.best = __shfl_xor(r.best, off);
+            o.open = __shfl_xor(r.open, off);
+            o.bestD = __shfl_xor(r.bestD, off);
+            o.openD = __shfl_xor(r.openD, off);
+            graph::merge_scan_join(&r, o);
+        }
+        if (lane == 0 && !graph::merge_decide(mv, i, cur, q, r, st)) next[atomicAdd(nleft, 1)] = i;
+    }
+}
+
+// The id scan over the final states, 64 points per wave: mask[w] = which of them are new
+// vertices (state == own seq), cnt[w] = how many ...
+__global__ void __launch_bounds__(256) k_graph_merge_flags(int v0, int n, const int *__restrict__ state,
+                                                           unsigned long long *__restrict__ mask, int *__restrict__ cnt) {
+    const long long lanes = ((long long)n + 63) / 64 * 64;
+    for (long long idx = blockIdx.x * 256ll + threadIdx.x; idx < lanes; idx += gridDim.x * 256ll) {
+        const bool isNew = idx < n && state[idx] == v0 + (int)idx;
+        const unsigned long long m = __ballot(isNew);
+        if (__lane_id() == 0) {
+            mask[idx >> 6] = m;
+            cnt[idx >> 6] = __popcll(m);
+        }
+    }
+}
+
+// ... cnt[] to its exclusive prefix sum in place (one block: a run of waves per lane, the 256
+// run sums scanned in LDS), *total = the new vertices ...
+__global__ void __launch_bounds__(256) k_graph_merge_scan(int nw, int *__restrict__ cnt, int *__restrict__ total) {
+    __shared__ int s_part[256];
+    const int per = (nw + 255) / 256, t = threadIdx.x;
+    const int a = min(t * per, nw), b = min(a + per, nw);
+    int sum = 0;
+    for (int j = a; j < b; ++j) sum += cnt[j];
+    s_part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = t >= off ? s_part[t - off] : 0;
+        __syncthreads();
+        s_part[t] += v;
+        __syncthreads();
+    }
+    int run = s_part[t] - sum;
+    for (int j = a; j < b; ++j) {
+        const int c = cnt[j];
+        cnt[j] = run;
+        run += c;
+    }
+    if (t == 255) *total = s_part[255];
+}
+
+// ... and vertex_of_point: an existing vertex's id as it is, a new point's V0 + its rank
+__global__ void __launch_bounds__(256) k_graph_merge_ids(int v0, int n, const int *__restrict__ state,
+                                                         const unsigned long long *__restrict__ mask,
+                                                         const int *__restrict__ woff, int *__restrict__ ids) {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+        int t = state[i];
+        if (t >= v0) {
+            const int j = t - v0;
+            t = v0 + woff[j >> 6] + __popcll(mask[j >> 6] & ((1ull << (j & 63)) - 1ull));
+        }
+        ids[i] = t;
     }
 }
 

@@ -4,6 +4,7 @@
 #include "avr_graph_host.h"
 
 #include <atomic>
+#include <chrono>
 
 namespace {
 
@@ -411,6 +412,257 @@ int avr_graph_add_walks_from(avr_graph *g, long long n_walks, int max_depth, con
     }
     return AVR_OK;
 }
+
+}  // extern "C"
+
+namespace {
+
+// The walk arguments of the merge entries: counts and start vertices (NULL: none) in range as
+// avr_graph_add_walks_from checks them; vertex_of_point is n_walks x max_depth
+int merge_arguments(const avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                    const int *start_vertex, const int *vertex_of_point) {
+    if (!g || n_walks < 0 || max_depth < 0) return fail(AVR_ERR_ARG, "bad walks");
+    if (n_walks > 0 && (!counts || (max_depth > 0 && (!points || !vertex_of_point)))) return fail(AVR_ERR_ARG, "null buffer");
+    for (long long w = 0; w < n_walks; ++w) {
+        const int k = counts[w], sv = start_vertex ? start_vertex[w] : -1;
+        if (k < 0 || k > max_depth) return fail(AVR_ERR_ARG, "walk count out of range");
+        if (sv < -1 || sv >= (long long)g->b.NumVertices()) return fail(AVR_ERR_ARG, "start vertex out of range");
+        if (k > (sv >= 0 ? max_depth - 1 : max_depth)) return fail(AVR_ERR_ARG, "walk count out of range");
+    }
+    return AVR_OK;
+}
+
+int merge_grid(const avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+               const int *start_vertex, avr::graph::MergeGrid *mg) {
+    if (const char *msg = mg->Build(g->b.Radius(), g->b.NumVertices(), g->b.Vertices().data(), n_walks, max_depth, points,
+                                    counts, start_vertex))
+        return fail(AVR_ERR_ARG, msg);
+    return AVR_OK;
+}
+
+// ids per point in seq order -> vertex_of_point (n_walks x max_depth, -1 past a walk's count)
+void merge_scatter(const avr::graph::MergeGrid &mg, long long n_walks, int max_depth, const int *ids,
+                   int *vertex_of_point) {
+    const std::vector<int> &first = mg.WalkFirst();
+    for (long long w = 0; w < n_walks; ++w) {
+        const int k = first[(size_t)w + 1] - first[(size_t)w];
+        int *row = vertex_of_point + (size_t)w * max_depth;
+        for (int j = 0; j < max_depth; ++j) row[j] = j < k ? ids[first[(size_t)w] + j] : -1;
+    }
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Rounds with at most this many open points run one wave per point (k_graph_merge_round_wave).
+// Measured (tools/graph_merge_profile.py, radius modifier 20, 262 k points, ms of rounds): one
+// lane per point throughout 82.2, one wave per point throughout 141.2, this threshold 64.9.
+#ifndef AVR_MERGE_WAVE_BELOW
+#define AVR_MERGE_WAVE_BELOW 32768
+#endif
+constexpr int kMergeWaveBelow = AVR_MERGE_WAVE_BELOW;
+
+// The rounds and the id scan on the device over an uploaded copy of `mg`: ids per point in
+// seq order. *ms_upload: the allocation and the upload, which the caller counts with the sort.
+int merge_assign_device(avr_context *c, const avr::graph::MergeGrid &mg, std::vector<int> *ids, int *rounds,
+                        int *new_vertices, double *ms_upload) {
+    const avr::graph::MergeView h = mg.View();
+    const int n = h.n;
+    const size_t E = (size_t)h.v0 + (size_t)n, cells = mg.NumCells(), nw = ((size_t)n + 63) / 64;
+    ids->assign((size_t)n, 0);
+    *rounds = 0;
+    *new_vertices = 0;
+    *ms_upload = 0;
+    if (n == 0) return AVR_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(c->device));
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t szRec = pad(E * sizeof(avr::graph::MergeRec)), szMask = pad(nw * 8), szStart = pad((cells + 1) * 4);
+    const size_t szN = pad((size_t)n * 4), szCnt = pad(nw * 4);
+    constexpr int kCtr = 256;   // one counter per round, zeroed kCtr at a time; the last takes the scan's total
+    char *buf = nullptr;
+    HIP_TRY(dalloc(&buf, 2 * szRec + szMask + szStart + 5 * szN + szCnt + kCtr * 4));
+    char *d = buf;
+    auto take = [&d](size_t b) { char *p = d; d += b; return p; };
+    auto *dRec = (avr::graph::MergeRec *)take(szRec), *dEnt = (avr::graph::MergeRec *)take(szRec);
+    auto *dMask = (unsigned long long *)take(szMask);
+    int *dStart = (int *)take(szStart), *dPrev = (int *)take(szN), *dState = (int *)take(szN);
+    int *dWork[2] = {(int *)take(szN), (int *)take(szN)};
+    int *dIds = (int *)take(szN), *dCnt = (int *)take(szCnt), *dCtr = (int *)take(kCtr * 4);
+    hipError_t e = hipMemcpyAsync(dRec, h.rec, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dEnt, h.ent, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dStart, h.cell_start, (cells + 1) * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dPrev, h.prev, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dWork[0], mg.Work().data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dState, 0xff, (size_t)n * 4, c->stream);   // kMergeUndecided
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    *ms_upload = ms_since(t0);
+    avr::graph::MergeView dv = h;
+    dv.rec = dRec;
+    dv.ent = dEnt;
+    dv.cell_start = dStart;
+    dv.prev = dPrev;
+    // one sweep per launch over the points still open; the host reads the count after each
+    int left = n, r = 0, cur = 0;
+    bool stuck = false;
+    while (e == hipSuccess && left > 0) {
+        int now = 0;
+        int *ctr = dCtr + r % (kCtr - 1);
+        if (r % (kCtr - 1) == 0) e = hipMemsetAsync(dCtr, 0, kCtr * 4, c->stream);
+        if (e != hipSuccess) break;
+        if (left <= kMergeWaveBelow)
+            hipLaunchKernelGGL(avr::k_graph_merge_round_wave, dim3(blocks_for(left, 4, 256 * 64)), dim3(256), 0, c->stream,
+                               dv, dState, dWork[cur], left, dWork[cur ^ 1], ctr);
+        else
+            hipLaunchKernelGGL(avr::k_graph_merge_round, dim3(blocks_for(left, 256, 256 * 64)), dim3(256), 0, c->stream, dv,
+                               dState, dWork[cur], left, dWork[cur ^ 1], ctr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&now, ctr, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) break;
+        ++r;
+        if (now < 0 || now >= left) {   // a round must finalise a point: never loop on a bug
+            stuck = true;
+            break;
+        }
+        left = now;
+        cur ^= 1;
+    }
+    int news = 0;
+    if (e == hipSuccess && !stuck) {
+        hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
+                           dState, dMask, dCnt);
+        hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dCtr + kCtr - 1);
+        hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
+                           dState, dMask, dCnt, dIds);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(ids->data(), dIds, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&news, dCtr + kCtr - 1, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph merge: ") + hipGetErrorString(e));
+    if (stuck) return fail(AVR_ERR_INTERNAL, "graph merge: a round finalised no point");
+    *rounds = r;
+    *new_vertices = news;
+    return AVR_OK;
+}
+
+// The ids of walk w's points: row w of vertex_of_point (first == null), or the compact ids in
+// seq order from MergeGrid::WalkFirst
+const int *merge_row(const int *ids, int max_depth, const int *first, long long w) {
+    return first ? ids + first[w] : ids + (size_t)w * max_depth;
+}
+
+// Ids as avr_graph_add_walks_assigned takes them: every id at most the vertex count at its turn
+int merge_ids_valid(const avr_graph *g, long long n_walks, int max_depth, const int *counts, const int *ids,
+                    const int *first) {
+    long long nv = (long long)g->b.NumVertices();
+    for (long long w = 0; w < n_walks; ++w) {
+        const int *row = merge_row(ids, max_depth, first, w);
+        for (int j = 0; j < counts[w]; ++j) {
+            if (row[j] < 0 || row[j] > nv) return fail(AVR_ERR_ARG, "vertex id out of range at its turn");
+            nv += row[j] == nv;
+        }
+    }
+    return AVR_OK;
+}
+
+void merge_replay(avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                  const int *start_vertex, const int *ids, const int *first) {
+    for (long long w = 0; w < n_walks; ++w) {
+        const int k = counts[w], sv = start_vertex ? start_vertex[w] : -1;
+        const int cap = sv >= 0 ? max_depth - 1 : max_depth;
+        g->b.AddWalkAssigned(points + (size_t)w * max_depth * 3, merge_row(ids, max_depth, first, w), k, k == cap, sv);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int avr_graph_merge_assign(const avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                           const int *start_vertex, int *vertex_of_point, int *rounds) {
+    int rc = merge_arguments(g, n_walks, max_depth, points, counts, start_vertex, vertex_of_point);
+    if (rc) return rc;
+    avr::graph::MergeGrid mg;
+    rc = merge_grid(g, n_walks, max_depth, points, counts, start_vertex, &mg);
+    if (rc) return rc;
+    std::vector<int> state, ids((size_t)mg.NumPoints());
+    int r = 0;
+    if (!mg.Assign(&state, &r)) return fail(AVR_ERR_INTERNAL, "graph merge: a round finalised no point");
+    avr::graph::merge_ids(state.data(), mg.NumExisting(), mg.NumPoints(), ids.data());
+    merge_scatter(mg, n_walks, max_depth, ids.data(), vertex_of_point);
+    if (rounds) *rounds = r;
+    return AVR_OK;
+}
+
+int avr_graph_merge_assign_device(avr_context *c, const avr_graph *g, long long n_walks, int max_depth,
+                                  const float *points, const int *counts, const int *start_vertex, int *vertex_of_point,
+                                  int *rounds) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    int rc = merge_arguments(g, n_walks, max_depth, points, counts, start_vertex, vertex_of_point);
+    if (rc) return rc;
+    avr::graph::MergeGrid mg;
+    rc = merge_grid(g, n_walks, max_depth, points, counts, start_vertex, &mg);
+    if (rc) return rc;
+    std::vector<int> ids;
+    int r = 0, news = 0;
+    double msUp = 0;
+    rc = merge_assign_device(c, mg, &ids, &r, &news, &msUp);
+    if (rc) return rc;
+    merge_scatter(mg, n_walks, max_depth, ids.data(), vertex_of_point);
+    if (rounds) *rounds = r;
+    return AVR_OK;
+}
+
+int avr_graph_add_walks_assigned(avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                                 const int *start_vertex, const int *vertex_of_point) {
+    int rc = merge_arguments(g, n_walks, max_depth, points, counts, start_vertex, vertex_of_point);
+    if (rc) return rc;
+    rc = merge_ids_valid(g, n_walks, max_depth, counts, vertex_of_point, nullptr);
+    if (rc) return rc;
+    merge_replay(g, n_walks, max_depth, points, counts, start_vertex, vertex_of_point, nullptr);
+    return AVR_OK;
+}
+
+int avr_graph_add_walks_device(avr_context *c, avr_graph *g, long long n_walks, int max_depth, const float *points,
+                               const int *counts, const int *start_vertex, avr_graph_merge_stats *stats) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    if (stats) *stats = avr_graph_merge_stats{};
+    int dummy = 0;   // no vertex_of_point here: the replay takes the ids in seq order
+    int rc = merge_arguments(g, n_walks, max_depth, points, counts, start_vertex, &dummy);
+    if (rc) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    avr::graph::MergeGrid mg;
+    rc = merge_grid(g, n_walks, max_depth, points, counts, start_vertex, &mg);
+    if (rc) return rc;
+    const double msGrid = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    std::vector<int> ids;
+    int r = 0, news = 0;
+    double msUp = 0;
+    rc = merge_assign_device(c, mg, &ids, &r, &news, &msUp);
+    if (rc) return rc;
+    const double msDev = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    const int *first = mg.WalkFirst().data();
+    rc = merge_ids_valid(g, n_walks, max_depth, counts, ids.data(), first);
+    if (rc) return fail(AVR_ERR_INTERNAL, "graph merge: the device assignment is not a valid replay");
+    merge_replay(g, n_walks, max_depth, points, counts, start_vertex, ids.data(), first);
+    if (stats) {
+        stats->rounds = r;
+        stats->points = mg.NumPoints();
+        stats->new_vertices = news;
+        stats->ms_sort = msGrid + msUp;
+        stats->ms_rounds = msDev - msUp;
+        stats->ms_replay = ms_since(t0);
+    }
+    return AVR_OK;
+}
+
 int avr_graph_out_degrees(avr_graph *g, int *out) {
     if (!g || !out) return fail(AVR_ERR_ARG, "null buffer");
     g->b.OutDegrees(out);

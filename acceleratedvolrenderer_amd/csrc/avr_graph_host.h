@@ -2,7 +2,9 @@
 // FreeGraphBuilder, free/free_graph_builder.cpp:19-141 and 241-273, over Graph's
 // AddVertex / AddEdge / AddVertexToPath, graph.cpp:79-229). The walks themselves come from
 // the GPU (k_graph_walks); merging them into vertices depends on every earlier walk, so it
-// runs here in walk order, as the reference's single-threaded BuildGraph loop does.
+// runs here in walk order, as the reference's single-threaded BuildGraph loop does. The
+// radius search of that merge can also be done beforehand, for a whole batch in data-parallel
+// rounds (avr_graph_merge.h): AddWalkAssigned then replays a walk from its points' vertex ids.
 //
 // Radius search: a uniform hash grid with cells of the vertex radius (the 27 cells around a
 // point hold every vertex within the radius). GetClosestInRadius takes result[0] of
@@ -27,6 +29,7 @@ class Builder {
     // start >= 0: TracePath's startingVertex (free_graph_builder.cpp:24-25), the path's
     // first vertex before any scatter (the reinforcement walks)
     void AddWalk(const float *pts, int k, bool forced, int start = -1) {
+        SyncGrid();
         path_.clear();
         if (start >= 0) path_.push_back(start);
         for (int j = 0; j < k; ++j) {
@@ -45,6 +48,27 @@ class Builder {
         PathInfo(forced);
     }
 
+    // AddWalk with the radius search already done (avr_graph_merge.h): ids[j] is point j's
+    // vertex, in place of Closest and the previous-vertex fallback; ids[j] == NumVertices() at
+    // its turn creates the vertex. The caller has checked 0 <= ids[j] <= NumVertices() then.
+    // The new vertices enter the search grid when a search next needs it (SyncGrid).
+    void AddWalkAssigned(const float *pts, const int *ids, int k, bool forced, int start = -1) {
+        path_.clear();
+        if (start >= 0) path_.push_back(start);
+        for (int j = 0; j < k; ++j) {
+            const float p[3] = {pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]};
+            if (!path_.empty()) ++vsamples_[path_.back()];
+            int v = ids[j];
+            if (v == (int)NumVertices()) v = NewVertex(p, false);
+            path_.push_back(v);
+            if (path_.size() >= 2) AddEdge(path_[path_.size() - 2], v);
+        }
+        if (!forced && !path_.empty()) ++vsamples_[path_.back()];
+        PathInfo(forced);
+    }
+
+    float Radius() const { return r_; }
+
     // Vertex::outEdges.size(): distinct targets per vertex
     void OutDegrees(int *out) const {
         for (size_t v = 0; v < NumVertices(); ++v) out[v] = 0;
@@ -53,6 +77,7 @@ class Builder {
     // CountInRadius (free_graph_builder.cpp:229-236): vertices with squared distance strictly
     // below Sqr(radius) (nanoflann RadiusResultSet), the vertex itself included
     int CountInRadius(int v, float radius) const {
+        SyncGrid();
         const float r2 = radius * radius;
         const float *p = &vxyz_[3 * (size_t)v];
         const int reach = (int)std::ceil(radius / r_);
@@ -126,12 +151,22 @@ class Builder {
                 }
         return best;
     }
-    int NewVertex(const float *p) {
+    int NewVertex(const float *p, bool gridded = true) {
         const int id = (int)vsamples_.size();
         vxyz_.insert(vxyz_.end(), p, p + 3);
         vsamples_.push_back(0);
-        grid_[Key(Cell(p[0]), Cell(p[1]), Cell(p[2]))].push_back(id);
+        if (gridded) {   // AddWalk and CountInRadius have synced the grid before
+            grid_[Key(Cell(p[0]), Cell(p[1]), Cell(p[2]))].push_back(id);
+            gridded_ = vsamples_.size();
+        }
         return id;
+    }
+    // The vertices AddWalkAssigned created, into the search grid in id order
+    void SyncGrid() const {
+        for (; gridded_ < vsamples_.size(); ++gridded_) {
+            const float *p = &vxyz_[3 * gridded_];
+            grid_[Key(Cell(p[0]), Cell(p[1]), Cell(p[2]))].push_back((int)gridded_);
+        }
     }
     void AddEdge(int from, int to) {   // Graph::AddEdge with EdgeData{1}: merge adds samples
         const uint64_t key = ((uint64_t)(uint32_t)from << 32) | (uint32_t)to;
@@ -167,7 +202,8 @@ class Builder {
     std::vector<int> vsamples_;
     std::vector<int> efrom_, eto_, esamples_;
     std::unordered_map<uint64_t, int> edges_;
-    std::unordered_map<uint64_t, std::vector<int>> grid_;
+    mutable std::unordered_map<uint64_t, std::vector<int>> grid_;
+    mutable size_t gridded_ = 0;   // vertices [0, gridded_) are in grid_
     std::vector<int> path_;
     double plSum_ = 0;
     long long plCount_ = 0;

@@ -15,7 +15,9 @@ then solves light transport on it (cmd/graph_maker.cpp:70-160):
 Here the walks (k_graph_walks), the per-vertex transmittance estimates (k_graph_disk /
 k_graph_tr / k_graph_average) and the sparse bounce iteration (k_graph_spmv) run on the GPU
 through include/avr.h; the order-dependent vertex merge runs in C++ on the host
-(avr_graph_add_walks). Names, parameters and error behaviour follow the reference. All
+(avr_graph_add_walks) or, with FreeGraphBuilder(merge="device"), as data-parallel rounds on the
+GPU followed by a host replay (k_graph_merge_round, avr_graph_add_walks_device): the same
+graph. Names, parameters and error behaviour follow the reference. All
 geometry is in the scene's render space; the medium's boundary primitive is its bounds box
 or, with primitive="interface", the scene's interface sphere or mesh:
 MediumData(scene, primitive) carries the choice, and FreeGraphBuilder, LightingCalculator,
@@ -48,6 +50,7 @@ Not mirrored: the uniform-graph branch, --graph-debug.
 """
 import json
 import math
+import time
 
 import numpy as np
 
@@ -309,16 +312,28 @@ def load_index(path):
 
 
 class FreeGraphBuilder:
-    """FreeGraphBuilder (free/free_graph_builder.cpp): walks on the GPU, merge on the host."""
+    """FreeGraphBuilder (free/free_graph_builder.cpp): walks on the GPU, merge on the host or,
+    with merge="device", in rounds on the GPU (the same graph)."""
 
     def __init__(self, ctx, medium_data, in_direction, sampling, config, node_radius=None, sample_index_offset=0,
-                 search_ranges="scipy"):
+                 search_ranges="scipy", merge="host"):
         """search_ranges: how ComputeSearchRanges runs: "scipy" (compute_search_ranges, the
         float64 k-d tree), "host" or "device" (compute_search_ranges_host / _device: the
-        reference's float arithmetic over the vertex index; the two agree bitwise)."""
+        reference's float arithmetic over the vertex index; the two agree bitwise).
+        merge: how the walks' scatter points become vertices, in build_graph and in every
+        reinforcement cycle: "host" (avr_graph_add_walks, in walk order) or "device"
+        (avr_graph_add_walks_device: the assignment in rounds on the GPU, then the host replay;
+        the same graph). merge_stats holds the last device merge's avr_graph_merge_stats,
+        merge_seconds and merge_rounds the sums over this builder's merge calls."""
         if search_ranges not in ("scipy", "host", "device"):
             raise ValueError('search_ranges must be "scipy", "host" or "device"')
+        if merge not in ("host", "device"):
+            raise ValueError('merge must be "host" or "device"')
         self.search_ranges = search_ranges
+        self.merge = merge
+        self.merge_stats = None
+        self.merge_seconds = 0.0
+        self.merge_rounds = 0
         self.ctx = ctx
         self.md = medium_data
         self.in_dir = np.asarray(in_direction, f32)
@@ -394,7 +409,7 @@ class FreeGraphBuilder:
         pts, counts = self.ctx.graph_walks(self.sampling.struct(), o, d, t, idx, c.iterations_per_step,
                                            self.sample_index_offset, c.max_depth)
         g = capi.Graph(self.radius)
-        g.add_walks(pts, counts, c.max_depth)
+        self._add_walks(g, pts, counts, c.max_depth)
         self.reinforce_cycles = self.reinforce_sparse_vertices(g)
         graph = FreeGraph(g, self.radius)
         if search_ranges:
@@ -436,7 +451,19 @@ class FreeGraphBuilder:
                                            1, cycle, md - 1, skip_dims=2)
         padded = np.zeros((len(counts), md, 3), np.float32)   # avr_graph_add_walks_from: stride max_depth
         padded[:, :md - 1] = pts[:, :md - 1]
-        g.add_walks_from(padded, counts, md, np.repeat(ids, k)[sel])
+        self._add_walks(g, padded, counts, md, np.repeat(ids, k)[sel])
+
+    def _add_walks(self, g, pts, counts, max_depth, start_vertex=None):
+        """The walks into the graph, by the builder's merge form."""
+        t0 = time.perf_counter()
+        if self.merge == "device":
+            self.merge_stats = g.add_walks_device(self.ctx, pts, counts, max_depth, start_vertex)
+            self.merge_rounds += self.merge_stats["rounds"]
+        elif start_vertex is None:
+            g.add_walks(pts, counts, max_depth)
+        else:
+            g.add_walks_from(pts, counts, max_depth, start_vertex)
+        self.merge_seconds += time.perf_counter() - t0
 
     def reinforce_sparse_vertices(self, g):
         """FreeGraphBuilder::ReinforceSparseVertices (free_graph_builder.cpp:280-432): until the

@@ -28,6 +28,7 @@ extern "C" {
 #define AVR_ERR_ARG 1
 #define AVR_ERR_HIP 2
 #define AVR_ERR_STATE 3
+#define AVR_ERR_INTERNAL 4 /* an invariant of the library failed: a bug, reported and never looped on */
 
 #define AVR_TABLE_SIZE 471 /* DenselySampledSpectrum over 360..830 nm (spectrum.h:374-420) */
 
@@ -547,6 +548,41 @@ int avr_graph_add_walks(avr_graph *g, long long n_walks, int max_depth, const fl
  * max_depth - 1 scatters when a start vertex is given (max_depth counts path vertices). */
 int avr_graph_add_walks_from(avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
                              const int *start_vertex);
+/* The merge in data-parallel rounds (csrc/avr_graph_merge.h): which vertex every scatter
+ * point of a batch of walks belongs to, exactly as avr_graph_add_walks_from would decide it in
+ * walk order. Walks as there: points n_walks x max_depth x 3, counts, start_vertex per walk
+ * or NULL (none). vertex_of_point: n_walks x max_depth ids, -1 past a walk's count; an id
+ * equal to the number of vertices that exist at the point's turn (the graph's, plus the new
+ * ones before it in walk, then point order) means the point becomes that new vertex.
+ * avr_graph_merge_assign runs synchronous rounds on the host, avr_graph_merge_assign_device one
+ * kernel sweep per round over the points still open (states read while other lanes write
+ * them, so it needs at most the host's rounds); both leave the graph untouched, sort the
+ * call's entities on the host, and give the same ids. *rounds (may be NULL): rounds run.
+ * AVR_ERR_INTERNAL instead of looping if a round finalises no point (a bug: the open point of
+ * lowest sequence can always be finalised). AVR_ERR_ARG: counts or start vertices out of range
+ * as avr_graph_add_walks_from checks them, a non-finite coordinate, null buffers. Empty
+ * batches and walks of count 0 are valid.
+ * avr_graph_add_walks_assigned: avr_graph_add_walks_from with the radius search replaced by
+ * vertex_of_point (vertex samples, edges in first-seen order and the in-node path lengths
+ * follow in O(points)); AVR_ERR_ARG with the graph unchanged for a negative id or one above the
+ * vertex count at its turn. avr_graph_add_walks_device: avr_graph_merge_assign_device, then the
+ * replay; stats (may be NULL): wall-clock milliseconds of the host sort and upload, of the
+ * device rounds with the id scan and its download, and of the replay. */
+typedef struct avr_graph_merge_stats {
+    int rounds;
+    long long points;         /* scatter points in the call            */
+    long long new_vertices;   /* of them, points that became vertices  */
+    double ms_sort, ms_rounds, ms_replay;
+} avr_graph_merge_stats;
+int avr_graph_merge_assign(const avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                           const int *start_vertex, int *vertex_of_point, int *rounds);
+int avr_graph_merge_assign_device(avr_context *ctx, const avr_graph *g, long long n_walks, int max_depth,
+                                  const float *points, const int *counts, const int *start_vertex, int *vertex_of_point,
+                                  int *rounds);
+int avr_graph_add_walks_assigned(avr_graph *g, long long n_walks, int max_depth, const float *points, const int *counts,
+                                 const int *start_vertex, const int *vertex_of_point);
+int avr_graph_add_walks_device(avr_context *ctx, avr_graph *g, long long n_walks, int max_depth, const float *points,
+                               const int *counts, const int *start_vertex, avr_graph_merge_stats *stats);
 /* Vertex::outEdges.size() per vertex; CountInRadius (squared distance < radius^2, self included) */
 int avr_graph_out_degrees(avr_graph *g, int *out);
 int avr_graph_count_in_radius(avr_graph *g, int n, const int *vertex_ids, float radius, int *counts);

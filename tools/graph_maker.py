@@ -7,7 +7,7 @@ fork's `pbrt --graph` read. PREFIX_stats.json holds the graph's sizes and the se
 
 usage: python tools/graph_maker.py [--scene s-cloud] [--n 64] [--config CONFIG.json] --out PREFIX
                                    [--precision 9] [--search-ranges device] [--sampler 0] [--seed 0]
-                                   [--interface-sphere CX,CY,CZ,R]
+                                   [--interface-sphere CX,CY,CZ,R] [--merge host]
 
 --interface-sphere bounds the medium by a sphere (world space): the scene gets it as its
 interface and the graph is made with the sphere as the primitive (primitive="interface").
@@ -69,6 +69,8 @@ def parser():
     p.add_argument("--out", required=True, help="output prefix: PREFIX_d{depth}.txt, PREFIX_stats.json")
     p.add_argument("--precision", type=int, default=9, help="significant digits of the floats written")
     p.add_argument("--search-ranges", choices=("device", "host", "scipy"), default="device")
+    p.add_argument("--merge", choices=("host", "device"), default="host",
+                   help="the vertex merge: in walk order on the host, or in rounds on the device (the same graph)")
     p.add_argument("--sampler", type=int, choices=(0, 1), default=0, help="0 independent, 1 zsobol")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--interface-sphere", type=interface_sphere, metavar="CX,CY,CZ,R",
@@ -101,9 +103,11 @@ def main(argv=None):
     active = bool(cfg.graph_builder.render_search_range.get("active"))
     k = int(cfg.graph_builder.render_search_range.get("neighboursToUse", 0))
     t0 = time.perf_counter()
-    builder = graph.FreeGraphBuilder(ctx, md, in_dir, smp, cfg.graph_builder, search_ranges=a.search_ranges)
+    builder = graph.FreeGraphBuilder(ctx, md, in_dir, smp, cfg.graph_builder, search_ranges=a.search_ranges,
+                                     merge=a.merge)
     g = builder.build_graph(search_ranges=False)
     seconds["build_graph"] = time.perf_counter() - t0
+    seconds["merge"] = builder.merge_seconds   # within build_graph: the walks into vertices, every cycle
     t0 = time.perf_counter()
     builder.compute_search_ranges(g)
     seconds["search_ranges"] = time.perf_counter() - t0
@@ -146,6 +150,7 @@ def main(argv=None):
                                 "neighbours": k if active else 0, "computed_on": a.search_ranges if active else None},
         "sizes": {"node_radius": float(g.radius), "scene_radius": float(md.max_dist_to_center)},
         "reinforce_cycles": int(builder.reinforce_cycles),
+        "merge": {"on": a.merge, "rounds": int(builder.merge_rounds) if a.merge == "device" else None},
         "files": files,
         "seconds": seconds,
     }
