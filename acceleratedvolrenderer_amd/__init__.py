@@ -17,11 +17,11 @@ from . import capi
 from . import scenes
 from . import graph
 from . import graph_io
-from .capi import GraphIndex
+from .capi import GraphIndex, GraphUniform
 from .graph import GraphIntegrator, IntegrationAnalyzer
 
 __all__ = ["spectra", "transform", "GridMedium", "DistantLight", "UniformInfiniteLight", "OrthographicCamera",
            "PerspectiveCamera", "RGBFilm", "Scene", "film_rgb", "VolPathIntegrator", "shard_samples",
            "INTEGRATOR_NAMES", "capi", "scenes", "HomogeneousMedium", "CloudMedium", "NanoVDBMedium", "NanoVDBGrid", "RGBGridMedium", "RGBToSpectrumTable",
            "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler",
-           "graph", "graph_io", "GraphIndex", "GraphIntegrator", "IntegrationAnalyzer"]
+           "graph", "graph_io", "GraphIndex", "GraphUniform", "GraphIntegrator", "IntegrationAnalyzer"]

@@ -17,6 +17,8 @@ c_float_p = ctypes.POINTER(ctypes.c_float)
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int_p = ctypes.POINTER(ctypes.c_int)
 c_u64_p = ctypes.POINTER(ctypes.c_ulonglong)
+# pbrt's Inv4Pi as a float: the uniform graph render's default light_scale
+INV_4PI = float(np.float32(0.07957747154594766788))
 
 
 class AvrStats(ctypes.Structure):
@@ -248,6 +250,22 @@ SIGNATURES = {
                                         ctypes.c_int]),
     "avr_graph_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int_p,
                                            ctypes.c_longlong]),
+    "avr_graph_uniform_create": (ctypes.c_int, [ctypes.c_longlong, c_int_p, c_float_p, ctypes.c_float,
+                                                ctypes.POINTER(ctypes.c_void_p)]),
+    "avr_graph_uniform_from_points": (ctypes.c_int, [ctypes.c_longlong, c_float_p, c_float_p, ctypes.c_float,
+                                                     ctypes.c_int, c_int_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "avr_graph_uniform_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "avr_graph_uniform_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), c_float_p]),
+    "avr_graph_uniform_get": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_float_p]),
+    "avr_graph_uniform_lookup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_int_p, c_float_p]),
+    "avr_graph_uniform_trace": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p, c_int_p,
+                                               c_float_p, c_float_p]),
+    "avr_graph_uniform_lookup_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p,
+                                                       c_int_p, c_float_p]),
+    "avr_graph_uniform_trace_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p,
+                                                      c_float_p, c_int_p, c_float_p, c_float_p]),
+    "avr_graph_render_uniform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_float]),
     "avr_graph_index_coverage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_int_p, c_int_p,
                                                 c_float_p]),
     "avr_graph_coverage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_int_p,
@@ -701,6 +719,38 @@ class Context:
         m = None if graph_from_render is None else np.ascontiguousarray(graph_from_render, np.float32).reshape(16)
         _check(self.lib.avr_graph_render(self.h, index.h, _fp(m), int(spp_begin), int(spp_end), int(seed)))
 
+    def graph_uniform_lookup(self, uniform, points):
+        """GraphUniform.lookup on the device for (n, 3) graph-space points: (ids, light), bitwise
+        the host's."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ids = np.zeros(len(p), np.int32)
+        light = np.zeros(len(p), np.float32)
+        _check(self.lib.avr_graph_uniform_lookup_device(self.h, uniform.h, len(p), _fp(p), ids.ctypes.data_as(c_int_p),
+                                                        _fp(light)))
+        return ids, light
+
+    def graph_uniform_trace(self, uniform, o, d):
+        """GraphUniform.trace on the device for (n, 3) graph-space rays: (ids, hit0, hit1), bitwise
+        the host's."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("graph_uniform_trace: one direction per origin")
+        ids = np.zeros(len(o), np.int32)
+        hit0, hit1 = np.zeros(len(o), np.float32), np.zeros(len(o), np.float32)
+        _check(self.lib.avr_graph_uniform_trace_device(self.h, uniform.h, len(o), _fp(o), _fp(d),
+                                                       ids.ctypes.data_as(c_int_p), _fp(hit0), _fp(hit1)))
+        return ids, hit0, hit1
+
+    def graph_render_uniform(self, uniform, spp_begin, spp_end, seed, graph_from_render=None, view=0,
+                             light_scale=INV_4PI):
+        """GraphIntegrator::Li (uniform graph) for sample indices [spp_begin, spp_end) into the
+        film; view 1 is --graph-debug's voxel view. light_scale: the reference's Inv4Pi by
+        default; a graph lit by LightingCalculator already carries it and takes 1."""
+        m = None if graph_from_render is None else np.ascontiguousarray(graph_from_render, np.float32).reshape(16)
+        _check(self.lib.avr_graph_render_uniform(self.h, uniform.h, _fp(m), int(spp_begin), int(spp_end), int(seed),
+                                                 int(view), float(light_scale)))
+
     def graph_last_pass(self, npix, max_samples):
         """The last graph pass per sample (indexed as last_pass_samples): camera ray o, d, the
         scatter point in render space ((n, 3) each) and the vertices averaged (-1: no scatter)."""
@@ -981,6 +1031,101 @@ class GraphIndex:
     def close(self):
         if self.h:
             self.lib.avr_graph_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GraphUniform:
+    """The uniform (voxel) lighting graph (avr_graph_uniform_*): vertices on the integer lattice
+    of `spacing`, one lightScalar each, behind one hash table. GraphUniform(coors, light_scalar,
+    spacing) takes (m, 3) integer coordinates; GraphUniform.from_points converts free-graph
+    vertices. Host code; Context.graph_render_uniform, graph_uniform_lookup and
+    graph_uniform_trace upload the table to the device on first use."""
+
+    def __init__(self, coors, light_scalar, spacing):
+        self.lib = load()
+        self.h = None
+        c = np.asarray(coors)
+        if c.dtype.kind not in "iu":
+            raise ValueError("GraphUniform: integer lattice coordinates (GraphUniform.from_points takes points)")
+        c64 = c.reshape(-1, 3).astype(np.int64)
+        c = np.ascontiguousarray(np.clip(c64, -2 ** 31, 2 ** 31 - 1), np.int32)   # out of range either way
+        light = np.ascontiguousarray(light_scalar, np.float32).reshape(-1)
+        if len(light) != len(c):
+            raise ValueError("GraphUniform: one light scalar per vertex")
+        h = ctypes.c_void_p()
+        _check(self.lib.avr_graph_uniform_create(len(c), c.ctypes.data_as(c_int_p), _fp(light), float(spacing),
+                                                 ctypes.byref(h)))
+        self._adopt(h)
+
+    def _adopt(self, h):
+        self.h = h
+        n, s = ctypes.c_longlong(), ctypes.c_float()
+        _check(self.lib.avr_graph_uniform_size(h, ctypes.byref(n), ctypes.byref(s)))
+        self.num_vertices = n.value
+        self.spacing = np.float32(s.value)
+        self.coors = np.zeros((n.value, 3), np.int32)
+        self.light_scalar = np.zeros(n.value, np.float32)
+        _check(self.lib.avr_graph_uniform_get(h, self.coors.ctypes.data_as(c_int_p), _fp(self.light_scalar)))
+
+    @classmethod
+    def from_points(cls, points, light_scalar, spacing, reduce="first"):
+        """FreeGraph::ToUniform's vertices: the points in ascending id, one new vertex per voxel
+        at its first appearance; reduce "first" keeps that point's light, "mean" the float mean
+        of the voxel's lights. The old -> new id map is left in .vertex_of."""
+        if reduce not in ("first", "mean"):
+            raise ValueError('GraphUniform.from_points: reduce is "first" or "mean"')
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        light = np.ascontiguousarray(light_scalar, np.float32).reshape(-1)
+        if len(light) != len(p):
+            raise ValueError("GraphUniform: one light scalar per vertex")
+        self = cls.__new__(cls)
+        self.lib = load()
+        self.h = None
+        vertex_of = np.zeros(len(p), np.int32)
+        h = ctypes.c_void_p()
+        _check(self.lib.avr_graph_uniform_from_points(len(p), _fp(p), _fp(light), float(spacing),
+                                                      1 if reduce == "mean" else 0, vertex_of.ctypes.data_as(c_int_p),
+                                                      ctypes.byref(h)))
+        self._adopt(h)
+        self.vertex_of = vertex_of
+        return self
+
+    @property
+    def points(self):
+        """The vertices' points, (float)coors * spacing (graph.cpp:555)."""
+        return (self.coors.astype(np.float32) * self.spacing).astype(np.float32)
+
+    def lookup(self, points):
+        """UniformGraph::GetVertexConst on the host for (n, 3) graph-space points: (ids, light);
+        id -1 and light 0 without a vertex."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ids = np.zeros(len(p), np.int32)
+        light = np.zeros(len(p), np.float32)
+        _check(self.lib.avr_graph_uniform_lookup(self.h, len(p), _fp(p), ids.ctypes.data_as(c_int_p), _fp(light)))
+        return ids, light
+
+    def trace(self, o, d):
+        """The lit voxel each graph-space ray enters first, on the host: (ids, hit0, hit1) of
+        IntersectP for its box; id -1 without one."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("GraphUniform.trace: one direction per origin")
+        ids = np.zeros(len(o), np.int32)
+        hit0, hit1 = np.zeros(len(o), np.float32), np.zeros(len(o), np.float32)
+        _check(self.lib.avr_graph_uniform_trace(self.h, len(o), _fp(o), _fp(d), ids.ctypes.data_as(c_int_p), _fp(hit0),
+                                                _fp(hit1)))
+        return ids, hit0, hit1
+
+    def close(self):
+        if self.h:
+            self.lib.avr_graph_uniform_destroy(self.h)
             self.h = None
 
     def __del__(self):

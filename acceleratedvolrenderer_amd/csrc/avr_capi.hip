@@ -219,7 +219,12 @@ struct avr_context {
     avr::graph::IndexView gidx{};
     float4 *d_gside = nullptr;
     long long gside_cap = 0;
-    bool last_graph = false;        // the last render was avr_graph_render's
+    bool last_graph = false;        // the last render was avr_graph_render's or avr_graph_render_uniform's
+    // the uniform graph's table (avr_graph_render_uniform, avr_graph_uniform_*_device): the device
+    // copy of the last one used, under the graph's id as gidx is
+    unsigned long long guni_uid = 0;
+    avr::graph::UniformEntry *d_guni = nullptr;
+    avr::graph::UniformView guni{};
     // the graph tools' primitive (avr_graph_set_geometry): 0 the bounds box, 1 the interface
     int graph_geometry = 0;
     // graph analysis (avr_graph_analyze): the pass's per-sample records, the per-pixel sums
@@ -893,6 +898,7 @@ int avr_context_destroy(avr_context *c) {
     if (c->d_brick) (void)hipFree(c->d_brick);
     if (c->d_gidx) (void)hipFree(c->d_gidx);
     if (c->d_gside) (void)hipFree(c->d_gside);
+    if (c->d_guni) (void)hipFree(c->d_guni);
     if (c->d_arec) (void)hipFree(c->d_arec);
     if (c->d_aacc) (void)hipFree(c->d_aacc);
     if (c->d_adetail) (void)hipFree(c->d_adetail);

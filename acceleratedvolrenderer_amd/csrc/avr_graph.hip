@@ -24,6 +24,11 @@
 //  k_graph_render  GraphIntegrator::Li, free-graph branch (graph_integrator.cpp:180-247): one
 //                  lane per camera record of the pass; delta tracking to the first real
 //                  scatter, then the same index_connect.
+//  k_graph_render_uniform  GraphIntegrator::Li, uniform-graph branch (:89-178): the same walk to
+//  k_graph_uniform_lookup  the first real scatter (graph_first_scatter), then one hashed lookup
+//  k_graph_uniform_trace   of the point's voxel (avr_graph_uniform.h); --graph-debug's voxel
+//                  view (:104-131) as its kView 1; the lookup and the first-lit-voxel search
+//                  for batches of points and rays.
 //  k_graph_coverage  IntegrationAnalyzer's Analyze (analysis/integration_analyzer.cpp:56-83)
 //                  for a batch of graph-space points: index_coverage, one lane per point.
 //  k_graph_analyze IntegrationAnalyzer::AnalyzeRay (:55-163): one lane per camera record walks
@@ -44,6 +49,7 @@
 // parameter: the kGeom 0 instantiations are the box-only kernels' code.
 #include "avr_graph_index.h"
 #include "avr_graph_merge.h"
+#include "avr_graph_uniform.h"
 
 namespace avr {
 namespace graph {
@@ -483,6 +489,145 @@ __global__ void __launch_bounds__(256) k_graph_range_average(int n, int k, const
         range[v] = graph::index_range_average(avg, (int)v, ids + (size_t)v * (size_t)k, k);
 }
 
+// Where a camera record's ray starts in the graph geometry's primitive (primitive_hits): a ray
+// from outside at its entry point with tMax = t1 - t0, a camera inside at its origin with the
+// exit as tMax; false on a miss.
+template <int kGeom>
+__device__ __forceinline__ bool graph_camera_start(const DevMedium &m, V3 o, V3 d, V3 *ro, float *tMax) {
+    const graph::Hits h = graph::primitive_hits<kGeom>(m, o, d);
+    if (h.type == graph::kOutsideZeroHits) return false;
+    *ro = o;
+    *tMax = h.t0;
+    if (h.type == graph::kOutsideTwoHits) {
+        *ro = o + d * h.t0;
+        *tMax = h.t1 - h.t0;
+    }
+    return true;
+}
+
+// GraphIntegrator::Li up to the first real scatter, the same for the free and the uniform
+// graph (graph_integrator.cpp:134-170, :205-243): graph_camera_start (a miss draws nothing),
+// hash0 and hash1 seed the RNG, SampleT_maj with the next Get1D, the medium's coefficients at
+// the sample's own wavelengths and the 3-way event choice on channel 0. The scatter point goes
+// to pS, and onScatter(li) runs after a real scatter, with the wavelengths' table offsets;
+// absorption or leaving the primitive leave pS alone and call nothing.
+template <int kGeom, typename Sampler, typename F>
+__device__ __forceinline__ void graph_first_scatter(const Params &P, const float *maj, Sampler &smp, V3 o, V3 d,
+                                                    const Spec &lam, V3 &pS, unsigned long long &nLookup,
+                                                    unsigned long long &nSteps, F onScatter) {
+    V3 ro;
+    float tMax;
+    if (graph_camera_start<kGeom>(P.med, o, d, &ro, &tMax)) {
+        const LambdaIdx li = lambda_index(lam);
+        const Spec sig_a = sample_table(P.med.sigma_a, li), sig_s = sample_table(P.med.sigma_s, li);
+        const float h0 = smp.get1d(P);
+        const float h1 = smp.get1d(P);
+        Pcg32 rng;
+        rng.set_sequence(hash_u32(f2u(h0)), hash_u32(f2u(h1)));
+        const float u = smp.get1d(P);
+        bool scattered = false;
+        auto cb = [&](V3 p, const MediumSample &ms, const Spec &sigma_maj, const Spec &) -> bool {
+            const float pAbsorb = ms.sigma_a.v0 / sigma_maj.v0;
+            const float pScat = ms.sigma_s.v0 / sigma_maj.v0;
+            const float pNull = fmaxf_(0.f, 1 - pAbsorb - pScat);
+            const int mode = sample_discrete3(pAbsorb, pScat, pNull, rng.uniform());
+            if (mode == 0) return false;
+            if (mode == 1) {
+                scattered = true;
+                pS = p;
+                return false;
+            }
+            return true;
+        };
+        sample_t_maj(P.med, maj, Ray{ro, d}, tMax, u, rng, sig_a, sig_s, Spec::c(0.f), lam, nLookup, nSteps, cb);
+        if (scattered) onScatter(li);
+    }
+}
+
+// UniformGraph::GetVertexConst for n points already in graph space (avr_graph_uniform_lookup_device)
+__global__ void __launch_bounds__(256) k_graph_uniform_lookup(graph::UniformView uv, long long n,
+                                                              const float *__restrict__ pts, int *__restrict__ id,
+                                                              float *__restrict__ light) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float l = 0.f;
+        id[i] = graph::uniform_lookup(uv, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], &l);
+        light[i] = l;
+    }
+}
+
+// The first lit voxel of n graph-space rays (avr_graph_uniform_trace_device)
+__global__ void __launch_bounds__(256) k_graph_uniform_trace(graph::UniformView uv, long long n, const float *__restrict__ o,
+                                                             const float *__restrict__ d, int *__restrict__ id,
+                                                             float *__restrict__ hit0, float *__restrict__ hit1) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float ro[3] = {o[3 * i], o[3 * i + 1], o[3 * i + 2]}, rd[3] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+        float h0 = 0.f, h1 = 0.f;
+        id[i] = graph::uniform_first_lit(uv, ro, rd, &h0, &h1);
+        hit0[i] = h0;
+        hit1[i] = h1;
+    }
+}
+
+// GraphIntegrator::Li, uniform graph (graph_integrator.cpp:89-178), after k_camera, one lane
+// per camera record. kView 0, the render: graph_first_scatter as k_graph_render, then the
+// vertex of the scatter point's voxel, L = (lightSpectrum.Sample(lambda) * lightScalar) *
+// lightFactor (the reference's Inv4Pi) or 0 without a vertex; side[id] = {p (render space),
+// count}: 1 vertex found, 0 scattered without one, -1 no scatter. kView 1, --graph-debug
+// (:104-131): no draw and no tracking; the ray from graph_camera_start, mapped to graph space,
+// finds its first lit voxel (uniform_first_lit), middle = o' + d' * ((hit0 + hit1) / 2), L =
+// lightSpectrum.Sample(lambda) * lightScalar of the vertex at middle; side[id] = {middle
+// (graph space), count}: 1 / 0 a lit voxel was hit and middle has / has no vertex, -1 else.
+template <bool kZSobol, int kGeom, int kView>
+__global__ void __launch_bounds__(256) k_graph_render_uniform(Params P, graph::UniformView uv, Xf graphFromRender,
+                                                              float lightFactor, float4 *__restrict__ side) {
+    [[maybe_unused]] const float *maj = nullptr;
+    if constexpr (kView == 0) {   // the voxel view tracks nothing: no majorant staging
+        __shared__ float s_maj[4096];
+        maj = stage_majorant(P.med, s_maj);
+    }
+    const float *lightL = P.lights.list[0].L;   // DistantLight::GetLEmit: scale * Lemit (lights.h:293-297)
+    const float lightScale = P.lights.list[0].scale;
+    unsigned long long nLookup = 0, nSteps = 0, nIn = 0;
+    const int n = P.pass_pixels * P.pass_samples;
+    for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
+        ++nIn;
+        const V3 o = from4(P.ps.o[id]), d = from4(P.ps.d[id]);
+        const Spec lam = spec4(P.ps.lambda[id]);
+        Spec L = Spec::c(0.f);
+        int count = -1;
+        V3 pS = {0.f, 0.f, 0.f};
+        if constexpr (kView == 0) {
+            PathSampler<kZSobol> smp;
+            smp.load(P, id);
+            graph_first_scatter<kGeom>(P, maj, smp, o, d, lam, pS, nLookup, nSteps, [&](const LambdaIdx &li) {
+                const V3 q = xf_point_lr(graphFromRender, pS);
+                float light = 0.f;
+                count = graph::uniform_lookup(uv, q.x, q.y, q.z, &light) >= 0 ? 1 : 0;
+                if (count) L = ((sample_table(lightL, li) * lightScale) * light) * lightFactor;
+            });
+        } else {
+            V3 ro;
+            float tMax;
+            if (graph_camera_start<kGeom>(P.med, o, d, &ro, &tMax)) {
+                const V3 og = xf_point_lr(graphFromRender, ro), dg = xf_vector(graphFromRender, d);
+                const float oa[3] = {og.x, og.y, og.z}, da[3] = {dg.x, dg.y, dg.z};
+                float hit0, hit1;
+                if (graph::uniform_first_lit(uv, oa, da, &hit0, &hit1) >= 0) {
+                    pS = og + dg * ((hit0 + hit1) / 2);
+                    float light = 0.f;
+                    count = graph::uniform_lookup(uv, pS.x, pS.y, pS.z, &light) >= 0 ? 1 : 0;
+                    if (count) L = (sample_table(lightL, lambda_index(lam)) * lightScale) * light;
+                }
+            }
+        }
+        P.ps.L[id] = to4(L);
+        side[id] = make_float4(pS.x, pS.y, pS.z, __int_as_float(count));
+    }
+    flush_stat(P.stats, 3, nLookup);
+    flush_stat(P.stats, 4, nIn);
+    flush_stat(P.stats, 6, nSteps);
+}
+
 // GraphIntegrator::Li, free graph (graph_integrator.cpp:180-247), after k_camera: the camera
 // record's ray crosses the primitive of the graph tools' geometry model (primitive_hits;
 // a ray from outside starts at its entry point, as FreeGraphBuilder's rays do; a camera
@@ -513,43 +658,12 @@ __global__ void __launch_bounds__(256) k_graph_render(Params P, graph::IndexView
         Spec L = Spec::c(0.f);
         int count = -1;
         V3 pS = {0.f, 0.f, 0.f};
-        const graph::Hits h = graph::primitive_hits<kGeom>(P.med, o, d);
-        if (h.type != graph::kOutsideZeroHits) {
-            V3 ro = o;
-            float tMax = h.t0;
-            if (h.type == graph::kOutsideTwoHits) {
-                ro = o + d * h.t0;
-                tMax = h.t1 - h.t0;
-            }
-            const LambdaIdx li = lambda_index(lam);
-            const Spec sig_a = sample_table(P.med.sigma_a, li), sig_s = sample_table(P.med.sigma_s, li);
-            const float h0 = smp.get1d(P);
-            const float h1 = smp.get1d(P);
-            Pcg32 rng;
-            rng.set_sequence(hash_u32(f2u(h0)), hash_u32(f2u(h1)));
-            const float u = smp.get1d(P);
-            bool scattered = false;
-            auto cb = [&](V3 p, const MediumSample &ms, const Spec &sigma_maj, const Spec &) -> bool {
-                const float pAbsorb = ms.sigma_a.v0 / sigma_maj.v0;
-                const float pScat = ms.sigma_s.v0 / sigma_maj.v0;
-                const float pNull = fmaxf_(0.f, 1 - pAbsorb - pScat);
-                const int mode = sample_discrete3(pAbsorb, pScat, pNull, rng.uniform());
-                if (mode == 0) return false;
-                if (mode == 1) {
-                    scattered = true;
-                    pS = p;
-                    return false;
-                }
-                return true;
-            };
-            sample_t_maj(P.med, maj, Ray{ro, d}, tMax, u, rng, sig_a, sig_s, Spec::c(0.f), lam, nLookup, nSteps, cb);
-            if (scattered) {
-                const V3 q = xf_point_lr(graphFromRender, pS);
-                int stage = 0;
-                const float conn = graph::index_connect(ix, q.x, q.y, q.z, buf, &count, &stage);
-                L = (sample_table(lightL, li) * lightScale) * conn;
-            }
-        }
+        graph_first_scatter<kGeom>(P, maj, smp, o, d, lam, pS, nLookup, nSteps, [&](const LambdaIdx &li) {
+            const V3 q = xf_point_lr(graphFromRender, pS);
+            int stage = 0;
+            const float conn = graph::index_connect(ix, q.x, q.y, q.z, buf, &count, &stage);
+            L = (sample_table(lightL, li) * lightScale) * conn;
+        });
         P.ps.L[id] = to4(L);
         side[id] = make_float4(pS.x, pS.y, pS.z, __int_as_float(count));
     }

@@ -53,6 +53,17 @@ bool graph_interface(const avr_context *c) { return c->graph_geometry == 1 && c-
             else hipLaunchKernelGGL((kernel<false, 0>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);       \
         }                                                                                                          \
     } while (0)
+// kernel<zsobol, geometry, view> with a constant view
+#define AVR_GRAPH_LAUNCH_ZGV(kernel, zs, geom, view, blocks, ...)                                                      \
+    do {                                                                                                                \
+        if (zs) {                                                                                                       \
+            if (geom) hipLaunchKernelGGL((kernel<true, 1, view>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);  \
+            else hipLaunchKernelGGL((kernel<true, 0, view>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);       \
+        } else {                                                                                                        \
+            if (geom) hipLaunchKernelGGL((kernel<false, 1, view>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__); \
+            else hipLaunchKernelGGL((kernel<false, 0, view>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);      \
+        }                                                                                                               \
+    } while (0)
 #define AVR_GRAPH_LAUNCH_G(kernel, geom, blocks, ...)                                                     \
     do {                                                                                                   \
         if (geom) hipLaunchKernelGGL((kernel<1>), dim3(blocks), dim3(256), 0, c->stream, __VA_ARGS__);     \
@@ -103,6 +114,40 @@ int ensure_graph_index(avr_context *c, const avr_graph_index *idx) {
     c->gidx.cell_start = (const int *)(d + szRec + szId);
     c->gidx.range2 = h.range2 ? (const float *)(d + szRec + szId + szStart) : nullptr;
     c->gidx_uid = idx->uid;
+    return AVR_OK;
+}
+
+}  // namespace
+
+// The host uniform graph (avr_graph_uniform.h) and the id its device copy is cached under
+struct avr_graph_uniform {
+    avr::graph::Uniform u;
+    unsigned long long uid = 0;
+};
+
+namespace {
+
+// The context's device copy of `u`'s table (c->guni), uploaded on first use and replaced when
+// another uniform graph is used; the ids come from the counter the vertex indices use
+int ensure_graph_uniform(avr_context *c, const avr_graph_uniform *u) {
+    if (c->guni_uid == u->uid) return AVR_OK;
+    // queued kernels may still read the previous copy
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_guni) (void)hipFree(c->d_guni);
+    c->d_guni = nullptr;
+    c->guni_uid = 0;
+    const avr::graph::UniformView h = u->u.View();
+    const size_t cap = u->u.Capacity();
+    HIP_TRY(dalloc(&c->d_guni, cap));
+    const hipError_t e = hipMemcpy(c->d_guni, h.tab, cap * sizeof(avr::graph::UniformEntry), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(c->d_guni);
+        c->d_guni = nullptr;
+        return fail(AVR_ERR_HIP, std::string("graph uniform upload: ") + hipGetErrorString(e));
+    }
+    c->guni = h;
+    c->guni.tab = c->d_guni;
+    c->guni_uid = u->uid;
     return AVR_OK;
 }
 
@@ -900,10 +945,12 @@ namespace {
 constexpr size_t kPathStateBytes = 252;
 
 // The pass loop of avr_render's wavefront organisation for the graph integrators: k_camera,
-// then k_graph_render and k_film (analyze_depth < 0), or k_graph_analyze and
-// k_graph_analyze_reduce with the film left alone; passes of at most max_paths samples.
+// then k_graph_render (or, with a uniform graph `uni`, k_graph_render_uniform<view>) and k_film
+// (analyze_depth < 0), or k_graph_analyze and k_graph_analyze_reduce with the film left alone;
+// passes of at most max_paths samples.
 int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
-                 int spp_end, int seed, int analyze_depth, int detail) {
+                 int spp_end, int seed, int analyze_depth, int detail, const avr_graph_uniform *uni = nullptr, int view = 0,
+                 float light_scale = 1.f) {
     const bool analyze = analyze_depth >= 0;
     static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     const float *gfr = graph_from_render ? graph_from_render : kIdentity;
@@ -913,7 +960,7 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
     avr::smp::ZSobolParams zs{};
     int rc = render_sampler(c, spp_end, seed, &zs);
     if (rc) return rc;
-    rc = ensure_graph_index(c, idx);
+    rc = uni ? ensure_graph_uniform(c, uni) : ensure_graph_index(c, idx);
     if (rc) return rc;
     const long long P = (long long)c->film.width * c->film.height;
     if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
@@ -1002,6 +1049,11 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
             avr::graph::AnalyzeDetail *det = detail ? c->d_adetail : nullptr;
             AVR_GRAPH_LAUNCH_ZG(avr::k_graph_analyze, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
                                 analyze_depth, c->d_arec, det);
+        } else if (uni) {
+            if (view) AVR_GRAPH_LAUNCH_ZGV(avr::k_graph_render_uniform, c->sampler_kind != 0, graph_interface(c), 1, nb, p,
+                                           c->guni, xf, light_scale, c->d_gside);
+            else AVR_GRAPH_LAUNCH_ZGV(avr::k_graph_render_uniform, c->sampler_kind != 0, graph_interface(c), 0, nb, p,
+                                      c->guni, xf, light_scale, c->d_gside);
         } else {
             AVR_GRAPH_LAUNCH_ZG(avr::k_graph_render, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
                                 c->d_gside);
@@ -1026,13 +1078,8 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
     return AVR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
-                     int spp_end, int seed) {
-    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
+// What the graph renders require of the context (avr_graph_render, avr_graph_render_uniform)
+int graph_render_state(avr_context *c, int spp_begin, int spp_end) {
     if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
     if (spp_begin < 0 || spp_end < spp_begin) return fail(AVR_ERR_ARG, "bad sample range");
     // GraphIntegrator::Create takes the scene's one DistantLight (lightSpectrum, lightDir)
@@ -1040,7 +1087,29 @@ int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float gra
         return fail(AVR_ERR_STATE, "graph render: exactly one distant light required");
     if (c->med.boundary != 0 && c->graph_geometry == 0)
         return fail(AVR_ERR_STATE, "graph render: the graph's geometry model is the medium's bounds box (no interface sphere or convex; avr_graph_set_geometry(ctx, 1) takes the interface as the primitive)");
+    return AVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int avr_graph_render(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
+                     int spp_end, int seed) {
+    if (!c || !idx) return fail(AVR_ERR_ARG, "null context or graph index");
+    int rc = graph_render_state(c, spp_begin, spp_end);
+    if (rc) return rc;
     return graph_passes(c, idx, graph_from_render, spp_begin, spp_end, seed, -1, 0);
+}
+
+int avr_graph_render_uniform(avr_context *c, const avr_graph_uniform *u, const float graph_from_render[16], int spp_begin,
+                             int spp_end, int seed, int view, float light_scale) {
+    if (!c || !u) return fail(AVR_ERR_ARG, "null context or uniform graph");
+    if (view != 0 && view != 1) return fail(AVR_ERR_ARG, "graph render: view must be 0 (render) or 1 (voxel view)");
+    if (!std::isfinite(light_scale)) return fail(AVR_ERR_ARG, "graph render: light_scale must be finite");
+    int rc = graph_render_state(c, spp_begin, spp_end);
+    if (rc) return rc;
+    return graph_passes(c, nullptr, graph_from_render, spp_begin, spp_end, seed, -1, 0, u, view, light_scale);
 }
 
 int avr_graph_analyze(avr_context *c, const avr_graph_index *idx, const float graph_from_render[16], int spp_begin,
@@ -1151,6 +1220,123 @@ int avr_graph_last_pass(avr_context *c, float *o, float *d, float *points, int *
             if (k == 2 && counts) std::memcpy(&counts[i], &h[(size_t)i].w, sizeof(int));
         }
     }
+    return AVR_OK;
+}
+
+int avr_graph_uniform_create(long long m, const int *coors, const float *light, float spacing, avr_graph_uniform **out) {
+    if (!out) return fail(AVR_ERR_ARG, "null out");
+    *out = nullptr;
+    auto *u = new avr_graph_uniform();
+    const std::string msg = u->u.Create(m, coors, light, spacing);
+    if (!msg.empty()) {
+        delete u;
+        return fail(AVR_ERR_ARG, msg);
+    }
+    u->uid = ++g_index_uid;
+    *out = u;
+    return AVR_OK;
+}
+int avr_graph_uniform_from_points(long long n, const float *xyz, const float *light, float spacing, int reduce,
+                                  int *vertex_of, avr_graph_uniform **out) {
+    if (!out) return fail(AVR_ERR_ARG, "null out");
+    *out = nullptr;
+    auto *u = new avr_graph_uniform();
+    const std::string msg = u->u.FromPoints(n, xyz, light, spacing, reduce, vertex_of);
+    if (!msg.empty()) {
+        delete u;
+        return fail(AVR_ERR_ARG, msg);
+    }
+    u->uid = ++g_index_uid;
+    *out = u;
+    return AVR_OK;
+}
+int avr_graph_uniform_destroy(avr_graph_uniform *u) {
+    delete u;
+    return AVR_OK;
+}
+int avr_graph_uniform_size(const avr_graph_uniform *u, long long *n_vertices, float *spacing) {
+    if (!u) return fail(AVR_ERR_ARG, "null uniform graph");
+    if (n_vertices) *n_vertices = (long long)u->u.NumVertices();
+    if (spacing) *spacing = u->u.Spacing();
+    return AVR_OK;
+}
+int avr_graph_uniform_get(const avr_graph_uniform *u, int *coors, float *light) {
+    if (!u) return fail(AVR_ERR_ARG, "null uniform graph");
+    const size_t m = u->u.NumVertices();
+    if (coors) std::memcpy(coors, u->u.Coors(), 3 * m * sizeof(int));
+    if (light) std::memcpy(light, u->u.Light(), m * sizeof(float));
+    return AVR_OK;
+}
+int avr_graph_uniform_lookup(const avr_graph_uniform *u, long long n, const float *points, int *id_out, float *light_out) {
+    if (!u || n < 0) return fail(AVR_ERR_ARG, "bad uniform lookup arguments");
+    if (n > 0 && !points) return fail(AVR_ERR_ARG, "null buffer");
+    u->u.Lookup(n, points, id_out, light_out);
+    return AVR_OK;
+}
+int avr_graph_uniform_trace(const avr_graph_uniform *u, long long n, const float *o, const float *d, int *id_out,
+                            float *hit0, float *hit1) {
+    if (!u || n < 0) return fail(AVR_ERR_ARG, "bad uniform trace arguments");
+    if (n > 0 && (!o || !d)) return fail(AVR_ERR_ARG, "null buffer");
+    u->u.Trace(n, o, d, id_out, hit0, hit1);
+    return AVR_OK;
+}
+
+int avr_graph_uniform_lookup_device(avr_context *c, const avr_graph_uniform *u, long long n, const float *points,
+                                    int *id_out, float *light_out) {
+    if (!c || !u || n < 0) return fail(AVR_ERR_ARG, "bad uniform lookup arguments");
+    if (n == 0) return AVR_OK;
+    if (!points || !id_out || !light_out) return fail(AVR_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_graph_uniform(c, u);
+    if (rc) return rc;
+    char *buf = nullptr;
+    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
+    HIP_TRY(dalloc(&buf, szP + 2 * szL));
+    float *dP = (float *)buf, *dL = (float *)(buf + szP);
+    int *dI = (int *)(buf + szP + szL);
+    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_graph_uniform_lookup, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni,
+                           n, dP, dI, dL);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(light_out, dL, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(id_out, dI, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform lookup: ") + hipGetErrorString(e));
+    return AVR_OK;
+}
+
+int avr_graph_uniform_trace_device(avr_context *c, const avr_graph_uniform *u, long long n, const float *o, const float *d,
+                                   int *id_out, float *hit0, float *hit1) {
+    if (!c || !u || n < 0) return fail(AVR_ERR_ARG, "bad uniform trace arguments");
+    if (n == 0) return AVR_OK;
+    if (!o || !d || !id_out || !hit0 || !hit1) return fail(AVR_ERR_ARG, "null buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_graph_uniform(c, u);
+    if (rc) return rc;
+    char *buf = nullptr;
+    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
+    HIP_TRY(dalloc(&buf, 2 * szP + 3 * szL));
+    float *dO = (float *)buf, *dD = (float *)(buf + szP), *dH0 = (float *)(buf + 2 * szP + szL),
+          *dH1 = (float *)(buf + 2 * szP + 2 * szL);
+    int *dI = (int *)(buf + 2 * szP);
+    hipError_t e = hipMemcpyAsync(dO, o, szP, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dD, d, szP, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_graph_uniform_trace, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni,
+                           n, dO, dD, dI, dH0, dH1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(id_out, dI, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hit0, dH0, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hit1, dH1, szL, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform trace: ") + hipGetErrorString(e));
     return AVR_OK;
 }
 

@@ -46,7 +46,13 @@ real scatters and each scatter point is looked up in the vertex index (k_graph_a
 capi.GraphIndex.coverage): a vertex within the vertex radius? vertices within their own search
 range, and how far? GraphAnalysis holds the per-pixel counters and the reference's figures.
 
-Not mirrored: the uniform-graph branch, --graph-debug.
+The uniform graph (UniformGraph, graph.h:195; GraphIntegrator's uniform branch,
+graph_integrator.cpp:89-178) has its vertices on the integer lattice of a spacing:
+FreeGraph.to_uniform(spacing, light_scalar) converts a lit free graph (FreeGraph::ToUniform's
+vertex part), UniformGraph.save / load_uniform go through the reference's file format, and
+GraphIntegrator renders from it when handed a capi.GraphUniform: the scatter point's voxel is
+looked up in one hash table (k_graph_render_uniform), with no radius search; voxel_view=True is
+--graph-debug's view of the lit voxels.
 """
 import json
 import math
@@ -295,6 +301,58 @@ class FreeGraph:
         """Graph::WriteToDisk as graph_maker calls it (graph_io.write_graph): the vertices with
         `light_scalar` and, when computed, their search ranges, in the reference's file format."""
         graph_io.write_graph(path, self, light_scalar, description=description, precision=precision, edges=edges)
+
+
+    def to_uniform(self, spacing, light_scalar, reduce="first"):
+        """FreeGraph::ToUniform (graph.cpp:597-604), the vertex part: a UniformGraph of
+        `spacing` over these vertices with `light_scalar`, taken in ascending id (the reference
+        iterates an unordered map: its order is unspecified); the first vertex of a voxel makes
+        the new vertex. reduce "first" keeps that vertex's light, as the reference's AddVertex
+        does; "mean" takes the float mean of the voxel's lights. Edges and paths are not
+        carried: the render reads neither."""
+        return UniformGraph(capi.GraphUniform.from_points(self.points, light_scalar, spacing, reduce=reduce))
+
+
+class UniformGraph:
+    """A uniform lighting graph: capi.GraphUniform (`.table`, what GraphIntegrator takes) with
+    the graph-level names: spacing, coors (m, 3), points, light_scalar, num_vertices,
+    vertex_of (after a conversion: old -> new vertex id), save."""
+
+    def __init__(self, table):
+        self.table = table
+        self.spacing = table.spacing
+        self.coors = table.coors
+        self.light_scalar = table.light_scalar
+        self.vertex_of = getattr(table, "vertex_of", None)
+
+    @property
+    def num_vertices(self):
+        return self.table.num_vertices
+
+    @property
+    def points(self):
+        return self.table.points
+
+    def save(self, path, description="basic", precision=9):
+        """UniformGraph::WriteToStream's file (graph_io.write_uniform_graph)."""
+        graph_io.write_uniform_graph(path, self, description=description, precision=precision)
+
+
+def load_uniform(path):
+    """The uniform graph of a graph file (UniformGraph::ReadFromDisk): the vertices are added
+    in file order, keyed by FitToGraph(point); a later vertex in an occupied voxel is dropped,
+    as ReadFromStream -> AddVertex does (the coors column is read but is not the key). Vertex
+    ids are the order of first appearance. Raises on a free graph and on a file written
+    without lighting."""
+    g = graph_io.read_graph(path)
+    if g.kind != "uniform":
+        raise ValueError(f"{path}: a {g.kind} graph; load_uniform takes uniform graphs")
+    if g.light_scalar is None:
+        raise ValueError(f"{path}: written without lighting (useLighting False): nothing to render")
+    if g.num_vertices == 0:
+        raise ValueError(f"{path}: no vertices")
+    order = g.file_ids
+    return UniformGraph(capi.GraphUniform.from_points(g.points[order], g.light_scalar[order], g.spacing, reduce="first"))
 
 
 def load_index(path):
@@ -608,16 +666,23 @@ class GraphIntegrator(FilmIntegrator):
     medium's bounds box, which refuses a scene with an interface sphere or mesh; "interface",
     the scene's interface sphere or mesh (the box for a scene without one). The scene needs
     exactly one DistantLight and not a GBufferFilm (its geometric channels have no meaning
-    here). render(), film_sums(), image(), get_image() and write_image() are
+    here). A capi.GraphUniform (or a UniformGraph) as `graph_index` renders the uniform branch
+    (:89-178) instead: L = lightSpectrum * lightScalar * light_scale for the vertex of the
+    scatter point's voxel (k_graph_render_uniform); light_scale is the reference's Inv4Pi by
+    default, and a graph whose light comes from LightingCalculator, which already carries
+    Inv4Pi, takes light_scale=1. voxel_view=True is --graph-debug (:104-131): every camera ray
+    shows the first lit voxel it enters, without light_scale. render(), film_sums(), image(), get_image() and write_image() are
     VolPathIntegrator's."""
 
     def __init__(self, scene, graph_index, spp=1, seed=0, graph_from_render=None, device=0, max_paths=0,
-                 primitive="box"):
+                 primitive="box", voxel_view=False, light_scale=None):
         if isinstance(scene.film, GBufferFilm):
             raise ValueError("GraphIntegrator does not render into a GBufferFilm")
         self.primitive = _check_primitive(primitive)
         self.scene = scene
-        self.index = graph_index
+        self.index = graph_index.table if isinstance(graph_index, UniformGraph) else graph_index
+        self.voxel_view = bool(voxel_view)
+        self.light_scale = capi.INV_4PI if light_scale is None else float(light_scale)
         self.spp = int(spp)
         self.seed = int(seed)
         self.device = int(device)
@@ -628,18 +693,27 @@ class GraphIntegrator(FilmIntegrator):
 
     @classmethod
     def from_file(cls, scene, path, **kw):
-        """The integrator over a graph file (`pbrt --graph`): load_index(path), then the
+        """The integrator over a graph file (`pbrt --graph`): load_uniform(path) or
+        load_index(path) by the file's kind, as GraphIntegrator::Initialize decides, then the
         constructor's keywords."""
+        if graph_io.read_kind(path) == "uniform":
+            return cls(scene, load_uniform(path), **kw)
         return cls(scene, load_index(path), **kw)
 
     def _render_range(self, spp_begin, spp_end):
-        self.ctx.graph_render(self.index, spp_begin, spp_end, self.seed, self.graph_from_render)
+        if isinstance(self.index, capi.GraphUniform):
+            self.ctx.graph_render_uniform(self.index, spp_begin, spp_end, self.seed, self.graph_from_render,
+                                          view=1 if self.voxel_view else 0, light_scale=self.light_scale)
+        else:
+            self.ctx.graph_render(self.index, spp_begin, spp_end, self.seed, self.graph_from_render)
 
     def last_pass(self, max_samples=None):
         """The last pass per sample: dict of first sample index, sample count, L, lambda, pdf
         (n, 4), camera ray o, d, scatter point p (n, 3, render space) and the vertices
         averaged (count, -1 without a scatter); n = pixels x samples of that pass, element
-        s * pixels + pixel."""
+        s * pixels + pixel. With a uniform graph count is 1 (the point's voxel has a vertex), 0
+        or -1; with voxel_view p is the lit voxel's chord middle in graph space and count 1 / 0
+        where a lit voxel was hit, -1 elsewhere."""
         f = self.scene.film
         npix = f.width * f.height
         ms = self.spp if max_samples is None else int(max_samples)

@@ -16,6 +16,9 @@ newline. The reader takes whitespace-separated tokens as the reference's operato
 line breaks carry no meaning to it; vertex lines may come in any id order (the reference
 writes an unordered_map) and are placed by id.
 
+A uniform graph's file (write_uniform_graph) has useCoors True: the vertex's three integer
+lattice coordinates follow its data.
+
 Floats are written as %.{precision}g. precision 6 is the text of the reference's ostream at
 its default precision; the default 9 lets every float32 survive a round trip exactly. The
 reference reads either.
@@ -34,6 +37,7 @@ class GraphFile:
     description, kind ("free" or "uniform"), radius (free: vertexRadius) or spacing (uniform),
     flags (dict over FLAG_NAMES), cur_vertex_id, cur_edge_id, cur_path_id;
     points (n, 3) float32, vertex_type, light_scalar, samples, search_range, coors (n, 3) int32;
+    file_ids: the vertex ids in the order of their lines (the reference adds vertices in that order);
     edge_id, edge_from, edge_to, edge_samples; paths: list of (id, int32 vertex ids)."""
 
     def __init__(self):
@@ -44,6 +48,7 @@ class GraphFile:
         self.flags = dict.fromkeys(FLAG_NAMES, False)
         self.cur_vertex_id = self.cur_edge_id = self.cur_path_id = 0
         self.points = np.zeros((0, 3), f32)
+        self.file_ids = np.zeros(0, np.int32)
         self.vertex_type = self.light_scalar = self.samples = self.search_range = self.coors = None
         self.edge_id = self.edge_from = self.edge_to = np.zeros(0, np.int32)
         self.edge_samples = None
@@ -121,6 +126,19 @@ class _Tokens:
         return cols
 
 
+def read_kind(path):
+    """"free" or "uniform": the second token of a graph file, which GraphIntegrator::Initialize
+    (graph_integrator.cpp:29-33) reads to choose its branch."""
+    with open(path, "r") as fh:
+        tk = _Tokens(path, fh.read(4096))
+    tk.word("the description")
+    i = tk.pos
+    kind = tk.word('"free" or "uniform"')
+    if kind not in ("free", "uniform"):
+        raise tk.error(i, '"free" or "uniform"')
+    return kind
+
+
 def read_graph(path):
     """Read a graph file (Graph::ReadFromStream, graph.cpp:347-416, under the free / uniform
     header, :572-577 / :650-655) into a GraphFile. ValueError with the line number on a short
@@ -171,6 +189,7 @@ def read_graph(path):
         what = f"vertex id {b} is missing" if seen > b else f"vertex id {seen} is out of place or repeated"
         raise ValueError(f"{path}: line {tk.line(start + int(order[b]) * len(kinds))}: {what}: "
                          f"Graph must have sequential vertex ids 0..{nv - 1}")
+    g.file_ids = ids.astype(np.int32)
     cols = [c[order] for c in cols]
     g.points = np.stack(cols[1:4], axis=1).astype(f32) if nv else np.zeros((0, 3), f32)
     c = 4
@@ -247,3 +266,33 @@ def write_graph(path, graph, light_scalar=None, description="basic", precision=9
             es = np.asarray(graph.edge_samples, np.int64).tolist()
             fh.writelines("%d %d %d %d \n" % row for row in zip(range(nedges), np.asarray(graph.edge_from).tolist(),
                                                                np.asarray(graph.edge_to).tolist(), es))
+
+
+def write_uniform_graph(path, uniform, description="basic", precision=9):
+    """Write a uniform graph (a capi.GraphUniform, a graph.UniformGraph, or anything with coors
+    (m, 3), light_scalar and spacing) as UniformGraph::WriteToStream does (graph.cpp:566-570,
+    :284-345): "uniform <spacing>", vertices only, useLighting, and useCoors True with the three
+    lattice coordinates after the vertex data (:314-315). The point of a vertex is
+    (float)coors * spacing (:555). precision as write_graph's."""
+    coors = np.ascontiguousarray(uniform.coors, np.int32).reshape(-1, 3)
+    light = np.ascontiguousarray(uniform.light_scalar, f32).reshape(-1)
+    n = len(coors)
+    if len(light) != n:
+        raise ValueError("write_uniform_graph: one light_scalar per vertex")
+    if not isinstance(description, str) or len(description.split()) != 1:
+        raise ValueError("write_uniform_graph: the description is one token without whitespace")
+    p = int(precision)
+    if p < 1:
+        raise ValueError("write_uniform_graph: precision must be positive")
+    spacing = f32(uniform.spacing)
+    pts = (coors.astype(f32) * spacing).astype(f32)
+    ff = f"%.{p}g "
+    fmt = "%d " + ff * 4 + "%d %d %d \n"
+    cols = [range(n)] + [pts[:, a].astype(np.float64).tolist() for a in range(3)] + [light.astype(np.float64).tolist()] \
+        + [coors[:, a].tolist() for a in range(3)]
+    with open(path, "w", newline="\n") as fh:
+        fh.write(f"{description}\n")
+        fh.write("uniform %.*g\n" % (p, float(spacing)))
+        fh.write("True False False True False\n")
+        fh.write(f"{n} 0 0 {n} 0 0\n")
+        fh.writelines(fmt % row for row in zip(*cols))

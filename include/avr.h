@@ -673,8 +673,76 @@ int avr_graph_render(avr_context *ctx, const avr_graph_index *idx, const float g
  * avr_last_pass_weights, returns that pass's L, wavelengths, pdfs and filter weights): the
  * camera ray o, d (n*3 each), the scatter point in render space (n*3) and the number of
  * vertices averaged, -1 when the sample did not scatter. Any output may be NULL.
+ * After avr_graph_render_uniform with view 0: the scatter point in render space and 1 (its
+ * voxel has a vertex), 0 (scattered, no vertex) or -1 (no scatter); with view 1: the point
+ * `middle` in graph space and 1 / 0 (a lit voxel was hit, and the lookup at middle found /
+ * did not find a vertex), -1 otherwise.
  * AVR_ERR_STATE when the last render was avr_render's or avr_graph_analyze's. */
 int avr_graph_last_pass(avr_context *ctx, float *o, float *d, float *points, int *counts, long long n_max);
+
+/* The uniform (voxel) lighting graph: UniformGraph (graph/graph.h:195, graph.cpp:545-577),
+ * vertices on the integer lattice of a spacing. Host code, no GPU needed.
+ * Coordinates (FitToGraph, graph/util.h:302-311): per axis q = p / spacing in float, r =
+ * roundf(q) (half away from zero), c = (int)r; valid iff |r| < 2^20 (the reference casts any
+ * value; NaN is invalid), so that a voxel packs into one 64-bit key. The vertex's point is
+ * (float)c * spacing per axis. Lookup structure: one open-addressing hash table with linear
+ * probing, 16-B entries {key, id, lightScalar}, capacity the smallest power of two >= 2 m (at
+ * least 16), uploaded to the device on first use and cached on the context under an id stored
+ * in the object, as avr_graph_index is.
+ * avr_graph_uniform_create: m vertices with coordinates coors (m*3) and lightScalar light (m);
+ * AVR_ERR_ARG, naming the vertex: spacing not finite or <= 0, m < 1, a coordinate outside
+ * +-2^20, a NaN light, a repeated coordinate.
+ * avr_graph_uniform_from_points: FreeGraph::ToUniform's vertex part (graph.cpp:597-604,
+ * 545-564) for n free-graph vertices xyz (n*3) with lights light (n). The vertices are taken
+ * in ascending id (the reference iterates an unordered map: its order is unspecified) and a
+ * new vertex is made at the first appearance of a voxel, new ids in that order. reduce 0
+ * ("first"): the voxel keeps its first vertex's light (AddVertex returns the existing vertex);
+ * reduce 1 ("mean"): the float sum from 0 of its vertices' lights in ascending id over
+ * (float)count. vertex_of (n, may be NULL): old -> new id. Edges and paths are not carried.
+ * AVR_ERR_ARG as above, and for a point whose coordinate is invalid.
+ * avr_graph_uniform_get: the coordinates (m*3) and lights (m) by vertex id; either may be NULL.
+ * avr_graph_uniform_lookup: UniformGraph::GetVertexConst for n points in graph space: the
+ * vertex id of the point's voxel or -1 (also for an invalid coordinate) and its light (0
+ * without a vertex). Either output may be NULL.
+ * avr_graph_uniform_trace: --graph-debug's search (graph_integrator.cpp:104-131) for n rays
+ * o + t d (n*3 each) in graph space: among the vertices with light != 0, the one whose box
+ * [mid - spacing / 2, mid + spacing / 2] the ray enters first, with hit0 and hit1 of
+ * Bounds3::IntersectP(o, d, Infinity, &hit0, &hit1) for it (t0 from 0, tFar widened by
+ * 1 + 2 gamma(3)); id -1 and 0, 0 without one. The reference keeps the smallest hit0 over all
+ * lit voxels with a strict < in unordered-map order; here equal hit0 go to the lower id. A
+ * 3-D DDA over the lattice cells with the exact IntersectP per lit candidate: the brute-force
+ * answer whenever the two smallest hit0 differ and the winner's chord is more than rounding. */
+typedef struct avr_graph_uniform avr_graph_uniform;
+int avr_graph_uniform_create(long long m, const int *coors, const float *light, float spacing, avr_graph_uniform **out);
+int avr_graph_uniform_from_points(long long n, const float *xyz, const float *light, float spacing, int reduce,
+                                  int *vertex_of, avr_graph_uniform **out);
+int avr_graph_uniform_destroy(avr_graph_uniform *u);
+int avr_graph_uniform_size(const avr_graph_uniform *u, long long *n_vertices, float *spacing);
+int avr_graph_uniform_get(const avr_graph_uniform *u, int *coors, float *light);
+int avr_graph_uniform_lookup(const avr_graph_uniform *u, long long n, const float *points, int *id_out,
+                             float *light_out);
+int avr_graph_uniform_trace(const avr_graph_uniform *u, long long n, const float *o, const float *d, int *id_out,
+                            float *hit0, float *hit1);
+/* The same on the device (k_graph_uniform_lookup, k_graph_uniform_trace: one lane per query)
+ * with bitwise the host's results. Host arrays, synchronous; every output is required. */
+int avr_graph_uniform_lookup_device(avr_context *ctx, const avr_graph_uniform *u, long long n, const float *points,
+                                    int *id_out, float *light_out);
+int avr_graph_uniform_trace_device(avr_context *ctx, const avr_graph_uniform *u, long long n, const float *o,
+                                   const float *d, int *id_out, float *hit0, float *hit1);
+/* GraphIntegrator::Li, uniform-graph branch (graph_integrator.cpp:89-178): avr_graph_render's
+ * pass loop, requirements and errors with k_graph_render_uniform in place of k_graph_render.
+ * view 0: the walk to the first real scatter p is avr_graph_render's, draw for draw; then
+ * L = (lightSpectrum.Sample(lambda) * lightScalar) * light_scale for the vertex of
+ * graph_from_render(p)'s voxel, 0 without one. The reference's light_scale is Inv4Pi; a
+ * graph lit by avr_graph_light already carries Inv4Pi and takes 1. view 1, --graph-debug's
+ * voxel view: no sampler draw and no tracking; the ray from where avr_graph_render's walk
+ * starts, mapped to graph space (point and vector), finds its first lit voxel as
+ * avr_graph_uniform_trace does; middle = o' + d' * ((hit0 + hit1) / 2); L =
+ * lightSpectrum.Sample(lambda) * lightScalar of the vertex at middle (light_scale unused), 0
+ * on a miss of the primitive, without a lit voxel or without a vertex at middle.
+ * AVR_ERR_ARG: view outside {0, 1}, a light_scale that is not finite. */
+int avr_graph_render_uniform(avr_context *ctx, const avr_graph_uniform *u, const float graph_from_render[16],
+                             int spp_begin, int spp_end, int seed, int view, float light_scale);
 
 /* IntegrationAnalyzer's Analyze (graph/analysis/integration_analyzer.cpp:56-83) for n points
  * already in graph space; host code, no GPU needed. node[i] = 1 when radiusSearch(point,

@@ -8,9 +8,16 @@ fork's `pbrt --graph` read. PREFIX_stats.json holds the graph's sizes and the se
 usage: python tools/graph_maker.py [--scene s-cloud] [--n 64] [--config CONFIG.json] --out PREFIX
                                    [--precision 9] [--search-ranges device] [--sampler 0] [--seed 0]
                                    [--interface-sphere CX,CY,CZ,R] [--merge host]
+                                   [--uniform SPACING [--uniform-reduce first|mean]]
 
 --interface-sphere bounds the medium by a sphere (world space): the scene gets it as its
 interface and the graph is made with the sphere as the primitive (primitive="interface").
+
+--uniform SPACING also converts each lit graph to a uniform graph of that spacing
+(FreeGraph.to_uniform; --uniform-reduce: the light of a voxel with several vertices is its first
+vertex's, as in the reference, or their mean) and writes PREFIX_d{depth}_uniform.txt, which
+GraphIntegrator.from_file renders with the uniform branch; such a graph's light already carries
+Inv4Pi, so it takes light_scale=1.
 
 CONFIG.json is the reference's graph config (graphBuilder / lightingCalculator, util.h:750-812);
 without one the defaults below are used.
@@ -75,6 +82,10 @@ def parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--interface-sphere", type=interface_sphere, metavar="CX,CY,CZ,R",
                    help="bound the medium by this sphere (world space) and use it as the graph tools' primitive")
+    p.add_argument("--uniform", type=float, metavar="SPACING",
+                   help="also write PREFIX_d{depth}_uniform.txt, the uniform graph of this spacing")
+    p.add_argument("--uniform-reduce", choices=("first", "mean"), default="first",
+                   help="the light of a voxel that holds several vertices")
     return p
 
 
@@ -135,6 +146,14 @@ def main(argv=None):
         seconds["write"].append(time.perf_counter() - t0)
         files.append({"file": name, "bounces": int(bounces), "depth": int(depth_computed),
                       "light_average": float(np.mean(lc.light_scalar, dtype=np.float64))})
+        if a.uniform is not None:
+            t0 = time.perf_counter()
+            ug = g.to_uniform(a.uniform, lc.light_scalar, reduce=a.uniform_reduce)
+            uname = f"{a.out}_d{depth_computed}_uniform.txt"
+            ug.save(uname, precision=a.precision)
+            seconds.setdefault("uniform", []).append(time.perf_counter() - t0)
+            files[-1]["uniform"] = {"file": uname, "spacing": float(ug.spacing), "reduce": a.uniform_reduce,
+                                    "vertices": int(ug.num_vertices)}
         if depth != depth_computed:
             print(f"Numerical limits reached with depth {depth_computed}, depth {depth} not possible")
             break

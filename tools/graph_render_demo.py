@@ -7,10 +7,19 @@ for context, a VolPathIntegrator render of the same scene and spp at maxdepth = 
 usage: python tools/graph_render_demo.py [--n 256] [--out DIR] [--steps 64] [--iterations 8]
                                          [--radius-modifier 20] [--bounces 10]
                                          [--interface-sphere CX,CY,CZ,R]
+                                         [--uniform SPACING [--uniform-reduce first|mean] [--voxel-view]]
 
 --interface-sphere bounds the cloud by a sphere (world space): graph, graph render and the
 VolPathIntegrator render beside them then all take the sphere as the medium's boundary
 (primitive="interface").
+
+--uniform SPACING also converts the lit graph to a uniform graph of that spacing (a number, or
+a multiple of the vertex radius written as 1r, 2r, ...) and times its render (view 0,
+light_scale 1: the graph's light already carries Inv4Pi) against the free-graph render in
+the same process: 16 spp, the two alternately, three timed runs each after one warm-up each,
+median and spread of ms_medium and ms_total, and the share of the 1-spp pass's scatters that
+find a vertex, for both kinds. --voxel-view also times --graph-debug's voxel view once and
+writes its EXR.
 """
 import argparse
 import json
@@ -53,7 +62,72 @@ def parser():
     p.add_argument("--height", type=int, default=720)
     p.add_argument("--interface-sphere", type=interface_sphere, metavar="CX,CY,CZ,R",
                    help="bound the medium by this sphere (world space) and use it as the graph tools' primitive")
+    p.add_argument("--uniform", metavar="SPACING", help="also render the uniform graph of this spacing (number, or Nr = N vertex radii)")
+    p.add_argument("--uniform-reduce", choices=("first", "mean"), default="first")
+    p.add_argument("--voxel-view", action="store_true", help="with --uniform: also render the voxel view")
     return p
+
+
+def uniform_spacing(text, radius):
+    """--uniform's value: a number, or a multiple of the vertex radius ("1r", "2.5r")."""
+    if text.endswith("r"):
+        return float(np.float32(float(text[:-1] or 1) * float(radius)))
+    return float(text)
+
+
+def compare_uniform(a, integ, g, light_scalar, out):
+    """The uniform render beside the free render on the same lit graph (see the module text)."""
+    free = integ.index
+    spacing = uniform_spacing(a.uniform, g.radius)
+    t0 = time.perf_counter()
+    ug = g.to_uniform(spacing, light_scalar, reduce=a.uniform_reduce)
+    res = {"spacing": spacing, "reduce": a.uniform_reduce, "vertices": int(ug.num_vertices),
+           "s_convert": time.perf_counter() - t0, "light_scale": 1.0}
+    integ.light_scale = 1.0
+    kinds = {"free": free, "uniform": ug.table}
+    found = {}
+    for name, index in kinds.items():          # the warm-up: uploads, allocations; and the found share
+        integ.index = index
+        integ.render(0, 1)
+        c = integ.last_pass(1)["count"]
+        found[name] = float(np.mean(c[c >= 0] > 0))
+        integ.render(0, 16)
+    res["scatters_finding_a_vertex_1spp"] = found
+    runs = {"free": [], "uniform": []}
+    for _ in range(3):
+        for name, index in kinds.items():
+            integ.index = index
+            integ.ctx.sync()
+            integ.ctx.reset_stats()
+            integ.render(0, 16)
+            integ.ctx.sync()
+            st = integ.ctx.stats()
+            runs[name].append({"ms_medium": st["ms_medium"], "ms_total": st["ms_total"]})
+    for name, rr in runs.items():
+        res[name + "_16spp"] = {k: {"median": float(np.median([r[k] for r in rr])),
+                                    "min": float(min(r[k] for r in rr)), "max": float(max(r[k] for r in rr)),
+                                    "runs": [float(r[k]) for r in rr]} for k in ("ms_medium", "ms_total")}
+    rgb, w = integ.film_sums()
+    res["image_mean"] = float(integ.write_image(os.path.join(a.out, "graph_render_uniform_16spp.exr"), rgb, w, spp=16).mean())
+    if a.voxel_view:
+        integ.voxel_view = True
+        integ.render(0, 16)
+        integ.ctx.sync()
+        integ.ctx.reset_stats()
+        integ.render(0, 16)
+        integ.ctx.sync()
+        st = integ.ctx.stats()
+        res["voxel_view_16spp"] = {"ms_medium": st["ms_medium"], "ms_total": st["ms_total"]}
+        rgb, w = integ.film_sums()
+        integ.write_image(os.path.join(a.out, "graph_voxel_view_16spp.exr"), rgb, w, spp=16)
+        integ.voxel_view = False
+    integ.index = free
+    out["uniform"] = res
+    print("uniform vs free, 16 spp: k_graph_render_uniform %.3f ms (%.3f..%.3f), k_graph_render %.3f ms (%.3f..%.3f); "
+          "scatters finding a vertex: uniform %.3f, free %.3f" % (
+              res["uniform_16spp"]["ms_medium"]["median"], res["uniform_16spp"]["ms_medium"]["min"],
+              res["uniform_16spp"]["ms_medium"]["max"], res["free_16spp"]["ms_medium"]["median"],
+              res["free_16spp"]["ms_medium"]["min"], res["free_16spp"]["ms_medium"]["max"], found["uniform"], found["free"]))
 
 
 def main(argv=None):
@@ -109,6 +183,8 @@ def main(argv=None):
     rgb, w = integ.film_sums()
     img = integ.write_image(os.path.join(a.out, "graph_render_16spp.exr"), rgb, w, spp=16)
     out["graph_image_mean"] = float(img.mean())
+    if a.uniform:
+        compare_uniform(a, integ, g, lc.light_scalar, out)
     integ.close()
 
     vp = VolPathIntegrator(scene, maxdepth=a.bounces + 1, spp=16, seed=0)
