@@ -1,7 +1,7 @@
 """Build libavr_hip.so in-tree with hipcc for gfx950 (no JIT cache: the .so travels
 with the repository snapshot to the GPU box).
 
-The persistent path kernel k_paths has 112 instantiations (medium kind x emission x gray
+The persistent path kernel k_paths has 168 instantiations (medium kind x emission x gray
 state x sampler x image light x render mode); they are compiled as eight objects
 (csrc/avr_kpaths.hip, one per medium kind and render mode) in parallel with the C-ABI
 unit (csrc/avr_capi.hip, -DAVR_KP_SPLIT), then linked."""
@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "avr_capi.hip")
 KPATHS = os.path.join(CSRC, "avr_kpaths.hip")
 DEPS = [os.path.join(CSRC, f) for f in (
-    "avr_capi.hip", "avr_kernels.hip", "avr_kpaths.hip", "avr_kpaths_list.h", "avr_numerics.h", "avr_canon.h",
+    "avr_capi.hip", "avr_render.hip", "avr_kernels.hip", "avr_kpaths.hip", "avr_kpaths_list.h", "avr_kpaths_slot.h", "avr_numerics.h", "avr_canon.h",
     "avr_sampling.h", "avr_vdb.h", "avr_envmap.h", "avr_flip.h", "avr_graph.hip", "avr_graph_capi.hip",
     "avr_graph_host.h", "avr_graph_index.h", "avr_graph_merge.h", "avr_graph_uniform.h", "avr_boundary.h", "avr_fastdiv.h", "avr_image_kernels.h")] + [os.path.join(ROOT, "include", "avr.h")]
 OUT = os.path.join(HERE, "libavr_hip.so")

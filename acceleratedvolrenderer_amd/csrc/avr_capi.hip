@@ -10,10 +10,11 @@
 // Everything is enqueued on one HIP stream; the host reads back one int (the
 // survivor count) per depth iteration to size the next launch and stop early.
 #include "avr_kernels.hip"
+#include "avr_kpaths_list.h"
+#include "avr_kpaths_slot.h"
 #ifdef AVR_KP_SPLIT
 // k_paths is instantiated in avr_kpaths.hip's translation units (one per medium kind and
 // render mode, compiled in parallel by build.py); declared here, launched from avr_render
-#include "avr_kpaths_list.h"
 namespace avr {
 #define AVR_KP_DECL(em, gr, zs, med, im, fa) extern template __global__ void k_paths<em, gr, zs, med, im, fa>(Params);
 AVR_KP_ALL(AVR_KP_DECL)
@@ -48,18 +49,106 @@ int fail(int code, const std::string &msg) {
             return fail(AVR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
     } while (0)
 
-#ifndef AVR_ZS_TWO_LEVEL
-#define AVR_ZS_TWO_LEVEL 1   // build the ZSobol pass table from a level-A table shared by 4 passes
-#endif
-
 template <typename T>
 hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)); }
 
 }  // namespace
 
-#ifndef AVR_PASS_OVERLAP_DEFAULT
-#define AVR_PASS_OVERLAP_DEFAULT 1
-#endif
+// The camera set: k_paths' per-sample records, its camera stage's buffers (PathSoA's rec, cam0..5,
+// camw) and the work heads the stage resets. The one place that lists them.
+struct CameraSet {
+    float4 *rec = nullptr, *cam0 = nullptr, *cam1 = nullptr, *cam2 = nullptr, *cam4 = nullptr;
+    uint4 *cam3 = nullptr, *cam5 = nullptr;
+    float *camw = nullptr;
+    int *heads = nullptr;   // 8 per-XCD work counters of k_paths + the pass generation
+    template <typename F>
+    void each_buffer(F f) { f(rec); f(cam0); f(cam1); f(cam2); f(cam3); f(cam4); f(cam5); f(camw); }
+    // point a launch's arguments at this set
+    void point(avr::Params &p) const {
+        p.ps.rec = rec; p.ps.camw = camw; p.heads = heads;
+        p.ps.cam0 = cam0; p.ps.cam1 = cam1; p.ps.cam2 = cam2; p.ps.cam3 = cam3; p.ps.cam4 = cam4; p.ps.cam5 = cam5;
+    }
+    // the eight per-sample buffers for n samples (on failure, those allocated stay for free_buffers)
+    hipError_t alloc_buffers(size_t n) {
+        hipError_t e = hipSuccess;
+        each_buffer([&](auto *&p) { if (e == hipSuccess) e = dalloc(&p, n); });
+        return e;
+    }
+    // heads that no pass generation matches
+    hipError_t alloc_heads() {
+        hipError_t e = dalloc(&heads, 9);
+        return e == hipSuccess ? hipMemset(heads, 0xff, 9 * sizeof(int)) : e;
+    }
+    void free_buffers() { each_buffer([](auto *&p) { if (p) (void)hipFree(p); p = nullptr; }); }
+    void free_heads() { if (heads) (void)hipFree(heads); heads = nullptr; }
+};
+
+constexpr int kPtabKey = 8;   // what a built ZSobol pass table depends on (ptab_key)
+
+// Pass overlap: k_paths is held to four blocks per CU while a camera stage runs beside it
+// (pass_kpaths, avr_render.hip); the dynamic LDS that keeps a fifth block off a CU: 4 x (k_paths'
+// 31.5 KB + pad) + the camera block's 28.3 KB fit the 160 KiB, 5 x (31.5 KB + pad) do not
+// (tests/test_overlap_resources.py reads the value from this file)
+constexpr int kOverlapLdsPad = 1536;
+
+// What the side stream holds (or is making) for the pass expected next: its ZSobol pass table
+// (avr_set_pass_table_ahead) and, with pass overlap, its camera records in the other camera set.
+struct LookAhead {
+    bool tab_valid = false;   // a table for `key` in pass-table buffer `buf`
+    long long key[kPtabKey] = {};
+    int buf = 0;
+    bool cam_valid = false;   // ... and camera records made with the arguments `params`, at setup generation `gen`
+    avr::Params params{};
+    unsigned long long gen = 0;
+    void invalidate() { tab_valid = cam_valid = false; }
+    // Take what was built ahead for the pass that `k` names. `stream` waits for the side stream's
+    // work (ev_tab) whether it is used or not, so no build of this pass overlaps it. *b: the
+    // table's buffer, or -1 when none was built for this pass; *cam: camera records came with it
+    // and no setup call or readback (cfg_gen) came between. Nothing stays claimed.
+    hipError_t claim(hipStream_t stream, hipEvent_t ev_tab, const long long *k, unsigned long long cfg_gen, int *b,
+                     bool *cam) {
+        *b = -1;
+        *cam = false;
+        if (!tab_valid) return hipSuccess;
+        const hipError_t e = hipStreamWaitEvent(stream, ev_tab, 0);
+        if (e != hipSuccess) return e;
+        const bool same = std::equal(k, k + kPtabKey, key);
+        if (same) *b = buf;
+        *cam = same && cam_valid && gen == cfg_gen;
+        invalidate();
+        return hipSuccess;
+    }
+    void publish(const long long *k, int b, const avr::Params *cam_params, unsigned long long cfg_gen) {
+        std::copy(k, k + kPtabKey, key);
+        buf = b;
+        tab_valid = true;
+        cam_valid = cam_params != nullptr;
+        if (cam_params) params = *cam_params, gen = cfg_gen;
+    }
+};
+
+// The last pass rendered, written once per pass by the integrator that ran it and read by the
+// avr_last_*, avr_graph_last_pass and avr_graph_analyze_last_pass readbacks
+struct LastPass {
+    bool persistent = false;   // k_paths (else the wavefront kernels or a graph integrator)
+    bool fast = false;         // ... in fast mode
+    bool graph = false;        // avr_graph_render's or avr_graph_render_uniform's
+    int analyze = 0;           // avr_graph_analyze's: 1 without, 2 with detail
+    int analyze_depth = 0;     // ... and its max_depth (the detail's stride)
+    int base = 0, S = 0;       // sample indices [base, base + S)
+    int order_gen = 0;         // the pixel-order generation its k_paths records are in
+    // of the last k_paths pass (a pass of another integrator carries them over): it took camera
+    // records made ahead (avr_pass_overlap_active); its slot in the kernel table, -1 none yet
+    // (avr_last_kernel, so a profiler pass can be matched to the timed run)
+    bool overlap = false;
+    int variant = -1;
+    // the record of a pass [base, base + S) that ran other kernels than k_paths
+    LastPass without_kpaths(int b, int s) const {
+        LastPass n;
+        n.base = b; n.S = s; n.overlap = overlap; n.variant = variant;
+        return n;
+    }
+};
 
 struct avr_context {
     int device = 0;
@@ -97,28 +186,21 @@ struct avr_context {
     size_t ev_used = 0;
     struct Timed { int a, b; double avr_stats::*field; bool launch; };
     std::vector<Timed> timed;         // pending (event a -> event b) intervals to fold into stats
-    int last_base = 0, last_S = 0;
+    LastPass last;
     int kernel_mode = 0;      // 0: persistent k_paths (default), 1: wavefront k_medium/k_shadow
-    bool last_persistent = false;   // which organisation the last avr_render ran
-    bool last_fast = false;         // ... and whether k_paths ran in fast mode
-    int *d_heads = nullptr;   // 8 per-XCD work counters of k_paths + the pass generation
-    int pass_gen = 0;         // k_paths passes enqueued (the camera stage stamps it into d_heads[8])
+    int pass_gen = 0;         // k_paths passes enqueued (the camera stage stamps it into its set's heads[8])
     // k_paths' pixel order (avr_set_pixel_order): slot -> pixel and pixel -> slot, and the
     // host copy of the latter (to return the last pass in pixel order); empty = scanline
     int *d_pix_order = nullptr, *d_pix_slot = nullptr;
     std::vector<int> h_pix_slot;
     // bumped whenever the pixel order changes (avr_set_pixel_order, avr_film); the last
-    // render's records are in the order of generation last_order_gen
-    int order_gen = 0, last_order_gen = 0;
-    // template arguments of the last k_paths instantiation launched ("k_paths<em, gray, smp,
-    // med, image, fast>", avr_last_kernel), so a profiler pass can be matched to the timed run
-    char last_kpaths[64] = "";
-    // k_paths<emissive, gray, sampler, medium, image, fast> at slot
-    // ((((fast*2 + image)*4 + medium(0 grid, 1 vdb, 2 rgb, 3 homogeneous/cloud))*3 + sampler(0
-    // independent, 1 zsobol 32-bit, 2 zsobol 64-bit))*2 + emissive)*2 + gray
-    static constexpr int kNumPaths = 192;
+    // render's records are in the order of generation last.order_gen
+    int order_gen = 0;
+    // the k_paths instantiations by slot (avr_kpaths_slot.h), each one's persistent grid and name
+    static constexpr int kNumPaths = avr::kp::kNumSlots;
     int paths_grid[kNumPaths] = {};
     void (*kpaths[kNumPaths])(avr::Params) = {};
+    const char *kpaths_name[kNumPaths] = {};
     int render_mode = 0;      // 0 replay (canonical math, per-sample parity), 1 fast (hardware math)
     int ray_binning = 0;      // wavefront organisation: counting-sort queues by (majorant cell, octant)
     int majorant_occupancy = 0;   // NanoVDB k_paths: coarse occupancy level of the majorant in LDS (opt-in)
@@ -171,34 +253,27 @@ struct avr_context {
     int zs_pdims = 96;
     int tab_buf = 1;              // the buffer the last pass read
     int ptab_spec = 1;            // avr_set_pass_table_ahead
-    bool spec_valid = false;      // tstream holds (or is building) the table for spec_key
-    long long spec_key[8] = {};
-    int spec_buf = 0;
+    LookAhead look;               // what tstream holds (or is building) for the next pass
     hipStream_t tstream = nullptr;
     hipEvent_t ev_cam = nullptr, ev_tab = nullptr;
     long long prev_call_begin = -1;   // avr_render's previous spp_begin (the call stride)
     // Pass overlap (avr_set_pass_overlap): behind the table built ahead, tstream also runs the
-    // next pass's camera stage, into the other set of camera buffers, records and work heads
-    // (alt / d_heads_alt; ps and d_heads always name the set of the last rendered pass), while
-    // this pass's k_paths runs. The pass that follows takes those records when its camera
-    // stage's kernel arguments equal spec_params byte for byte and no setup call or readback
-    // came between (cfg_gen, bumped by AVR_QUIESCE); otherwise it runs its own camera stage.
-    int pass_overlap = AVR_PASS_OVERLAP_DEFAULT;
-    bool last_overlap = false;        // the last pass took camera records made ahead
+    // next pass's camera stage, into the other camera set (alt; set always names the set of the
+    // last rendered pass), while this pass's k_paths runs. The pass that follows takes those
+    // records when its camera stage's kernel arguments equal look.params byte for byte and no
+    // setup call or readback came between (cfg_gen, bumped by AVR_QUIESCE); otherwise it runs
+    // its own camera stage.
+    int pass_overlap = 1;
     int num_cus = 0;
-    avr::PathSoA alt{};               // rec, cam0..cam5, camw only
-    int *d_heads_alt = nullptr;
+    CameraSet set, alt;               // set.heads lives as long as the context, the rest by ensure_records / ensure_alt
     long long alt_cap = 0;            // samples the other set holds (rec_cap, or 0: none)
     long long alt_failed_cap = 0;     // the rec_cap at which its allocation failed (not retried)
-    bool cam_spec_valid = false;      // tstream holds (or is making) camera records for spec_params
-    avr::Params spec_params{};
-    unsigned long long cfg_gen = 0, spec_gen = 0;
+    unsigned long long cfg_gen = 0;
     // Level-A pass table (the same table for plo + 2, shared by four consecutive passes);
-    // zs_akey names the build it holds (rebuilt when any field changes), zs_two_level 0 = off
+    // zs_akey names the build it holds (rebuilt when any field changes)
     uint64_t *d_zs_atab = nullptr;
     size_t zs_atab_cap = 0;
     long long zs_akey[6] = {-1, -1, -1, -1, -1, -1};
-    int zs_two_level = AVR_ZS_TWO_LEVEL;
     int refill_min = 0;       // 0: the default (32 lanes; 20 for a non-emissive NanoVDB walk, 16 for RGB grids, 48 for a <= 2^3 GridMedium majorant)
     int dda_budget = 0;       // 0: by majorant resolution (12 cells up to 16^3, 32 for NanoVDB's 64^3)
     int grid_layout = 1;
@@ -219,7 +294,6 @@ struct avr_context {
     avr::graph::IndexView gidx{};
     float4 *d_gside = nullptr;
     long long gside_cap = 0;
-    bool last_graph = false;        // the last render was avr_graph_render's or avr_graph_render_uniform's
     // the uniform graph's table (avr_graph_render_uniform, avr_graph_uniform_*_device): the device
     // copy of the last one used, under the graph's id as gidx is
     unsigned long long guni_uid = 0;
@@ -235,8 +309,6 @@ struct avr_context {
     avr::graph::AnalyzeAcc *d_aacc = nullptr;
     avr::graph::AnalyzeDetail *d_adetail = nullptr;
     size_t adetail_cap = 0;
-    int last_analyze = 0;           // the last render was avr_graph_analyze's: 1 without, 2 with detail
-    int last_analyze_depth = 0;     // ... and its max_depth (the detail's stride)
 };
 
 namespace {
@@ -268,14 +340,8 @@ void free_paths(avr_context *c) {
     if (c->sh.path) (void)hipFree(c->sh.path);
     if (c->sh.pdfs) (void)hipFree(c->sh.pdfs);
     for (auto &q : c->d_queue) if (q) (void)hipFree(q), q = nullptr;
-    // the k_paths records and camera stage are managed by ensure_records
-    float4 *rec = c->ps.rec, *cam0 = c->ps.cam0, *cam1 = c->ps.cam1, *cam2 = c->ps.cam2, *cam4 = c->ps.cam4;
-    uint4 *cam3 = c->ps.cam3, *cam5 = c->ps.cam5;
-    float *camw = c->ps.camw;
+    // (the k_paths records and camera stage are not in ps: c->set, managed by ensure_records)
     c->ps = {};
-    c->ps.rec = rec;
-    c->ps.cam0 = cam0; c->ps.cam1 = cam1; c->ps.cam2 = cam2; c->ps.cam3 = cam3; c->ps.cam4 = cam4; c->ps.cam5 = cam5;
-    c->ps.camw = camw;
     c->sh = {};
     c->cap = 0;
 }
@@ -290,24 +356,16 @@ void free_pixel_order(avr_context *c) {
 
 // The other set of records, camera buffers and work heads (pass overlap)
 void free_alt(avr_context *c) {
-    for (void *p : {(void *)c->alt.rec, (void *)c->alt.cam0, (void *)c->alt.cam1, (void *)c->alt.cam2, (void *)c->alt.cam3,
-                    (void *)c->alt.cam4, (void *)c->alt.cam5, (void *)c->alt.camw, (void *)c->d_heads_alt})
-        if (p) (void)hipFree(p);
-    c->alt = {};
-    c->d_heads_alt = nullptr;
+    c->alt.free_buffers();
+    c->alt.free_heads();
     c->alt_cap = 0;
 }
 
 void free_records(avr_context *c) {
     // camera records made ahead may still be written: let the side stream finish, and drop them
     if (c->tstream && c->alt_cap) (void)hipStreamSynchronize(c->tstream);
-    c->cam_spec_valid = false;
-    for (void *p : {(void *)c->ps.rec, (void *)c->ps.cam0, (void *)c->ps.cam1, (void *)c->ps.cam2, (void *)c->ps.cam3,
-                    (void *)c->ps.cam4, (void *)c->ps.cam5, (void *)c->ps.camw})
-        if (p) (void)hipFree(p);
-    c->ps.rec = c->ps.cam0 = c->ps.cam1 = c->ps.cam2 = c->ps.cam4 = nullptr;
-    c->ps.cam3 = c->ps.cam5 = nullptr;
-    c->ps.camw = nullptr;
+    c->look.cam_valid = false;
+    c->set.free_buffers();
     c->rec_cap = 0;
     free_alt(c);
 }
@@ -315,12 +373,7 @@ void free_records(avr_context *c) {
 // ... as large as the first set. Without room for it the passes keep the serial chain (no error).
 void ensure_alt(avr_context *c) {
     if (c->alt_cap == c->rec_cap || c->alt_failed_cap == c->rec_cap) return;
-    const size_t n = (size_t)c->rec_cap;
-    if (dalloc(&c->alt.rec, n) == hipSuccess && dalloc(&c->alt.cam0, n) == hipSuccess &&
-        dalloc(&c->alt.cam1, n) == hipSuccess && dalloc(&c->alt.cam2, n) == hipSuccess &&
-        dalloc(&c->alt.cam3, n) == hipSuccess && dalloc(&c->alt.cam4, n) == hipSuccess &&
-        dalloc(&c->alt.cam5, n) == hipSuccess && dalloc(&c->alt.camw, n) == hipSuccess &&
-        dalloc(&c->d_heads_alt, 9) == hipSuccess && hipMemset(c->d_heads_alt, 0xff, 9 * sizeof(int)) == hipSuccess) {
+    if (c->alt.alloc_buffers((size_t)c->rec_cap) == hipSuccess && c->alt.alloc_heads() == hipSuccess) {
         c->alt_cap = c->rec_cap;
         return;
     }
@@ -334,15 +387,22 @@ void ensure_alt(avr_context *c) {
 int ensure_records(avr_context *c, long long n) {
     if (n <= c->rec_cap) return AVR_OK;
     free_records(c);
-    HIP_TRY(dalloc(&c->ps.rec, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam0, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam1, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam2, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam3, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam4, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.cam5, (size_t)n));
-    HIP_TRY(dalloc(&c->ps.camw, (size_t)n));
+    HIP_TRY(c->set.alloc_buffers((size_t)n));
     c->rec_cap = n;
+    return AVR_OK;
+}
+
+// Grow a device buffer to n entries (contents are not kept). drain: queued kernels may still
+// read the old one, so the stream is drained before it is freed.
+template <typename T, typename N>
+int grow(avr_context *c, T **p, N *cap, N n, bool drain = true) {
+    if (n <= *cap) return AVR_OK;
+    if (drain) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(dalloc(p, (size_t)n));
+    *cap = n;
     return AVR_OK;
 }
 
@@ -742,7 +802,7 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
         (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
     }
-    if (dalloc(&c->d_heads, 9) != hipSuccess || hipMemset(c->d_heads, 0xff, 9 * sizeof(int)) != hipSuccess ||
+    if (c->set.alloc_heads() != hipSuccess ||
         hipMemset(c->d_stats, 0, sizeof(unsigned long long) * (avr::kNumStats + 8)) != hipSuccess) {
         (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
@@ -758,28 +818,20 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
             return fail(AVR_ERR_HIP, "device query failed");
         }
         c->num_cus = prop.multiProcessorCount;
-        // slot 32*image + 8*medium(0 grid, 1 vdb, 2 rgb, 3 homogeneous/cloud) + 4*zsobol + 2*emissive + gray; RGB grids
-        // are never gray (their gray slots hold the 4-wavelength kernel)
-#define AVR_KP(em, gr, zs, med, im, fa) avr::k_paths<em, (med == 4 ? false : gr), zs, med, im, fa>
-#define AVR_KP4(zs, med, im, fa)                                                                                      \
-    AVR_KP(false, false, zs, med, im, fa), AVR_KP(false, true, zs, med, im, fa), AVR_KP(true, false, zs, med, im, fa), \
-        AVR_KP(true, true, zs, med, im, fa)
-#define AVR_KP12(med, im, fa) AVR_KP4(0, med, im, fa), AVR_KP4(2, med, im, fa), AVR_KP4(3, med, im, fa)
-#define AVR_KP48(im, fa) AVR_KP12(0, im, fa), AVR_KP12(3, im, fa), AVR_KP12(4, im, fa), AVR_KP12(1, im, fa)
-        void (*kerns[avr_context::kNumPaths])(avr::Params) = {AVR_KP48(false, false), AVR_KP48(true, false),
-                                                              AVR_KP48(false, true), AVR_KP48(true, true)};
-#undef AVR_KP48
-#undef AVR_KP12
-#undef AVR_KP4
-#undef AVR_KP
+#define AVR_KP_ENTRY(em, gr, zs, med, im, fa)                                                    \
+    c->kpaths[avr::kp::slot_of(em, gr, zs, med, im, fa)] = avr::k_paths<em, gr, zs, med, im, fa>; \
+    c->kpaths_name[avr::kp::slot_of(em, gr, zs, med, im, fa)] = AVR_KP_NAME(em, gr, zs, med, im, fa);
+        AVR_KP_ALL(AVR_KP_ENTRY)
+#undef AVR_KP_ENTRY
+        avr::kp::alias_rgb_gray(c->kpaths);
+        avr::kp::alias_rgb_gray(c->kpaths_name);
         for (int k = 0; k < avr_context::kNumPaths; ++k) {
             int blocksPerCU = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kerns[k], 256, 0) != hipSuccess) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, c->kpaths[k], 256, 0) != hipSuccess) {
                 (void)avr_context_destroy(c);
                 return fail(AVR_ERR_HIP, "occupancy query failed");
             }
             c->paths_grid[k] = prop.multiProcessorCount * std::max(1, blocksPerCU);
-            c->kpaths[k] = kerns[k];
         }
     }
     *out = c;
@@ -825,8 +877,7 @@ int avr_set_pass_table_ahead(avr_context *c, int on) {
     AVR_QUIESCE(c);
     if (!c || (on != 0 && on != 1)) return fail(AVR_ERR_ARG, "pass table ahead must be 0 or 1");
     c->ptab_spec = on;
-    c->spec_valid = false;   // (the side stream is idle after the quiesce)
-    c->cam_spec_valid = false;
+    c->look.invalidate();   // (the side stream is idle after the quiesce)
     return AVR_OK;
 }
 
@@ -834,12 +885,11 @@ int avr_set_pass_overlap(avr_context *c, int on) {
     AVR_QUIESCE(c);
     if (!c || (on != 0 && on != 1)) return fail(AVR_ERR_ARG, "pass overlap must be 0 or 1");
     c->pass_overlap = on;
-    c->spec_valid = false;
-    c->cam_spec_valid = false;
+    c->look.invalidate();
     return AVR_OK;
 }
 
-int avr_pass_overlap_active(avr_context *c) { return c && c->last_overlap ? 1 : 0; }
+int avr_pass_overlap_active(avr_context *c) { return c && c->last.overlap ? 1 : 0; }
 
 int avr_set_majorant_occupancy(avr_context *c, int on) {
     AVR_QUIESCE(c);
@@ -875,7 +925,7 @@ int avr_context_destroy(avr_context *c) {
     if (c->film.w_sum) (void)hipFree(c->film.w_sum);
     if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
     if (c->d_counts) (void)hipFree(c->d_counts);
-    if (c->d_heads) (void)hipFree(c->d_heads);
+    c->set.free_heads();
     for (int *b : {c->d_bin_keys, c->d_bin_out, c->d_bin_hist}) if (b) (void)hipFree(b);
     if (c->d_planes) (void)hipFree(c->d_planes);
     if (c->d_occ) (void)hipFree(c->d_occ);
@@ -918,8 +968,7 @@ int avr_set_stream(avr_context *c, void *s) {
     // work built ahead on the side stream is ordered against the stream it was enqueued beside
     AVR_QUIESCE(c);
     if (!c) return fail(AVR_ERR_ARG, "null context");
-    c->spec_valid = false;
-    c->cam_spec_valid = false;
+    c->look.invalidate();
     c->stream = s ? (hipStream_t)s : c->own_stream;
     return AVR_OK;
 }
@@ -1265,7 +1314,7 @@ static int probe_loop(avr_context *c, int n, Setup setup, Restore restore, int s
     // (a probe would wait for the previous one's), restored afterwards
     const int spec0 = c->ptab_spec;
     c->ptab_spec = 0;
-    c->spec_valid = false;
+    c->look.invalidate();
     // two rounds over the candidates, the second in reverse order, each candidate's time the
     // faster of its two probes (one probe each left 1^3 and 2^3 of fast mode to noise)
     std::vector<float> tmin(n, -1.f);
@@ -1651,7 +1700,7 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     free_pixel_order(c);   // an order is for one film resolution
     if (c->d_aacc) (void)hipFree(c->d_aacc);   // the analysis' per-pixel sums go with the film
     c->d_aacc = nullptr;
-    c->last_analyze = 0;
+    c->last.analyze = 0;
     c->film = {};
     c->film.width = width;
     c->film.height = height;
@@ -1857,572 +1906,11 @@ static int fold_stats(avr_context *c) {
     return AVR_OK;
 }
 
-// The ZSobol pass table of sample indices [base, base + S): its entries hold the digits above
-// the lowest plo bits, where the pass's indices differ
-static int pass_plo(long long base, int S) {
-    int plo = 0;
-    while ((base >> plo) != ((base + S - 1) >> plo)) ++plo;
-    return plo;
-}
-constexpr int kPtabKey = 8;
-// what a built table depends on (a table built ahead is used only when the pass's key equals it)
-static void ptab_key(const avr_context *c, const avr::smp::ZSobolParams &zs, long long base, int plo, long long *key) {
-    const long long k[kPtabKey] = {base, plo, (long long)zs.log2spp, (long long)zs.seed,
-                                   (long long)c->film.width * 65536 + c->film.height, c->zs_pdims,
-                                   (long long)(uintptr_t)zs.upper, zs.dmax};
-    for (int i = 0; i < kPtabKey; ++i) key[i] = k[i];
-}
-// Build the pass table (and the camera stage's compact copy) of [base, base + S) into buffer buf
-// on stream s, with its level-A table when the two-level build applies. No room for a buffer:
-// d_zs_ptab[buf] stays null (the pixel table / every digit per call serve the pass).
-static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParams &zs, long long base, int plo, int buf,
-                      bool two_level) {
-    const long long P = (long long)c->film.width * c->film.height;
-    const size_t prow = (size_t)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
-    const size_t need_e = prow * (size_t)c->zs_pdims;
-    // the same headroom policy as the fat / bricked density copies: allocate only with >= 8 GiB
-    // of HBM to spare
-    auto fits = [](size_t bytes) {
-        size_t freeB = 0, totalB = 0;
-        return hipMemGetInfo(&freeB, &totalB) == hipSuccess && bytes + (8ull << 30) < freeB;
-    };
-    if (need_e > c->zs_ptab_cap[buf]) {
-        if (c->d_zs_ptab[buf]) (void)hipFree(c->d_zs_ptab[buf]);
-        c->d_zs_ptab[buf] = nullptr;
-        c->zs_ptab_cap[buf] = 0;
-        if (!fits(need_e * sizeof(uint64_t)) ||
-            hipMalloc((void **)&c->d_zs_ptab[buf], need_e * sizeof(uint64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_zs_ptab[buf] = nullptr;
-            return AVR_OK;
-        }
-        c->zs_ptab_cap[buf] = need_e;
-    }
-    // two-level build: the plo + 2 table is shared by the four passes whose indices agree above
-    // plo + 2 bits; each pass then derives its own from it (not when the caller's passes stride
-    // past each other's group: a sample shard's rank would rebuild it for every pass)
-    const uint64_t *atab = nullptr;
-    if (two_level && c->zs_two_level && plo + 2 <= zs.log2spp) {
-        if (need_e > c->zs_atab_cap) {
-            if (c->d_zs_atab) (void)hipFree(c->d_zs_atab);
-            c->d_zs_atab = nullptr;
-            c->zs_atab_cap = 0;
-            for (long long &k : c->zs_akey) k = -1;
-            if (!fits(need_e * sizeof(uint64_t)) ||
-                hipMalloc((void **)&c->d_zs_atab, need_e * sizeof(uint64_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                c->d_zs_atab = nullptr;   // no room: one-level build
-            } else {
-                c->zs_atab_cap = need_e;
-            }
-        }
-        if (c->d_zs_atab) {
-            const long long key[6] = {base >> (plo + 2), plo, (long long)zs.log2spp, zs.seed,
-                                      (long long)c->film.width * 65536 + c->film.height, c->zs_pdims};
-            bool same = true;
-            for (int k = 0; k < 6; ++k) same = same && key[k] == c->zs_akey[k];
-            if (!same) {
-                hipLaunchKernelGGL(avr::k_zsobol_pass_table,
-                                   dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s, zs,
-                                   c->film.width, c->film.height, c->zs_pdims, plo + 2, (base >> (plo + 2)) << (plo + 2),
-                                   c->d_zs_atab, (const uint64_t *)nullptr, avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)),
-                                   avr::fastdiv_make((uint32_t)c->film.width), (uint64_t *)nullptr);
-                HIP_TRY(hipGetLastError());
-                for (int k = 0; k < 6; ++k) c->zs_akey[k] = key[k];
-            }
-            atab = c->d_zs_atab;
-        }
-    }
-    // the camera stage's six entries per pixel (dimensions 0, 1, 6..9) also as a compact
-    // scanline-ordered copy (48 B per pixel), when the table holds them
-    const size_t need_c = c->zs_pdims >= 10 ? 6 * (size_t)P : 0;
-    if (need_c > c->zs_ctab_cap[buf]) {
-        if (c->d_zs_ctab[buf]) (void)hipFree(c->d_zs_ctab[buf]);
-        c->d_zs_ctab[buf] = nullptr;
-        c->zs_ctab_cap[buf] = 0;
-        if (hipMalloc((void **)&c->d_zs_ctab[buf], need_c * sizeof(uint64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_zs_ctab[buf] = nullptr;   // no room: the camera reads the rows
-        } else {
-            c->zs_ctab_cap[buf] = need_c;
-        }
-    }
-    uint64_t *ctab = need_c ? c->d_zs_ctab[buf] : nullptr;
-    hipLaunchKernelGGL(avr::k_zsobol_pass_table, dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s,
-                       zs, c->film.width, c->film.height, c->zs_pdims, plo, base, c->d_zs_ptab[buf], atab,
-                       avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.width), ctab);
-    HIP_TRY(hipGetLastError());
-    return AVR_OK;
-}
+}  // extern "C"
 
-// Pass overlap: whether k_paths is held to four blocks per CU while a camera stage runs beside
-// it, and the dynamic LDS that keeps a fifth block off a CU: 4 x (k_paths' 31.5 KB + pad) + the
-// camera block's 28.3 KB fit the 160 KiB, 5 x (31.5 KB + pad) do not (tests/test_overlap_resources.py)
-#ifndef AVR_OVERLAP_HOLD
-#define AVR_OVERLAP_HOLD 1
-#endif
-constexpr int kOverlapLdsPad = 1536;
-// next free pool event (folds first when the pool is full)
-static int next_event(avr_context *c, int *idx, hipStream_t s = nullptr) {
-    if (c->ev_used >= 512) {
-        int rc = fold_stats(c);
-        if (rc) return rc;
-    }
-    if (c->ev_used == c->evpool.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->evpool.push_back(e);
-    }
-    *idx = (int)c->ev_used++;
-    HIP_TRY(hipEventRecord(c->evpool[*idx], s ? s : c->stream));
-    return AVR_OK;
-}
-#define EV_MARK(var)                      \
-    int var;                              \
-    do {                                  \
-        int rc_ = next_event(c, &var);    \
-        if (rc_) return rc_;              \
-    } while (0)
+#include "avr_render.hip"
 
-// The pixel sampler of a render call (avr_render, avr_graph_render): the ZSobol range checks,
-// the device selected, and the ZSobol pixel table rebuilt when the sampler or film changed.
-static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobolParams *out) {
-    avr::smp::ZSobolParams zs{};
-    if (c->sampler_kind == 1) {
-        // ZSobolSampler indexes (Morton(pixel) << log2(spp)) | sampleIndex: indices must stay
-        // below the sampler's samplesPerPixel and the Sobol' index below 2^32
-        if (spp_end > c->sampler_spp) return fail(AVR_ERR_ARG, "zsobol: sample index beyond samplesPerPixel");
-        zs = avr::smp::zsobol_params(c->sampler_spp, c->film.width, c->film.height, seed);
-        // SobolSample takes indices below 2^SobolMatrixSize = 2^52 (lowdiscrepancy.h:170)
-        if (2 * zs.nBase4Digits - (zs.log2spp & 1) > 52)
-            return fail(AVR_ERR_ARG, "zsobol: resolution x spp beyond the 2^52 Sobol' index range");
-        // Morton(pixel) and the pixel-only digits (zsobol_upper, the pixel table) are 32-bit
-        const int res = (int)avr::smp::round_up_pow2((uint32_t)std::max(c->film.width, c->film.height));
-        if (2 * avr::smp::ilog2((uint32_t)res) > 32)
-            return fail(AVR_ERR_ARG, "zsobol: film resolution beyond 65536 (Morton(pixel) exceeds 32 bits)");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->sampler_kind == 1) {
-        // The digits of GetSampleIndex above log2(spp) depend on (pixel, dimension) only:
-        // tabulate them once per film/sampler (k_zsobol_table), so each sampler call computes
-        // the log2(spp)/2 sample digits plus one load instead of all nBase4Digits
-        const int key[3] = {c->sampler_spp, c->film.width, c->film.height};
-        if (c->zs_key[0] != key[0] || c->zs_key[1] != key[1] || c->zs_key[2] != key[2]) {
-            // a table built ahead reads the pixel table: let it finish, and drop it
-            if (c->tstream) HIP_TRY(hipStreamSynchronize(c->tstream));
-            c->spec_valid = false;
-            c->cam_spec_valid = false;
-            if (c->d_zs_table) (void)hipFree(c->d_zs_table);
-            c->d_zs_table = nullptr;
-            for (int k = 0; k < 3; ++k) c->zs_key[k] = key[k];
-            if (c->zs_dims > 0) {
-                const size_t rows =
-                    (size_t)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
-                if (hipMalloc((void **)&c->d_zs_table, rows * c->zs_dims * sizeof(uint32_t)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->d_zs_table = nullptr;   // no room: every call computes all digits
-                } else {
-                    EV_MARK(t0);
-                    hipLaunchKernelGGL(avr::k_zsobol_table, dim3(blocks_for((long long)c->film.width * c->film.height *
-                                                                            c->zs_dims, 256, 256 * 64)),
-                                       dim3(256), 0, c->stream, zs, c->film.width, c->film.height, c->zs_dims,
-                                       c->d_zs_table);
-                    HIP_TRY(hipGetLastError());
-                    EV_MARK(t1);
-                    c->timed.push_back({t0, t1, &avr_stats::ms_setup, false});
-                }
-            }
-        }
-        zs.upper = c->d_zs_table;
-        zs.dmax = c->d_zs_table ? c->zs_dims : 0;
-    }
-    *out = zs;
-    return AVR_OK;
-}
-
-int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, int max_depth) {
-    if (!c) return fail(AVR_ERR_ARG, "null context");
-    if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
-    if (spp_begin < 0 || spp_end < spp_begin || max_depth < 0) return fail(AVR_ERR_ARG, "bad sample range");
-    if (c->image_lights_ready < c->n_image_lights) return fail(AVR_ERR_STATE, "image light without avr_light_image");
-    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
-        return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
-    // (padding bytes zeroed too, here and in the Params below: a pass takes camera records made
-    // ahead only when its camera stage's arguments equal theirs byte for byte)
-    avr::smp::ZSobolParams zs;
-    std::memset(&zs, 0, sizeof zs);
-    {
-        avr::smp::ZSobolParams z{};
-        int rc = render_sampler(c, spp_end, seed, &z);
-        if (rc) return rc;
-        zs.log2spp = z.log2spp; zs.nBase4Digits = z.nBase4Digits; zs.seed = z.seed;
-        zs.upper = z.upper; zs.dmax = z.dmax;
-        zs.ptab = z.ptab; zs.pdims = z.pdims; zs.plo = z.plo; zs.ctab = z.ctab;
-    }
-    const long long P = (long long)c->film.width * c->film.height;
-    if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
-    // k_paths runs every medium type with every light type: GridMedium, RGBGridMedium and
-    // the single-segment Homogeneous/CloudMedium keep the majorant in LDS (at most 4096
-    // cells = pbrt's 16^3; larger grids take the wavefront kernels), NanoVDBMedium reads
-    // its 64^3 majorant through L2
-    const int mcells = c->med.mres[0] * c->med.mres[1] * c->med.mres[2];
-    const bool persistent = c->kernel_mode == 0 &&
-                            (((c->med.type != 3) && mcells <= 4096) || c->med.type == 3) &&
-                            c->med.mres[0] <= 255 && c->med.mres[1] <= 255 && c->med.mres[2] <= 255;
-    const long long maxp = c->max_paths_set ? c->max_paths : (persistent ? (64ll << 20) : c->max_paths);
-    const long long Smax = std::max<long long>(1, maxp / P);
-    const long long need = P * std::min<long long>(Smax, std::max(1, spp_end - spp_begin));
-    int rc = persistent ? ensure_records(c, need) : ensure_paths(c, need);
-    if (rc) return rc;
-    // Pass overlap: only the parked k_paths instantiations (gray non-emissive GridMedium without
-    // image lights) leave a block of the camera stage room beside four of their own on a CU;
-    // only on the context's own stream (the side stream is ordered against it by events), and
-    // only behind the ZSobol pass table built ahead
-    const bool overlap_ok = persistent && c->pass_overlap && c->ptab_spec && c->sampler_kind == 1 &&
-                            c->stream == c->own_stream && c->gray && c->med.type == 0 && !c->med.emissive &&
-                            c->n_image_lights == 0 && !c->lights.power;
-    if (overlap_ok) ensure_alt(c);
-    EV_MARK(evStart);
-    // the stride between consecutive calls' first sample indices (S for pbrt's pass loop and the
-    // one-GPU bench, N x S for a rank of an N-GPU sample shard): where the pass after this call's
-    // last one is expected to start, for the pass table built ahead
-    const long long call_stride = (c->prev_call_begin >= 0 && spp_begin > c->prev_call_begin) ? spp_begin - c->prev_call_begin : 0;
-    c->prev_call_begin = spp_begin;
-    for (long long base = spp_begin; base < spp_end; base += Smax) {
-        const int S = (int)std::min<long long>(Smax, spp_end - base);
-        bool spec_next = false;   // build the next pass's ZSobol table ahead (ptab_spec)
-        avr::smp::ZSobolParams spec_zs;
-        std::memset(&spec_zs, 0, sizeof spec_zs);
-        avr::Params p;
-        std::memset(&p, 0, sizeof p);
-        p.med = c->med;
-        p.lights = c->lights;
-        p.cam = c->cam;
-        p.film = c->film;
-        p.film.filter_type = c->filter_type;
-        p.film.gauss = c->ftab;
-        p.sampler_kind = c->sampler_kind;
-        p.zs = zs;
-        p.ps = c->ps;
-        p.sh = c->sh;
-        p.max_depth = max_depth;
-        p.seed = seed;
-        p.pass_pixels = (int)P;
-        p.div_pixels = avr::fastdiv_make((uint32_t)P);
-        p.div_width = avr::fastdiv_make((uint32_t)c->film.width);
-        p.pass_samples = S;
-        p.sample_base = (int)base;
-        p.stats = c->d_stats;
-        const long long n0 = P * S;
-        c->last_persistent = persistent;
-        c->last_fast = persistent && c->render_mode == 1;
-        c->last_graph = false;
-        c->last_analyze = 0;
-        if (persistent) {
-            // PCG32 Advance(s*65536) as an affine map state' = A*state + inc*H (rng.h:132-146:
-            // every step is linear in inc, so H = accPlus computed with inc = 1).
-            if (S > c->advance_cap) {
-                if (c->d_advance) (void)hipFree(c->d_advance);
-                HIP_TRY(dalloc(&c->d_advance, 2 * (size_t)S));
-                c->advance_cap = S;
-            }
-            if (c->sampler_kind == 0) {   // read by the IndependentSampler's camera stage only
-                hipLaunchKernelGGL(avr::k_advance, dim3((S + 255) / 256), dim3(256), 0, c->stream, c->d_advance,
-                                   (long long)base, S);
-                HIP_TRY(hipGetLastError());
-            }
-            p.advance = c->d_advance;
-            walk_schedule(c, c->refill_min, c->dda_budget, &p.refill_min, &p.dda_budget);   // defaults: measured optima
-            // zeroed by the camera stage (k_paths_camera), which must run first on this stream: it
-            // stamps pass_gen into heads[8], and a k_paths launched without it renders nothing and
-            // makes the stats readback fail (stats[7])
-            p.heads = c->d_heads;
-            p.pass_gen = ++c->pass_gen & 0x7fffffff;
-            bool cam_taken = false, cam_next = false;
-            avr::Params pcam{};   // the camera stage's arguments of this pass
-            void (*kcam_next)(avr::Params) = nullptr;
-            int cgrid_next = 0;
-            // the camera stage: one lane per sample (k_paths_camera)
-            {
-                const int sv = c->sampler_kind == 0 ? 0 : (avr::smp::zsobol_wide(p.zs) ? 2 : 1);
-                p.pix_order = c->d_pix_order;
-                // ZSobol quads: 4-aligned sample ranges, at most 8 lower base-4 digits
-                p.cam_quad = (base % 4 == 0 && S % 4 == 0 && p.zs.log2spp <= 16) ? 1 : 0;
-                using KC = void (*)(avr::Params);
-                static const KC kcam[2][3] = {
-                    {avr::k_paths_camera<0, false>, avr::k_paths_camera<2, false>, avr::k_paths_camera<3, false>},
-                    {avr::k_paths_camera<0, true>, avr::k_paths_camera<2, true>, avr::k_paths_camera<3, true>}};
-                EV_MARK(ec);
-                // rows = Morton(w-1, h-1) + 1 (up to ~4x the pixels of a non-square film): the
-                // table kernel indexes entries with 32 bits
-                const long long prow = (long long)avr::smp::encode_morton2((uint32_t)c->film.width - 1,
-                                                                           (uint32_t)c->film.height - 1) + 1;
-                if (c->sampler_kind == 1 && c->zs_pdims > 0 &&
-                    (long long)c->film.width * c->film.height * c->zs_pdims < (1ll << 31) &&
-                    prow * c->zs_pdims < (1ll << 31)) {
-                    // ZSobol pass table: the digits of GetSampleIndex that the pass's sample
-                    // indices [base, base + S) share (those above their lowest differing bits),
-                    // for the first zs_pdims dimensions; the camera stage and k_paths then
-                    // evaluate only the digits below (two MixBits at 64 indices per pass)
-                    const int plo = pass_plo(base, S);
-                    long long key[kPtabKey];
-                    ptab_key(c, zs, base, plo, key);
-                    int buf = -1;
-                    bool cam_ahead = false;   // tstream made (or is making) camera records beside that table
-                    if (c->spec_valid) {
-                        // the table the previous pass built ahead on the side stream (ptab_build's
-                        // caller below): this stream waits for it, whether it is used or not, so
-                        // no build of this pass overlaps it
-                        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tab, 0));
-                        bool same = true;
-                        for (int k = 0; k < kPtabKey; ++k) same = same && key[k] == c->spec_key[k];
-                        if (same) buf = c->spec_buf;
-                        cam_ahead = same && c->cam_spec_valid && c->spec_gen == c->cfg_gen && overlap_ok;
-                        c->spec_valid = false;
-                        c->cam_spec_valid = false;
-                    }
-                    if (buf < 0) {
-                        buf = 1 - c->tab_buf;
-                        int rc2 = ptab_build(c, c->stream, zs, base, plo, buf, call_stride == 0 || call_stride == S);
-                        if (rc2) return rc2;
-                        if (!c->d_zs_ptab[buf]) buf = -1;
-                    }
-                    if (buf >= 0) {
-                        c->tab_buf = buf;
-                        p.zs.ptab = c->d_zs_ptab[buf];
-                        p.zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[buf] : nullptr;
-                        p.zs.pdims = c->zs_pdims;
-                        p.zs.plo = plo;
-                        spec_next = c->ptab_spec != 0;
-                        spec_zs = zs;
-                        if (cam_ahead) {
-                            // the records made ahead are this pass's when the camera stage would be
-                            // launched with the very arguments they were made with
-                            avr::Params t = p;
-                            t.ps.rec = c->alt.rec;
-                            t.ps.cam0 = c->alt.cam0; t.ps.cam1 = c->alt.cam1; t.ps.cam2 = c->alt.cam2;
-                            t.ps.cam3 = c->alt.cam3; t.ps.cam4 = c->alt.cam4; t.ps.cam5 = c->alt.cam5;
-                            t.ps.camw = c->alt.camw;
-                            t.heads = c->d_heads_alt;
-                            if (std::memcmp(&t, &c->spec_params, sizeof t) == 0) {
-                                std::swap(c->ps.rec, c->alt.rec);
-                                std::swap(c->ps.cam0, c->alt.cam0); std::swap(c->ps.cam1, c->alt.cam1);
-                                std::swap(c->ps.cam2, c->alt.cam2); std::swap(c->ps.cam3, c->alt.cam3);
-                                std::swap(c->ps.cam4, c->alt.cam4); std::swap(c->ps.cam5, c->alt.cam5);
-                                std::swap(c->ps.camw, c->alt.camw);
-                                std::swap(c->d_heads, c->d_heads_alt);
-                                p = t;
-                                cam_taken = true;
-                            }
-                        }
-                    }
-                }
-                // 16384 blocks (64 per CU, ~14 samples per thread at the bench's pass): the measured optimum
-                // between one round of resident blocks and one sample per thread
-                // (profiles/r06_ab_camera_grid.json)
-                const int cgrid = blocks_for(n0, 256, 256 * 64);
-                pcam = p;
-                if (!cam_taken) {
-                    hipLaunchKernelGGL(kcam[c->render_mode ? 1 : 0][sv], dim3(cgrid), dim3(256), 0, c->stream, p);
-                    HIP_TRY(hipGetLastError());
-                    EV_MARK(ec1);
-                    c->timed.push_back({ec, ec1, &avr_stats::ms_camera, false});
-                }
-                if (spec_next) HIP_TRY(hipEventRecord(c->ev_cam, c->stream));
-                c->last_overlap = cam_taken;
-                // the next pass's camera stage follows its table on the side stream
-                cam_next = spec_next && overlap_ok && c->alt_cap >= n0 && c->alt_cap == c->rec_cap;
-                if (cam_next) {
-                    kcam_next = kcam[c->render_mode ? 1 : 0][sv];
-                    cgrid_next = cgrid;
-                }
-            }
-            EV_MARK(e0);
-            // gray medium: sigma_a and sigma_s tables constant over all 471 wavelengths
-            const int mk = c->med.type == 3 ? 1 : (c->med.type == 4 ? 2 : (c->med.type == 1 || c->med.type == 2 ? 3 : 0));
-            const int sv = c->sampler_kind == 0 ? 0 : (avr::smp::zsobol_wide(p.zs) ? 2 : 1);
-            // the kImage instantiation also carries the power light sampler's pick (light_pick)
-            const bool general_lights = c->n_image_lights > 0 || c->lights.power;
-            const int kv = ((((c->render_mode * 2 + (general_lights ? 1 : 0)) * 4 + mk) * 3 + sv) * 2 +
-                            (c->med.emissive ? 1 : 0)) * 2 + (c->gray && c->med.type != 4 ? 1 : 0);
-            // With a camera stage beside it, k_paths is launched as four blocks per CU (the grid,
-            // and kOverlapLdsPad bytes of dynamic LDS nobody uses so that a fifth block does not
-            // fit a CU): the fifth wave slot of every SIMD and the LDS left take a camera block
-            const bool hold = cam_next && AVR_OVERLAP_HOLD != 0 && c->paths_grid[kv] > 4 * c->num_cus;
-            hipLaunchKernelGGL(c->kpaths[kv], dim3(hold ? 4 * c->num_cus : c->paths_grid[kv]), dim3(256),
-                               hold ? kOverlapLdsPad : 0, c->stream, p);
-            HIP_TRY(hipGetLastError());
-            {
-                const int kmed = c->med.type == 3 ? 3 : (c->med.type == 4 ? 4 : (c->med.type == 1 || c->med.type == 2 ? 1 : 0));
-                std::snprintf(c->last_kpaths, sizeof(c->last_kpaths), "k_paths<%s, %s, %d, %d, %s, %s>",
-                              c->med.emissive ? "true" : "false", (c->gray && c->med.type != 4) ? "true" : "false",
-                              sv == 0 ? 0 : (sv == 1 ? 2 : 3), kmed, general_lights ? "true" : "false",
-                              c->render_mode ? "true" : "false");
-            }
-            EV_MARK(e1);
-            p.rec_mode = 1;   // k_film reads the records k_paths wrote (in slot order)
-            p.pix_slot = c->d_pix_slot;
-            p.fast = c->render_mode;
-            // fast mode: the wavelength pdfs with the hardware exp (its wavelengths are the hardware log's)
-            using KF = void (*)(avr::Params);
-            static const KF kfilm[2][2] = {{avr::k_film<false, false>, avr::k_film<true, false>},
-                                           {avr::k_film<false, true>, avr::k_film<true, true>}};
-            hipLaunchKernelGGL(kfilm[c->render_mode ? 1 : 0][c->film.nbuckets > 0 ? 1 : 0], dim3(blocks_for(P)), dim3(256), avr::film_lds_bytes(c->film.nbuckets),
-                               c->stream, p);
-            HIP_TRY(hipGetLastError());
-            EV_MARK(e2);
-            c->timed.push_back({e0, e1, &avr_stats::ms_medium, true});
-            c->timed.push_back({e1, e2, &avr_stats::ms_film, false});
-            if (spec_next) {
-                // the NEXT pass's table (sample indices [base + S, base + 2S): the next loop
-                // iteration's, or the next avr_render call's when the caller walks the indices in
-                // order) built ahead into the other buffer on the low-priority side stream: it
-                // waits for this pass's camera stage (the last reader of that buffer, k_paths of
-                // the previous pass, is then done too) and is dispatched as k_paths' blocks retire
-                // in its drain, instead of in front of the next camera stage. A pass whose key
-                // differs builds its own table (and this one is discarded).
-                const bool in_call = base + Smax < spp_end || call_stride == 0;
-                const long long nb = in_call ? base + S : spp_begin + call_stride;
-                const int nplo = pass_plo(nb, S);
-                HIP_TRY(hipStreamWaitEvent(c->tstream, c->ev_cam, 0));
-                const int tb = 1 - c->tab_buf;
-                // (not timed: events around it would measure its wait for the drain too)
-                { int rc2 = ptab_build(c, c->tstream, spec_zs, nb, nplo, tb, in_call || call_stride == S); if (rc2) return rc2; }
-                bool cam_spec = false;
-                if (cam_next && c->d_zs_ptab[tb]) {
-                    // ... and that pass's camera stage behind it, into the other set: its last
-                    // readers, the previous pass's k_paths and k_film, came before ev_cam on the
-                    // main stream. The pass is assumed to have this one's size and arguments;
-                    // the pass itself checks that (spec_params).
-                    avr::Params q = pcam;
-                    q.sample_base = (int)nb;
-                    q.pass_gen = (c->pass_gen + 1) & 0x7fffffff;
-                    q.cam_quad = (nb % 4 == 0 && S % 4 == 0 && q.zs.log2spp <= 16) ? 1 : 0;
-                    q.zs = spec_zs;
-                    q.zs.ptab = c->d_zs_ptab[tb];
-                    q.zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[tb] : nullptr;
-                    q.zs.pdims = c->zs_pdims;
-                    q.zs.plo = nplo;
-                    q.ps.rec = c->alt.rec;
-                    q.ps.cam0 = c->alt.cam0; q.ps.cam1 = c->alt.cam1; q.ps.cam2 = c->alt.cam2;
-                    q.ps.cam3 = c->alt.cam3; q.ps.cam4 = c->alt.cam4; q.ps.cam5 = c->alt.cam5;
-                    q.ps.camw = c->alt.camw;
-                    q.heads = c->d_heads_alt;
-                    int sc0, sc1;
-                    { int rc2 = next_event(c, &sc0, c->tstream); if (rc2) return rc2; }
-                    hipLaunchKernelGGL(kcam_next, dim3(cgrid_next), dim3(256), 0, c->tstream, q);
-                    HIP_TRY(hipGetLastError());
-                    { int rc2 = next_event(c, &sc1, c->tstream); if (rc2) return rc2; }
-                    c->timed.push_back({sc0, sc1, &avr_stats::ms_camera, false});
-                    c->spec_params = q;
-                    c->spec_gen = c->cfg_gen;
-                    cam_spec = true;
-                }
-                HIP_TRY(hipEventRecord(c->ev_tab, c->tstream));
-                if (c->d_zs_ptab[tb]) {
-                    ptab_key(c, spec_zs, nb, nplo, c->spec_key);
-                    c->spec_buf = tb;
-                    c->spec_valid = true;
-                    c->cam_spec_valid = cam_spec;
-                }
-            }
-            c->last_base = (int)base;
-            c->last_S = S;
-            c->last_order_gen = c->order_gen;
-            continue;
-        }
-        EV_MARK(c0);
-        if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
-        HIP_TRY(hipGetLastError());
-        EV_MARK(c1);
-        c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});
-        c->h_count[0] = (int)n0;
-        HIP_TRY(hipMemcpyAsync(c->d_counts, c->h_count, sizeof(int), hipMemcpyHostToDevice, c->stream));
-        int cur = 0;
-        long long count = n0;
-        bool first = true;
-        while (count > 0) {
-            const int nxt = cur ^ 1;
-            HIP_TRY(hipMemsetAsync(c->d_counts + nxt, 0, sizeof(int), c->stream));
-            HIP_TRY(hipMemsetAsync(c->d_counts + 2, 0, sizeof(int), c->stream));
-            p.queue_in = first ? nullptr : c->d_queue[cur];
-            p.count_in = c->d_counts + cur;
-            const int nbins = 8 * c->med.mres[0] * c->med.mres[1] * c->med.mres[2];
-            const bool bin = c->ray_binning && nbins <= 8 * 4096;
-            if (bin && c->bin_cap < n0) {
-                for (int **b : {&c->d_bin_keys, &c->d_bin_out}) {
-                    if (*b) (void)hipFree(*b);
-                    HIP_TRY(dalloc(b, (size_t)n0));
-                }
-                if (!c->d_bin_hist) HIP_TRY(dalloc(&c->d_bin_hist, (size_t)8 * 4096));
-                c->bin_cap = n0;
-            }
-            auto bin_queue = [&](const int *queue, const int *count_p, const float4 *o, const float4 *d) -> int {
-                HIP_TRY(hipMemsetAsync(c->d_bin_hist, 0, nbins * sizeof(int), c->stream));
-                const int nbk = blocks_for(count);
-                hipLaunchKernelGGL(avr::k_bin_count, dim3(nbk), dim3(256), 0, c->stream, c->med, queue, count_p, o, d,
-                                   c->d_bin_keys, c->d_bin_hist);
-                hipLaunchKernelGGL(avr::k_bin_scan, dim3(1), dim3(1024), 0, c->stream, c->d_bin_hist, nbins);
-                hipLaunchKernelGGL(avr::k_bin_scatter, dim3(nbk), dim3(256), 0, c->stream, queue, count_p,
-                                   c->d_bin_keys, c->d_bin_hist, c->d_bin_out);
-                HIP_TRY(hipGetLastError());
-                return AVR_OK;
-            };
-            // camera rays keep their pixel order (already coherent); later depths are binned
-            if (bin && !first) {
-                EV_MARK(s0);
-                int rc = bin_queue(c->d_queue[cur], c->d_counts + cur, c->ps.o, c->ps.d);
-                if (rc) return rc;
-                EV_MARK(s1);
-                c->timed.push_back({s0, s1, &avr_stats::ms_binning, false});
-                HIP_TRY(hipMemcpyAsync(c->d_queue[cur], c->d_bin_out, (size_t)count * sizeof(int),
-                                       hipMemcpyDeviceToDevice, c->stream));
-            }
-            p.queue_out = c->d_queue[nxt];
-            p.count_out = c->d_counts + nxt;
-            p.shadow_count = c->d_counts + 2;
-            const int nb = blocks_for(count);
-            EV_MARK(m0);
-            if (c->sampler_kind) hipLaunchKernelGGL(avr::k_medium<true>, dim3(nb), dim3(256), 0, c->stream, p);
-            else hipLaunchKernelGGL(avr::k_medium<false>, dim3(nb), dim3(256), 0, c->stream, p);
-            HIP_TRY(hipGetLastError());
-            EV_MARK(m1);
-            p.sh_perm = nullptr;
-            if (bin) {
-                // the shadow rays k_medium just pushed, binned the same way (read through sh_perm)
-                EV_MARK(s2);
-                int rc = bin_queue(nullptr, c->d_counts + 2, c->sh.o, c->sh.d);
-                if (rc) return rc;
-                EV_MARK(s3);
-                c->timed.push_back({s2, s3, &avr_stats::ms_binning, false});
-                p.sh_perm = c->d_bin_out;
-            }
-            EV_MARK(m15);
-            hipLaunchKernelGGL(avr::k_shadow, dim3(nb), dim3(256), 0, c->stream, p);
-            HIP_TRY(hipGetLastError());
-            EV_MARK(m2);
-            c->timed.push_back({m0, m1, &avr_stats::ms_medium, true});
-            c->timed.push_back({m15, m2, &avr_stats::ms_shadow, false});
-            // the queue length decides the next launch: the wavefront organisation syncs here
-            HIP_TRY(hipMemcpyAsync(c->h_count, c->d_counts + nxt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            count = c->h_count[0];
-            cur = nxt;
-            first = false;
-        }
-        EV_MARK(f0);
-        hipLaunchKernelGGL((c->film.nbuckets > 0 ? avr::k_film<true> : avr::k_film<false>), dim3(blocks_for(P)), dim3(256), avr::film_lds_bytes(c->film.nbuckets), c->stream, p);
-        HIP_TRY(hipGetLastError());
-        EV_MARK(f1);
-        c->timed.push_back({f0, f1, &avr_stats::ms_film, false});
-        c->last_base = (int)base;
-        c->last_S = S;
-    }
-    EV_MARK(evEnd);
-    c->timed.push_back({evStart, evEnd, &avr_stats::ms_total, false});
-    return AVR_OK;
-}
+extern "C" {
 
 int avr_transmittance_device(avr_context *c, long long n, const float *p0, const float *p1, const float *lambda,
                              float *tr) {
@@ -2634,22 +2122,22 @@ int avr_last_pass_samples(avr_context *c, float *L, float *lambda, float *pdf, l
                           int *ns) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film || !L || !lambda || !pdf || !first || !ns) return fail(AVR_ERR_ARG, "null arg");
-    const long long n = (long long)c->film.width * c->film.height * c->last_S;
+    const long long n = (long long)c->film.width * c->film.height * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
-    if (n > 0 && c->last_persistent && c->last_order_gen != c->order_gen)
+    if (n > 0 && c->last.persistent && c->last.order_gen != c->order_gen)
         return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
-    if (n > 0 && c->last_persistent) {
+    if (n > 0 && c->last.persistent) {
         // k_paths' records (L), its camera stage's wavelengths and their pdfs as k_film evaluates them
-        HIP_TRY(hipMemcpy(L, c->ps.rec, n * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(lambda, c->ps.cam2, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(L, c->set.rec, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(lambda, c->set.cam2, n * sizeof(float4), hipMemcpyDeviceToHost));
         {
             avr::DevFilm f = c->film;
-            hipLaunchKernelGGL(avr::k_lambda_pdfs, dim3(blocks_for(n)), dim3(256), 0, c->stream, f, c->ps.cam2, c->ps.cam4, n,
-                               c->last_fast ? 1 : 0);
+            hipLaunchKernelGGL(avr::k_lambda_pdfs, dim3(blocks_for(n)), dim3(256), 0, c->stream, f, c->set.cam2, c->set.cam4, n,
+                               c->last.fast ? 1 : 0);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        HIP_TRY(hipMemcpy(pdf, c->ps.cam4, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pdf, c->set.cam4, n * sizeof(float4), hipMemcpyDeviceToHost));
         if (!c->h_pix_slot.empty()) {   // slot order -> pixel order
             const long long np = (long long)c->film.width * c->film.height;
             std::vector<float> tmp(4 * (size_t)np);
@@ -2665,29 +2153,29 @@ int avr_last_pass_samples(avr_context *c, float *L, float *lambda, float *pdf, l
         HIP_TRY(hipMemcpy(lambda, c->ps.lambda, n * sizeof(float4), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(pdf, c->ps.pdf, n * sizeof(float4), hipMemcpyDeviceToHost));
     }
-    *first = c->last_base;
-    *ns = c->last_S;
+    *first = c->last.base;
+    *ns = c->last.S;
     return AVR_OK;
 }
 
 int avr_last_kernel(avr_context *c, char *buf, int cap) {
     if (!c || !buf || cap <= 0) return fail(AVR_ERR_ARG, "null arg");
-    std::snprintf(buf, (size_t)cap, "%s", c->last_kpaths);
+    std::snprintf(buf, (size_t)cap, "%s", c->last.variant >= 0 ? c->kpaths_name[c->last.variant] : "");
     return AVR_OK;
 }
 
 int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film || !w) return fail(AVR_ERR_ARG, "null arg");
-    const long long n = (long long)c->film.width * c->film.height * c->last_S;
+    const long long n = (long long)c->film.width * c->film.height * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
-    if (n > 0 && c->last_persistent && c->filter_type != 0 && c->last_order_gen != c->order_gen)
+    if (n > 0 && c->last.persistent && c->filter_type != 0 && c->last.order_gen != c->order_gen)
         return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
     if (c->filter_type == 0) {
         for (long long i = 0; i < n; ++i) w[i] = 1.f;   // BoxFilter::Sample weight
-    } else if (n > 0 && c->last_persistent) {
+    } else if (n > 0 && c->last.persistent) {
         std::vector<float> camw((size_t)n);
-        HIP_TRY(hipMemcpy(camw.data(), c->ps.camw, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(camw.data(), c->set.camw, n * sizeof(float), hipMemcpyDeviceToHost));
         const long long np = (long long)c->film.width * c->film.height;
         for (long long i = 0; i < n; ++i)
             w[i] = camw[c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]];

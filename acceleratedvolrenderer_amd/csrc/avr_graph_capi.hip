@@ -962,10 +962,9 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
     if (rc) return rc;
     rc = uni ? ensure_graph_uniform(c, uni) : ensure_graph_index(c, idx);
     if (rc) return rc;
-    const long long P = (long long)c->film.width * c->film.height;
-    if (P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
-    const long long Smax = std::max<long long>(1, c->max_paths / P);
-    const long long need = P * std::min<long long>(Smax, std::max(1, spp_end - spp_begin));
+    PassPlan plan;
+    if ((rc = pass_plan(c, false, spp_begin, spp_end, &plan))) return rc;
+    const long long P = plan.P, Smax = plan.Smax, need = plan.need;
     if (analyze && detail) {
         // asked for, never silent: pass samples x max_depth x 24 B, within the path state's policy
         const unsigned long long entries = (unsigned long long)need * (unsigned long long)std::max(analyze_depth, 1);
@@ -974,33 +973,12 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
             return fail(AVR_ERR_ARG, "graph analyze: the detail buffer (" + std::to_string(need) + " pass samples x max_depth " +
                                          std::to_string(analyze_depth) + " x 24 B) exceeds the path state's " +
                                          std::to_string(limit) + " B (max_paths x 252 B): lower max_depth or max_paths, or pass detail = 0");
-        if ((size_t)entries > c->adetail_cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (c->d_adetail) (void)hipFree(c->d_adetail);
-            c->d_adetail = nullptr;
-            c->adetail_cap = 0;
-            HIP_TRY(dalloc(&c->d_adetail, (size_t)entries));
-            c->adetail_cap = (size_t)entries;
-        }
+        if ((rc = grow(c, &c->d_adetail, &c->adetail_cap, (size_t)entries))) return rc;
     }
     rc = ensure_paths(c, need);
     if (rc) return rc;
-    if (!analyze && need > c->gside_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_gside) (void)hipFree(c->d_gside);
-        c->d_gside = nullptr;
-        c->gside_cap = 0;
-        HIP_TRY(dalloc(&c->d_gside, (size_t)need));
-        c->gside_cap = need;
-    }
-    if (analyze && need > c->arec_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_arec) (void)hipFree(c->d_arec);
-        c->d_arec = nullptr;
-        c->arec_cap = 0;
-        HIP_TRY(dalloc(&c->d_arec, (size_t)need));
-        c->arec_cap = need;
-    }
+    // (queued kernels may still read the buffer a larger one replaces: grow drains the stream)
+    if ((rc = analyze ? grow(c, &c->d_arec, &c->arec_cap, need) : grow(c, &c->d_gside, &c->gside_cap, need))) return rc;
     if (analyze && !c->d_aacc) {
         HIP_TRY(dalloc(&c->d_aacc, (size_t)P));
         HIP_TRY(hipMemsetAsync(c->d_aacc, 0, (size_t)P * sizeof(avr::graph::AnalyzeAcc), c->stream));
@@ -1008,41 +986,15 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
     EV_MARK(evStart);
     for (long long base = spp_begin; base < spp_end; base += Smax) {
         const int S = (int)std::min<long long>(Smax, spp_end - base);
-        avr::Params p{};
-        p.med = c->med;
-        p.lights = c->lights;
-        p.cam = c->cam;
-        p.film = c->film;
-        p.film.filter_type = c->filter_type;
-        p.film.gauss = c->ftab;
-        p.sampler_kind = c->sampler_kind;
-        p.zs = zs;
-        p.ps = c->ps;
-        p.sh = c->sh;
-        p.max_depth = 1;
-        p.seed = seed;
-        p.pass_pixels = (int)P;
-        p.div_pixels = avr::fastdiv_make((uint32_t)P);
-        p.div_width = avr::fastdiv_make((uint32_t)c->film.width);
-        p.pass_samples = S;
-        p.sample_base = (int)base;
-        p.stats = c->d_stats;
+        avr::Params p;
+        pass_params(c, zs, seed, 1, P, base, S, &p);
         const long long n0 = P * S;
-        c->last_persistent = false;
-        c->last_fast = false;
-        c->last_graph = !analyze;
-        c->last_analyze = analyze ? (detail ? 2 : 1) : 0;
-        c->last_analyze_depth = analyze_depth;
-        EV_MARK(c0);
         // the record keeps the camera's own ray: the graph kernels solve the primitive once from
         // it (k_camera would move it to the interface entry, as the path kernels want it)
         avr::Params pc = p;
         pc.med.boundary = 0;
-        if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, pc);
-        else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, pc);
-        HIP_TRY(hipGetLastError());
-        EV_MARK(c1);
-        c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});
+        int c1;
+        if ((rc = launch_camera(c, pc, &c1))) return rc;
         // one lane per camera record, as many blocks as records up to 64 per CU's worth
         const int nb = blocks_for(n0, 256, 256 * 64);
         if (analyze) {
@@ -1061,17 +1013,18 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
         HIP_TRY(hipGetLastError());
         EV_MARK(m1);
         c->timed.push_back({c1, m1, &avr_stats::ms_medium, true});
-        if (analyze)
+        if (analyze) {
             hipLaunchKernelGGL(avr::k_graph_analyze_reduce, dim3(blocks_for(P)), dim3(256), 0, c->stream, (int)P, S,
                                c->d_arec, c->d_aacc);
-        else
-            hipLaunchKernelGGL((c->film.nbuckets > 0 ? avr::k_film<true> : avr::k_film<false>), dim3(blocks_for(P)), dim3(256),
-                               avr::film_lds_bytes(c->film.nbuckets), c->stream, p);
-        HIP_TRY(hipGetLastError());
-        EV_MARK(f1);
-        c->timed.push_back({m1, f1, &avr_stats::ms_film, false});
-        c->last_base = (int)base;
-        c->last_S = S;
+            HIP_TRY(hipGetLastError());
+            EV_MARK(f1);
+            c->timed.push_back({m1, f1, &avr_stats::ms_film, false});
+        } else if ((rc = launch_film(c, p, false, m1))) {
+            return rc;
+        }
+        LastPass lp = c->last.without_kpaths((int)base, S);
+        lp.graph = !analyze; lp.analyze = analyze ? (detail ? 2 : 1) : 0; lp.analyze_depth = analyze_depth;
+        c->last = lp;
     }
     EV_MARK(evEnd);
     c->timed.push_back({evStart, evEnd, &avr_stats::ms_total, false});
@@ -1152,9 +1105,9 @@ int avr_graph_analyze_last_pass(avr_context *c, float *o, float *d, int *counts,
                                 int *in_range, float *range_sum, long long n_max, int max_depth) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
-    if (c->last_analyze != 2) return fail(AVR_ERR_STATE, "the last render was not avr_graph_analyze's with detail");
-    const long long n = (long long)c->film.width * c->film.height * c->last_S;
-    const int md = c->last_analyze_depth;
+    if (c->last.analyze != 2) return fail(AVR_ERR_STATE, "the last render was not avr_graph_analyze's with detail");
+    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const int md = c->last.analyze_depth;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (max_depth != md) return fail(AVR_ERR_ARG, "max_depth differs from the analysis'");
     if (n == 0) return AVR_OK;
@@ -1201,8 +1154,8 @@ int avr_graph_analyze_last_pass(avr_context *c, float *o, float *d, int *counts,
 int avr_graph_last_pass(avr_context *c, float *o, float *d, float *points, int *counts, long long n_max) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
-    if (!c->last_graph) return fail(AVR_ERR_STATE, "the last render was not avr_graph_render's");
-    const long long n = (long long)c->film.width * c->film.height * c->last_S;
+    if (!c->last.graph) return fail(AVR_ERR_STATE, "the last render was not avr_graph_render's");
+    const long long n = (long long)c->film.width * c->film.height * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n == 0) return AVR_OK;
     std::vector<float4> h((size_t)n);

@@ -1,7 +1,7 @@
 // avr_kpaths.hip — explicit instantiations of the persistent path kernel k_paths for ONE
 // medium kind (AVR_KP_MED: 0 GridMedium, 1 Homogeneous/Cloud, 3 NanoVDB, 4 RGBGridMedium)
 // and render mode (AVR_KP_FAST: 0 replay, 1 fast). build.py compiles one object per
-// (medium, mode) in parallel — the 112 instantiations are most of the library's compile
+// (medium, mode) in parallel — the 168 instantiations are most of the library's compile
 // time — and links them with avr_capi.hip, which declares them (AVR_KP_SPLIT).
 #define AVR_KPATHS_TU   // only the kernels' templates and device helpers, no host-launched kernels
 #include "avr_kernels.hip"

@@ -2,7 +2,8 @@
 and the C-ABI unit), compiled with build.py's exact flags and --save-temps.
 
 usage: python tools/isa_digest.py [out.json] [--root DIR] [-DNAME=VALUE ...]
-Per unit: sha256 over the device assembly (comments and .file / .ident stripped) and, per
+Per unit: sha256 over the device assembly (comments, .file / .ident and the path-derived
+compilation unit id stripped) and, per
 kernel symbol, sha256 over its instruction mnemonics in order (`ops`: register numbers,
 immediates and LDS / kernel-argument offsets ignored) plus its instruction count. --root
 compiles another checkout (e.g. a `git worktree` of the previous commit) with this tree's
@@ -35,7 +36,8 @@ def unit_asm(args):
         t = line.strip()
         if not t or t.startswith(";") or t.startswith(".ident") or t.startswith(".file"):
             continue
-        keep.append(re.sub(r"\s*;.*$", "", line))
+        # (the compilation unit id hashes the source's path: another checkout's differs)
+        keep.append(re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", re.sub(r"\s*;.*$", "", line)))
     body = "\n".join(keep)
     nins = sum(1 for l in keep if l.startswith("\t") and not l.strip().startswith("."))
     kern = {}
