@@ -17,6 +17,7 @@
 //   k_film     : per pixel, samples added in sampleIndex order into fp64 sums
 //                (bit-identical order to ImageTileIntegrator::Render's per-pixel loop).
 #include "avr_numerics.h"
+#include "avr_grid_index.h"
 #include "avr_sampling.h"
 #include "avr_vdb.h"
 #include "avr_envmap.h"
@@ -340,7 +341,7 @@ __device__ __forceinline__ void flush_stat(unsigned long long *stats, int idx, u
 // GridMedium density fetch — SampledGrid<float>::Lookup (util/containers.h:804-835)
 __device__ __forceinline__ float grid_at(const float *__restrict__ v, int nx, int ny, int nz, int x, int y, int z) {
     if (x < 0 || x >= nx || y < 0 || y >= ny || z < 0 || z >= nz) return 0.f;
-    return v[(z * ny + y) * nx + x];
+    return v[grid_linear_index(nx, ny, nz, x, y, z)];
 }
 // fn: float(nx, ny, nz) when the caller has them (the same value as the int -> float conversion)
 __device__ __forceinline__ float grid_lookup(const float *__restrict__ v, int nx, int ny, int nz, V3 p,
@@ -367,14 +368,10 @@ __device__ __forceinline__ bool fat_issue(const float4 *__restrict__ fat, int nx
     int ix = (int)__builtin_floorf(psx), iy = (int)__builtin_floorf(psy), iz = (int)__builtin_floorf(psz);
     if (ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz) return false;
     dx = psx - (float)ix, dy = psy - (float)iy, dz = psz - (float)iz;
-    // entry index in 32 bits with 24-bit multiplies when the copy has < 2^31 entries (grids to
-    // 1290^3; the condition is wave-uniform): (iz + 1)(ny + 1) + iy + 1 < 1291^2 < 2^24
-    const uint32_t ex = (uint32_t)nx + 1, ey = (uint32_t)ny + 1;
-    size_t e;
-    if ((uint64_t)ex * ey * ((uint64_t)nz + 1) < (1ull << 31))
-        e = (size_t)(__umul24(__umul24((uint32_t)(iz + 1), ey) + (uint32_t)(iy + 1), ex) + (uint32_t)(ix + 1)) * 2;
-    else
-        e = (((size_t)(iz + 1) * ey + (iy + 1)) * ex + (ix + 1)) * 2;
+    // entry index in 32 bits with 24-bit multiplies where every operand fits them
+    // ((ny + 1)(nz + 1) < 2^24, nx + 1 < 2^24, < 2^31 entries: cubes to 1289^3, not slabs thin in
+    // x), in 64 bits otherwise; the condition is wave-uniform (avr_grid_index.h)
+    const size_t e = fat_entry_index(nx, ny, nz, ix, iy, iz) * 2;
     a = fat[e], b = fat[e + 1];
     return true;
 }
@@ -386,7 +383,6 @@ __device__ __forceinline__ float fat_lerp(float4 a, float4 b, float dx, float dy
     return lerp(dz, lerp(dy, d00, d10), lerp(dy, d01, d11));
 }
 // Same value as grid_lookup() bit for bit from the bricked layout (DevMedium::brick).
-constexpr int kBrickFloats = 736;   // 9^3 = 729 apron values, padded to 23 x 128-B lines
 __device__ __forceinline__ float brick_lookup(const float *__restrict__ brick, const int nb[3],
                                               const float *__restrict__ v, int nx, int ny, int nz, V3 p,
                                               const float *fn = nullptr) {
@@ -395,9 +391,8 @@ __device__ __forceinline__ float brick_lookup(const float *__restrict__ brick, c
     int ix = (int)__builtin_floorf(psx), iy = (int)__builtin_floorf(psy), iz = (int)__builtin_floorf(psz);
     if (ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz) return grid_lookup(v, nx, ny, nz, p, fn);
     float dx = psx - (float)ix, dy = psy - (float)iy, dz = psz - (float)iz;
-    const int ux = ix + 1, uy = iy + 1, uz = iz + 1;   // 0 .. n: brick u >> 3, apron-local u & 7
-    const size_t b = ((size_t)(uz >> 3) * nb[1] + (uy >> 3)) * nb[0] + (ux >> 3);
-    const float *q = brick + b * kBrickFloats + ((uz & 7) * 9 + (uy & 7)) * 9 + (ux & 7);
+    // u = i + 1 in 0 .. n: brick u >> 3, apron-local u & 7
+    const float *q = brick + brick_float_offset(nb, ix + 1, iy + 1, iz + 1);
     float d00 = lerp(dx, q[0], q[1]);
     float d10 = lerp(dx, q[9], q[10]);
     float d01 = lerp(dx, q[81], q[82]);
@@ -443,11 +438,13 @@ __global__ void __launch_bounds__(256) k_fatten(const float *__restrict__ v, int
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const int ix = (int)(e % (nx + 1)) - 1, iy = (int)((e / (nx + 1)) % (ny + 1)) - 1,
                   iz = (int)(e / ((size_t)(nx + 1) * (ny + 1))) - 1;
-        fat[2 * e] = make_float4(grid_at(v, nx, ny, nz, ix, iy, iz), grid_at(v, nx, ny, nz, ix + 1, iy, iz),
-                                 grid_at(v, nx, ny, nz, ix, iy + 1, iz), grid_at(v, nx, ny, nz, ix + 1, iy + 1, iz));
-        fat[2 * e + 1] = make_float4(grid_at(v, nx, ny, nz, ix, iy, iz + 1), grid_at(v, nx, ny, nz, ix + 1, iy, iz + 1),
-                                     grid_at(v, nx, ny, nz, ix, iy + 1, iz + 1),
-                                     grid_at(v, nx, ny, nz, ix + 1, iy + 1, iz + 1));
+        // stored where fat_issue will look for it (fat_entry_index(...) == e)
+        const size_t w = fat_entry_index(nx, ny, nz, ix, iy, iz) * 2;
+        fat[w] = make_float4(grid_at(v, nx, ny, nz, ix, iy, iz), grid_at(v, nx, ny, nz, ix + 1, iy, iz),
+                             grid_at(v, nx, ny, nz, ix, iy + 1, iz), grid_at(v, nx, ny, nz, ix + 1, iy + 1, iz));
+        fat[w + 1] = make_float4(grid_at(v, nx, ny, nz, ix, iy, iz + 1), grid_at(v, nx, ny, nz, ix + 1, iy, iz + 1),
+                                 grid_at(v, nx, ny, nz, ix, iy + 1, iz + 1),
+                                 grid_at(v, nx, ny, nz, ix + 1, iy + 1, iz + 1));
     }
 }
 
