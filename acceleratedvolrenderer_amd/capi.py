@@ -276,6 +276,19 @@ SIGNATURES = {
     "avr_graph_analysis_clear": (ctypes.c_int, [ctypes.c_void_p]),
     "avr_graph_analyze_last_pass": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p,
                                                    c_int_p, c_float_p, ctypes.c_longlong, ctypes.c_int]),
+    "avr_graph_capture": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p,
+                                         ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "avr_graph_uniform_count_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, ctypes.c_float,
+                                                      ctypes.POINTER(ctypes.c_longlong)]),
+    "avr_graph_uniform_from_points_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, ctypes.c_float,
+                                                            ctypes.POINTER(ctypes.c_void_p), c_int_p]),
+    "avr_graph_voxels_create": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_float, ctypes.c_longlong, c_int_p,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "avr_graph_voxels_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "avr_graph_voxels_single_layer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int_p]),
+    "avr_graph_voxels_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_int_p]),
+    "avr_graph_voxels_state": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, ctypes.c_void_p, ctypes.c_longlong]),
+    "avr_graph_voxels_visited": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_longlong)] * 4),
 }
 
 _lib = None
@@ -742,6 +755,31 @@ class Context:
                                                        ids.ctypes.data_as(c_int_p), _fp(hit0), _fp(hit1)))
         return ids, hit0, hit1
 
+    def graph_capture(self, origin, direction, xvec, yvec, num_steps):
+        """VoxelBoundary::CaptureBoundary's ray bundles on the device (avr_graph_capture): per
+        bundle an origin, a direction (used as given, not normalised) and the two step vectors,
+        (n, 3) each; (2 num_steps + 1)^2 rays per bundle, (i, j) with i outer. Returns (points
+        (n_rays, 3), captured (n_rays,) bool, n_captured) in ray order."""
+        arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (origin, direction, xvec, yvec)]
+        nb = len(arrs[0])
+        if any(len(a) != nb for a in arrs):
+            raise ValueError("graph_capture: one direction and one pair of step vectors per origin")
+        side = 2 * int(num_steps) + 1
+        n = max(0, nb * side * side) if int(num_steps) >= 0 else 0
+        out = np.zeros((n, 4), np.float32) if n <= 2 ** 31 - 1 else np.zeros((1, 4), np.float32)
+        cnt = ctypes.c_longlong(0)
+        _check(self.lib.avr_graph_capture(self.h, nb, _fp(arrs[0]), _fp(arrs[1]), _fp(arrs[2]), _fp(arrs[3]),
+                                          int(num_steps), _fp(out), ctypes.byref(cnt)))
+        return np.ascontiguousarray(out[:, :3]), out[:, 3] != 0, cnt.value
+
+    def graph_uniform_count(self, points, spacing):
+        """The number of distinct voxels of `spacing` among (n, 3) points, on the device
+        (avr_graph_uniform_count_device): GraphUniform.from_points(...).num_vertices."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        cnt = ctypes.c_longlong(0)
+        _check(self.lib.avr_graph_uniform_count_device(self.h, len(p), _fp(p), float(spacing), ctypes.byref(cnt)))
+        return cnt.value
+
     def graph_render_uniform(self, uniform, spp_begin, spp_end, seed, graph_from_render=None, view=0,
                              light_scale=INV_4PI):
         """GraphIntegrator::Li (uniform graph) for sample indices [spp_begin, spp_end) into the
@@ -1096,6 +1134,23 @@ class GraphUniform:
         self.vertex_of = vertex_of
         return self
 
+    @classmethod
+    def from_points_device(cls, ctx, points, spacing):
+        """from_points(points, zeros, spacing) with the voxel set built on the device
+        (avr_graph_uniform_from_points_device): bitwise the same coordinates, ids and vertex_of."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        self = cls.__new__(cls)
+        self.lib = load()
+        self.h = None
+        vertex_of = np.zeros(len(p), np.int32)
+        h = ctypes.c_void_p()
+        _check(self.lib.avr_graph_uniform_from_points_device(ctx.h if ctx is not None else None, len(p), _fp(p),
+                                                             float(spacing), ctypes.byref(h),
+                                                             vertex_of.ctypes.data_as(c_int_p)))
+        self._adopt(h)
+        self.vertex_of = vertex_of
+        return self
+
     @property
     def points(self):
         """The vertices' points, (float)coors * spacing (graph.cpp:555)."""
@@ -1126,6 +1181,86 @@ class GraphUniform:
     def close(self):
         if self.h:
             self.lib.avr_graph_uniform_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+VOXEL_VERTEX, VOXEL_OUTSIDE, VOXEL_CAST, VOXEL_SINGLE, VOXEL_FILLED = 1, 2, 4, 8, 16
+VOXEL_FILL_START = {None: -1, "lowest": -1, "all": -2}
+
+
+class GraphVoxels:
+    """The voxel boundary's flood state (avr_graph_voxels_*): one byte per cell of the dense
+    lattice over FitBounds(pmin, pmax, spacing), x fastest; bits VOXEL_VERTEX, _OUTSIDE, _CAST,
+    _SINGLE, _FILLED. single_layer / fill take a Context for the device, None for the host: the
+    two leave the same bytes."""
+
+    def __init__(self, pmin, pmax, spacing, coors):
+        self.lib = load()
+        self.h = None
+        lo = np.ascontiguousarray(pmin, np.float32).reshape(3)
+        hi = np.ascontiguousarray(pmax, np.float32).reshape(3)
+        c = np.asarray(coors)
+        if c.dtype.kind not in "iu":
+            raise ValueError("GraphVoxels: integer lattice coordinates")
+        c = np.ascontiguousarray(np.clip(c.reshape(-1, 3).astype(np.int64), -2 ** 31, 2 ** 31 - 1), np.int32)
+        h = ctypes.c_void_p()
+        _check(self.lib.avr_graph_voxels_create(_fp(lo), _fp(hi), float(spacing), len(c), c.ctypes.data_as(c_int_p),
+                                                ctypes.byref(h)))
+        self.h = h
+        self.coors = c
+        self.spacing = np.float32(spacing)
+        self.lo, self.n = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        _check(self.lib.avr_graph_voxels_state(h, self.lo.ctypes.data_as(c_int_p), self.n.ctypes.data_as(c_int_p), None, 0))
+        self.cells = int(np.prod(self.n.astype(np.int64)))
+
+    def single_layer(self, ctx=None):
+        """ToSingleLayerAndSaveCast; returns the number of levels the flood ran."""
+        lv = ctypes.c_int(0)
+        _check(self.lib.avr_graph_voxels_single_layer(ctx.h if ctx is not None else None, self.h, ctypes.byref(lv)))
+        return lv.value
+
+    def fill(self, ctx=None, start=None):
+        """FillInside from the single-layer vertex `start` (an index into this state's
+        vertices), None / "lowest" or "all"; returns the number of levels."""
+        s = VOXEL_FILL_START[start] if start in VOXEL_FILL_START else start
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < -2:
+            raise ValueError('fill start: a single-layer vertex id, None / "lowest" or "all"')
+        lv = ctypes.c_int(0)
+        _check(self.lib.avr_graph_voxels_fill(ctx.h if ctx is not None else None, self.h, int(s), ctypes.byref(lv)))
+        return lv.value
+
+    def state(self):
+        """The state bytes, shaped (nz, ny, nx)."""
+        s = np.zeros(self.cells, np.uint8)
+        _check(self.lib.avr_graph_voxels_state(self.h, None, None, s.ctypes.data_as(ctypes.c_void_p), len(s)))
+        return s.reshape(int(self.n[2]), int(self.n[1]), int(self.n[0]))
+
+    def counts(self):
+        """(visited, cast, single layer, filled) cell counts."""
+        v = [ctypes.c_longlong(0) for _ in range(4)]
+        _check(self.lib.avr_graph_voxels_visited(self.h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def cells_with(self, bit):
+        """Lattice coordinates (k, 3) of the cells with `bit`, in ascending (z, y, x)."""
+        z, y, x = np.nonzero(self.state() & bit)
+        return (np.stack([x, y, z], axis=1).astype(np.int32) + self.lo).astype(np.int32)
+
+    def vertex_bits(self):
+        """The state byte of each vertex's cell, in vertex order."""
+        s = self.state()
+        c = self.coors - self.lo
+        return s[c[:, 2], c[:, 1], c[:, 0]]
+
+    def close(self):
+        if self.h:
+            self.lib.avr_graph_voxels_destroy(self.h)
             self.h = None
 
     def __del__(self):

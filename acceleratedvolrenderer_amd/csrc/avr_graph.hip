@@ -40,6 +40,15 @@
 //  k_graph_merge_flags  one lane per unfinalised scatter point runs merge_step; then the
 //  k_graph_merge_scan   id scan over the final states (new-vertex flags per wave, their
 //  k_graph_merge_ids    prefix sums, vertex_of_point).
+//  k_graph_capture  VoxelBoundary::CaptureBoundary's ray bundles (voxels/voxel_boundary.cpp:13-62):
+//                  one lane per ray, the primitive's crossing, then the majorant DDA up to the
+//                  first non-empty cell.
+//  k_graph_uniform_insert  FreeGraph::ToUniform's vertex part for points on the device: one lane
+//  k_graph_uniform_first   per point inserts its voxel key into an open-addressing set (64-bit
+//                  compare-and-swap) and keeps the key's lowest point index (atomic min); the
+//                  ids then come from k_graph_merge_flags / _scan / _ids.
+//  k_graph_voxels_level  one level of the voxel boundary's floods (avr_graph_voxels.h): one lane
+//                  per frontier cell, the next level appended with one atomic per wave.
 //
 // Geometry model (shared with the oracle): the medium's boundary primitive is
 // its bounds box (medium-space slab test, ray mapped without error offsets), kGeom 0, or, on
@@ -50,6 +59,7 @@
 #include "avr_graph_index.h"
 #include "avr_graph_merge.h"
 #include "avr_graph_uniform.h"
+#include "avr_graph_voxels.h"
 
 namespace avr {
 namespace graph {
@@ -900,6 +910,143 @@ __global__ void __launch_bounds__(256) k_graph_merge_ids(int v0, int n, const in
             t = v0 + woff[j >> 6] + __popcll(mask[j >> 6] & ((1ull << (j & 63)) - 1ull));
         }
         ids[i] = t;
+    }
+}
+
+// VoxelBoundary::CaptureBoundary (voxels/voxel_boundary.cpp:13-62), one lane per ray: ray r of
+// bundle b is (i, j) in [-S, S]^2, i outer; p = (origin_b + xv_b * (float)i) + yv_b * (float)j;
+// GetHits(primitive) along dir_b: a miss captures nothing, and neither does a start inside the
+// primitive (the reference skips to the exit hit, beyond which no medium lies); a ray from
+// outside moves to its entry (SkipIntersection, no offset). Then GridMedium::SampleRay with the
+// direction as given (not normalised: the segment bounds are in its units) and tMax = Infinity;
+// the first segment with sigma_t[0] * majorant != 0 (sigma at sample_visible(0), k_graph_walks'
+// defaultLambda) gives out[ray] = {p + dir_b * segMin, 1}; {0, 0, 0, 0} without one.
+template <int kGeom>
+__global__ void __launch_bounds__(256) k_graph_capture(DevMedium m, long long nRays, int S, const float *__restrict__ origin,
+                                                       const float *__restrict__ dir, const float *__restrict__ xvec,
+                                                       const float *__restrict__ yvec, float4 *__restrict__ out,
+                                                       int *__restrict__ nCaptured) {
+    __shared__ float s_maj[4096];
+    const float *maj = stage_majorant(m, s_maj);
+    const LambdaIdx li = lambda_index(sample_visible(0.f).l);
+    const float sigma_t0 = (sample_table(m.sigma_a, li) + sample_table(m.sigma_s, li)).v0;
+    const int side = 2 * S + 1;
+    const long long per = (long long)side * side;
+    const long long lanes = (nRays + 63) / 64 * 64;   // whole waves reach the ballot
+    for (long long ray = blockIdx.x * (long long)blockDim.x + threadIdx.x; ray < lanes;
+         ray += (long long)gridDim.x * blockDim.x) {
+        bool captured = false;
+        if (ray < nRays) {
+            const long long b = ray / per;
+            const int r = (int)(ray - b * per), i = r / side - S, j = r - (r / side) * side - S;
+            const V3 o = {origin[3 * b], origin[3 * b + 1], origin[3 * b + 2]}, d = {dir[3 * b], dir[3 * b + 1], dir[3 * b + 2]};
+            const V3 xv = {xvec[3 * b], xvec[3 * b + 1], xvec[3 * b + 2]}, yv = {yvec[3 * b], yvec[3 * b + 1], yvec[3 * b + 2]};
+            V3 p = (o + xv * (float)i) + yv * (float)j;
+            float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
+            const graph::Hits h = graph::primitive_hits<kGeom>(m, p, d);
+            if (h.type == graph::kOutsideTwoHits) p = p + d * h.t0;
+            // a grid point or an entry that overflowed captures nothing (the host checks the bundle)
+            const bool finite = __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z);
+            if (h.type == graph::kOutsideTwoHits && finite) {
+                Dda it;
+                dda_init(it, m, Ray{p, d}, kInf);
+                float segMin, segMax, mv;
+                while (dda_next(it, maj, m.mres, &segMin, &segMax, &mv)) {
+                    if (sigma_t0 * mv != 0) {
+                        const V3 q = p + d * segMin;
+                        res = make_float4(q.x, q.y, q.z, 1.f);
+                        captured = true;
+                        break;
+                    }
+                }
+            }
+            out[ray] = res;
+        }
+        const unsigned long long mask = __ballot(captured);
+        if (mask != 0 && __lane_id() == 0) atomicAdd(nCaptured, __popcll(mask));
+    }
+}
+
+// FreeGraph::ToUniform's vertices (Uniform::FromPoints, reduce 0) for n points on the device,
+// first pass: the point's voxel key goes into the set keys[0 .. mask] (empty = all ones, slot =
+// MixBits(key) & mask, linear probing; capacity at least 2 n, so a free slot exists), and
+// first[slot] keeps the lowest index of the key's points, which makes the result independent
+// of scheduling. slot_of[i] = the key's slot; *bad = the lowest index with an invalid coordinate.
+__global__ void __launch_bounds__(256) k_graph_uniform_insert(long long n, const float *__restrict__ xyz, float spacing,
+                                                              unsigned long long *keys, uint32_t mask, int *first,
+                                                              int *__restrict__ slot_of, int *bad) {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+        int c[3];
+        if (!graph::uniform_coors(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], spacing, c)) {
+            atomicMin(bad, (int)i);
+            slot_of[i] = -1;
+            continue;
+        }
+        const unsigned long long key = graph::uniform_key(c[0], c[1], c[2]);
+        uint32_t slot = (uint32_t)graph::uniform_mix(key) & mask;
+        int found = -1;
+        for (uint32_t probe = 0; probe <= mask; ++probe) {
+            const unsigned long long old = atomicCAS(keys + slot, graph::kUniformEmpty, key);
+            if (old == graph::kUniformEmpty || old == key) {
+                found = (int)slot;
+                break;
+            }
+            slot = (slot + 1) & mask;
+        }
+        if (found >= 0) atomicMin(first + found, (int)i);
+        slot_of[i] = found;
+    }
+}
+
+// Second pass: state[i] = the first point of i's voxel (i itself: a new vertex; the form
+// k_graph_merge_flags / _ids read with v0 = 0), *count += the new vertices
+__global__ void __launch_bounds__(256) k_graph_uniform_first(long long n, const int *__restrict__ first,
+                                                             const int *__restrict__ slot_of, int *__restrict__ state,
+                                                             int *count) {
+    const long long lanes = (n + 63) / 64 * 64;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < lanes; i += gridDim.x * 256ll) {
+        bool isNew = false;
+        if (i < n) {
+            const int s = slot_of[i];
+            const int f = s >= 0 ? first[s] : -1;
+            state[i] = f;
+            isNew = f == (int)i;
+        }
+        const unsigned long long m = __ballot(isNew);
+        if (m != 0 && __lane_id() == 0) atomicAdd(count, __popcll(m));
+    }
+}
+
+// The floods' state in device memory: four cells per 32-bit word, bits ored in with relaxed
+// atomics at agent scope (a stale read only costs an atomic; the or's old value decides)
+struct VoxelStateDev {
+    unsigned *w;
+    __device__ __forceinline__ unsigned bits(int cell) const {
+        return (__hip_atomic_load(w + (cell >> 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> ((cell & 3) * 8)) & 0xffu;
+    }
+    __device__ __forceinline__ bool set(int cell, unsigned bit) {
+        const unsigned m = bit << ((cell & 3) * 8);
+        return !(atomicOr(w + (cell >> 2), m) & m);
+    }
+};
+
+// One level of a flood (avr_graph_voxels.h), kFill 0 the single layer's, 1 the fill's: one lane
+// per cell of frontier[0 .. nFront); a neighbour joins next[] once, where its bit was first set
+// (each cell at most once over the whole flood, so next[] holds at most `cells` entries); one
+// atomic per wave and neighbour direction on *nNext, which the host reads to launch the next level.
+template <int kFill>
+__global__ void __launch_bounds__(256) k_graph_voxels_level(graph::VoxelDims d, unsigned *state,
+                                                            const int *__restrict__ frontier, int nFront,
+                                                            int *__restrict__ next, int *nNext) {
+    VoxelStateDev st{state};
+    for (long long idx = blockIdx.x * 256ll + threadIdx.x; idx < nFront; idx += gridDim.x * 256ll) {
+        const int cell = frontier[idx];
+        auto push = [&](int nb, bool fresh) {
+            const int slot = wave_push(nNext, fresh);
+            if (fresh) next[slot] = nb;
+        };
+        if constexpr (kFill == 0) graph::voxel_visit_outside(d, st, cell, push);
+        else graph::voxel_visit_fill(d, st, cell, push);
     }
 }
 

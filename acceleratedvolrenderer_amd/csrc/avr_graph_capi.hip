@@ -1293,4 +1293,266 @@ int avr_graph_uniform_trace_device(avr_context *c, const avr_graph_uniform *u, l
     return AVR_OK;
 }
 
+int avr_graph_capture(avr_context *c, int n_bundles, const float *origin, const float *dir, const float *xvec,
+                      const float *yvec, int num_steps, float *out_points4, long long *n_captured) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    if (n_bundles < 1 || num_steps < 0) return fail(AVR_ERR_ARG, "bad capture arguments");
+    if (!origin || !dir || !xvec || !yvec || !out_points4 || !n_captured) return fail(AVR_ERR_ARG, "null buffer");
+    const long long side = 2ll * num_steps + 1;
+    if (side > 0x7fffffffll / side || side * side > 0x7fffffffll / n_bundles)
+        return fail(AVR_ERR_ARG, "capture: more than 2^31 - 1 rays");
+    if (!c->has_medium) return fail(AVR_ERR_STATE, "medium required");
+    for (int b = 0; b < n_bundles; ++b) {
+        bool finite = true;
+        for (int k = 0; k < 3; ++k)
+            finite = finite && std::isfinite(origin[3 * b + k]) && std::isfinite(dir[3 * b + k]) &&
+                     std::isfinite(xvec[3 * b + k]) && std::isfinite(yvec[3 * b + k]);
+        if (!finite || (dir[3 * b] == 0 && dir[3 * b + 1] == 0 && dir[3 * b + 2] == 0))
+            return fail(AVR_ERR_ARG, "capture: bundle " + std::to_string(b) + ": finite vectors and a direction other than 0 required");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const long long n = side * side * n_bundles;
+    char *buf = nullptr;
+    const size_t szB = (size_t)n_bundles * 3 * sizeof(float), szO = (size_t)n * sizeof(float4);
+    HIP_TRY(dalloc(&buf, szO + 4 * szB + 16));
+    float4 *dOut = (float4 *)buf;
+    float *dB = (float *)(buf + szO);
+    int *dN = (int *)(buf + szO + 4 * szB);
+    const float *src[4] = {origin, dir, xvec, yvec};
+    hipError_t e = hipMemsetAsync(dN, 0, sizeof(int), c->stream);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        e = hipMemcpyAsync(dB + (size_t)k * 3 * n_bundles, src[k], szB, hipMemcpyHostToDevice, c->stream);
+    int nCap = 0;
+    if (e == hipSuccess) {
+        AVR_GRAPH_LAUNCH_G(avr::k_graph_capture, graph_interface(c), blocks_for(n, 256, 256 * 64), c->med, n, num_steps, dB,
+                           dB + (size_t)3 * n_bundles, dB + (size_t)6 * n_bundles, dB + (size_t)9 * n_bundles, dOut, dN);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_points4, dOut, szO, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&nCap, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(e));
+    *n_captured = nCap;
+    return AVR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Uniform::FromPoints(reduce 0) on the device: the number of distinct voxels and, when
+// vertex_of is given, every point's vertex id (ids in the order of first appearance)
+int uniform_points_device(avr_context *c, long long n, const float *xyz, float spacing, long long *count, int *vertex_of) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    // the host routine's checks, in its order
+    if (!(spacing > 0) || !std::isfinite(spacing)) return fail(AVR_ERR_ARG, "graph uniform: spacing must be positive and finite");
+    if (n < 1 || n > 0x3fffffff || !xyz) return fail(AVR_ERR_ARG, "graph uniform: at least one vertex required");
+    HIP_TRY(hipSetDevice(c->device));
+    size_t cap = 16;
+    while (cap < 2 * (size_t)n) cap *= 2;
+    const size_t nw = ((size_t)n + 63) / 64;
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t szX = pad((size_t)n * 12), szK = cap * 8, szF = cap * 4, szS = pad((size_t)n * 4);
+    const size_t szM = pad(nw * 8), szC = pad(nw * 4);
+    char *buf = nullptr;
+    HIP_TRY(dalloc(&buf, szK + szM + szX + szF + 3 * szS + szC + 16));
+    unsigned long long *dKeys = (unsigned long long *)buf, *dMask = (unsigned long long *)(buf + szK);
+    float *dX = (float *)(buf + szK + szM);
+    int *dFirst = (int *)(buf + szK + szM + szX);
+    int *dSlot = (int *)((char *)dFirst + szF), *dState = (int *)((char *)dSlot + szS), *dIds = (int *)((char *)dState + szS);
+    int *dCnt = (int *)((char *)dIds + szS), *dScal = (int *)((char *)dCnt + szC);   // dScal: bad, count, total
+    int scal[3] = {0x7fffffff, 0, 0};
+    hipError_t e = hipMemsetAsync(dKeys, 0xff, szK, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dFirst, 0x7f, szF, c->stream);   // 0x7f7f7f7f: above every index
+    if (e == hipSuccess) e = hipMemcpyAsync(dScal, scal, sizeof scal, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dX, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        const int blocks = blocks_for(n, 256, 256 * 64);
+        hipLaunchKernelGGL(avr::k_graph_uniform_insert, dim3(blocks), dim3(256), 0, c->stream, n, dX, spacing, dKeys,
+                           (uint32_t)(cap - 1), dFirst, dSlot, dScal);
+        hipLaunchKernelGGL(avr::k_graph_uniform_first, dim3(blocks), dim3(256), 0, c->stream, n, dFirst, dSlot, dState,
+                           dScal + 1);
+        if (vertex_of) {
+            hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt);
+            hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dScal + 2);
+            hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt,
+                               dIds);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(scal, dScal, sizeof scal, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    // an invalid point has no vertex: its id would be read from outside the scan
+    if (e == hipSuccess && vertex_of && scal[0] == 0x7fffffff)
+        e = hipMemcpy(vertex_of, dIds, (size_t)n * 4, hipMemcpyDeviceToHost);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform from points: ") + hipGetErrorString(e));
+    if (scal[0] != 0x7fffffff)
+        return fail(AVR_ERR_ARG, "graph uniform: vertex " + std::to_string(scal[0]) + ": coordinate outside +-2^20");
+    *count = scal[1];
+    return AVR_OK;
+}
+
+// One flood on the device (k_graph_voxels_level), level by level from the frontier the host
+// state starts with; the state is uploaded before and read back after
+int voxels_flood_device(avr_context *c, avr::graph::Voxels &vx, bool fill, const std::vector<int> &start, int *levels) {
+    HIP_TRY(hipSetDevice(c->device));
+    const avr::graph::VoxelDims d = vx.Dims();
+    const size_t szS = vx.StateBytes(), szQ = ((size_t)d.cells * 4 + 15) & ~(size_t)15;
+    char *buf = nullptr;
+    HIP_TRY(dalloc(&buf, ((szS + 15) & ~(size_t)15) + 2 * szQ + 16));
+    unsigned *dState = (unsigned *)buf;
+    int *dQ[2] = {(int *)(buf + ((szS + 15) & ~(size_t)15)), nullptr};
+    dQ[1] = (int *)((char *)dQ[0] + szQ);
+    int *dN = (int *)((char *)dQ[1] + szQ);
+    hipError_t e = hipMemcpyAsync(dState, vx.State(), szS, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dQ[0], start.data(), start.size() * 4, hipMemcpyHostToDevice, c->stream);
+    int nFront = (int)start.size(), lv = 0, cur = 0;
+    long long seen = nFront;
+    // each cell joins a frontier at most once, so the levels cannot outnumber the cells
+    while (e == hipSuccess && nFront > 0 && lv < d.cells) {
+        ++lv;
+        e = hipMemsetAsync(dN, 0, sizeof(int), c->stream);
+        if (e != hipSuccess) break;
+        const int blocks = blocks_for(nFront, 256, 256 * 64);
+        if (fill)
+            hipLaunchKernelGGL((avr::k_graph_voxels_level<1>), dim3(blocks), dim3(256), 0, c->stream, d, dState, dQ[cur], nFront,
+                               dQ[cur ^ 1], dN);
+        else
+            hipLaunchKernelGGL((avr::k_graph_voxels_level<0>), dim3(blocks), dim3(256), 0, c->stream, d, dState, dQ[cur], nFront,
+                               dQ[cur ^ 1], dN);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&nFront, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        cur ^= 1;
+        seen += nFront;
+        if (e == hipSuccess && (nFront < 0 || seen > d.cells)) {
+            (void)hipFree(buf);
+            return fail(AVR_ERR_HIP, "graph voxels: frontier count out of range");
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpy(vx.State(), dState, szS, hipMemcpyDeviceToHost);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph voxels flood: ") + hipGetErrorString(e));
+    if (levels) *levels = lv;
+    return AVR_OK;
+}
+
+}  // namespace
+
+struct avr_graph_voxels {
+    avr::graph::Voxels v;
+};
+
+extern "C" {
+
+int avr_graph_uniform_count_device(avr_context *c, long long n, const float *xyz, float spacing, long long *count) {
+    if (!count) return fail(AVR_ERR_ARG, "null out");
+    return uniform_points_device(c, n, xyz, spacing, count, nullptr);
+}
+
+int avr_graph_uniform_from_points_device(avr_context *c, long long n, const float *xyz, float spacing,
+                                         avr_graph_uniform **out, int *vertex_of) {
+    if (!out) return fail(AVR_ERR_ARG, "null out");
+    *out = nullptr;
+    std::vector<int> own;
+    if (!vertex_of && n >= 1 && n <= 0x3fffffff) {
+        own.resize((size_t)n);
+        vertex_of = own.data();
+    }
+    long long m = 0;
+    const int rc = uniform_points_device(c, n, xyz, spacing, &m, vertex_of);
+    if (rc) return rc;
+    // ids follow the first appearance: the point that brings id `next` is that vertex's first
+    std::vector<int> coors((size_t)m * 3);
+    long long next = 0;
+    for (long long i = 0; i < n && next < m; ++i)
+        if (vertex_of[i] == next) {
+            (void)avr::graph::uniform_coors(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], spacing, coors.data() + 3 * next);
+            ++next;
+        }
+    if (next != m) return fail(AVR_ERR_HIP, "graph uniform from points: device ids are not in order of first appearance");
+    const std::vector<float> light((size_t)m, 0.f);
+    auto *u = new avr_graph_uniform();
+    const std::string msg = u->u.Create(m, coors.data(), light.data(), spacing);
+    if (!msg.empty()) {
+        delete u;
+        return fail(AVR_ERR_ARG, msg);
+    }
+    u->uid = ++g_index_uid;
+    *out = u;
+    return AVR_OK;
+}
+
+int avr_graph_voxels_create(const float pmin[3], const float pmax[3], float spacing, long long m, const int *coors,
+                            avr_graph_voxels **out) {
+    if (!out) return fail(AVR_ERR_ARG, "null out");
+    *out = nullptr;
+    auto *v = new avr_graph_voxels();
+    const std::string msg = v->v.Create(pmin, pmax, spacing, m, coors);
+    if (!msg.empty()) {
+        delete v;
+        return fail(AVR_ERR_ARG, msg);
+    }
+    *out = v;
+    return AVR_OK;
+}
+int avr_graph_voxels_destroy(avr_graph_voxels *v) {
+    delete v;
+    return AVR_OK;
+}
+int avr_graph_voxels_single_layer(avr_context *c, avr_graph_voxels *v, int *levels) {
+    if (!v) return fail(AVR_ERR_ARG, "null voxels");
+    if (!c) {
+        v->v.SingleLayer(levels);
+        return AVR_OK;
+    }
+    std::vector<int> start;
+    v->v.BeginSingleLayer(&start);
+    const int rc = voxels_flood_device(c, v->v, false, start, levels);
+    if (rc == AVR_OK) v->v.SetSingleDone();
+    return rc;
+}
+int avr_graph_voxels_fill(avr_context *c, avr_graph_voxels *v, int start, int *levels) {
+    if (!v) return fail(AVR_ERR_ARG, "null voxels");
+    if (!v->v.SingleDone()) {   // FillInside runs the single layer first when it has not run (:184-186)
+        const int rc = avr_graph_voxels_single_layer(c, v, nullptr);
+        if (rc) return rc;
+    }
+    if (!c) {
+        const std::string msg = v->v.Fill(start, levels);
+        return msg.empty() ? AVR_OK : fail(AVR_ERR_ARG, msg);
+    }
+    std::vector<int> seeds;
+    const std::string msg = v->v.BeginFill(start, &seeds);
+    if (!msg.empty()) return fail(AVR_ERR_ARG, msg);
+    return voxels_flood_device(c, v->v, true, seeds, levels);
+}
+int avr_graph_voxels_state(const avr_graph_voxels *v, int lo[3], int n[3], unsigned char *state, long long capacity) {
+    if (!v) return fail(AVR_ERR_ARG, "null voxels");
+    const avr::graph::VoxelDims &d = v->v.Dims();
+    for (int a = 0; a < 3; ++a) {
+        if (lo) lo[a] = d.lo[a];
+        if (n) n[a] = d.n[a];
+    }
+    if (state) {
+        if (capacity < d.cells) return fail(AVR_ERR_ARG, "graph voxels: state buffer shorter than the cell count");
+        std::memcpy(state, v->v.State(), (size_t)d.cells);
+    }
+    return AVR_OK;
+}
+int avr_graph_voxels_visited(const avr_graph_voxels *v, long long *visited, long long *cast, long long *single_layer,
+                             long long *filled) {
+    if (!v) return fail(AVR_ERR_ARG, "null voxels");
+    if (visited) *visited = v->v.Count(avr::graph::kVoxOutside);
+    if (cast) *cast = v->v.Count(avr::graph::kVoxCast);
+    if (single_layer) *single_layer = v->v.Count(avr::graph::kVoxSingle);
+    if (filled) *filled = v->v.Count(avr::graph::kVoxFilled);
+    return AVR_OK;
+}
+
 }  // extern "C"

@@ -53,6 +53,12 @@ vertex part), UniformGraph.save / load_uniform go through the reference's file f
 GraphIntegrator renders from it when handed a capi.GraphUniform: the scatter point's voxel is
 looked up in one hash table (k_graph_render_uniform), with no radius search; voxel_view=True is
 --graph-debug's view of the lit voxels.
+
+The voxel boundary (VoxelBoundary, voxels/voxel_boundary.cpp) makes a uniform graph straight
+from the medium: ray bundles from a sphere of points capture where the majorant grid first is
+not empty (k_graph_capture), the points go onto the lattice (k_graph_uniform_insert), one flood
+thins them to a single layer and another fills the inside (k_graph_voxels_level, or the same
+cell rules on the host).
 """
 import json
 import math
@@ -353,6 +359,227 @@ def load_uniform(path):
         raise ValueError(f"{path}: no vertices")
     order = g.file_ids
     return UniformGraph(capi.GraphUniform.from_points(g.points[order], g.light_scalar[order], g.spacing, reduce="first"))
+
+
+# ---------------------------------------------------------------------------
+# Voxel boundary (voxels/voxel_boundary.{h,cpp})
+
+_PI = f32(3.14159265358979323846)
+
+
+def _rotate_x(deg):   # RotateX (transform.cpp:49-57), the 3x3 part
+    rad = f32(f32(_PI / f32(180)) * f32(deg))
+    s, c = f32(np.sin(rad)), f32(np.cos(rad))
+    return np.array([[1, 0, 0, 0], [0, c, -s, 0], [0, s, c, 0]], f32)
+
+
+def _spherical_direction(sin_t, cos_t, phi):   # vecmath.h:1666-1673
+    st, ct = f32(min(max(sin_t, f32(-1)), f32(1))), f32(min(max(cos_t, f32(-1)), f32(1)))
+    return np.array([f32(st * f32(np.cos(f32(phi)))), f32(st * f32(np.sin(f32(phi)))), ct], f32)
+
+
+def sphere_surface_points(center, radius, equator_step_degrees):
+    """util::GetSphereSurfacePoints (util.h:134-176) in its float operation order: rings of
+    points from the equator (elevation 0) up to the pole in steps of equator_step_degrees, the
+    step in phi widened by the ring's radius ratio; every elevation other than 0 gives an up
+    point and a down point per phi. Returns (n, 3) float32 in the reference's order. ValueError
+    unless 0 < step <= 90. sin and cos are the platform's float routines, as in the reference
+    (std::sin / std::cos of a float): they are not pinned, so the last bit of a point may differ
+    between platforms."""
+    step = f32(equator_step_degrees)
+    if not (step > 0 and step <= 90):
+        raise ValueError("Step must be between 0 and 90 degrees")
+    center = np.asarray(center, f32).reshape(3)
+    radius = f32(radius)
+    to_world = _rotate_x(-90)
+    pts = []
+    elevation = f32(0)
+    with np.errstate(divide="ignore", over="ignore"):
+        while elevation <= 90:
+            rad = f32(f32(f32(f32(90) - elevation) * _PI) / f32(180))
+            sin_t, cos_t = f32(np.sin(rad)), f32(np.cos(rad))
+            rad_down = f32(f32(f32(f32(90) + elevation) * _PI) / f32(180))
+            sin_d, cos_d = f32(np.sin(rad_down)), f32(np.cos(rad_down))
+            d = _xf_vector(to_world, _spherical_direction(sin_t, cos_t, f32(0)))
+            ratio = f32(np.sqrt(f32(f32(f32(d[0] * d[0]) + f32(0)) + f32(d[2] * d[2]))))
+            phi_step = f32(step / ratio)
+            # at least two points on a circle, except for the pole
+            if phi_step >= 180 and float(ratio) > 1e-6:
+                break
+            phi = f32(0)
+            while phi < 360:
+                phi_rad = f32(f32(phi * _PI) / f32(180))
+                up = _xf_vector(to_world, _spherical_direction(sin_t, cos_t, phi_rad))
+                pts.append((center + (up * radius).astype(f32)).astype(f32))
+                if elevation != 0:
+                    down = _xf_vector(to_world, _spherical_direction(sin_d, cos_d, phi_rad))
+                    pts.append((center + (down * radius).astype(f32)).astype(f32))
+                phi = f32(phi + phi_step)
+            elevation = f32(elevation + step)
+    return np.array(pts, f32).reshape(-1, 3)
+
+
+class VoxelBoundary:
+    """graph::VoxelBoundary (voxels/voxel_boundary.cpp): a medium to a voxel set. Ray bundles
+    shot at the medium from a sphere around it keep the first non-empty majorant cell they meet
+    (capture_points, k_graph_capture); the points go onto the lattice of a spacing and a flood
+    from outside thins them to the voxels that touch the outside (capture_boundary); a flood
+    from that boundary fills the inside (fill_inside). Every result is a UniformGraph with
+    lights 0; the filled one's points, lit by Context.graph_light, make a uniform lighting graph
+    straight from the medium, with no walks and no merge.
+
+    Bundles (CaptureBoundary :15-31): origin = a point of sphere_surface_points(bounds_center,
+    2 max_dist_to_center, equator_step); dir = bounds_center - origin, not normalised;
+    (xv, yv) = CoordinateSystem(dir) * (max_dist_to_center / num_steps); (2 num_steps + 1)^2 rays
+    per bundle. frame="reference" hands CoordinateSystem the un-normalised dir, as the reference
+    does: the function assumes a unit vector, so the frame is skewed and not of unit length.
+    frame="orthonormal", a deviation, builds the frame from normalize(dir); the rays still run
+    along dir itself. num_steps is the reference's constant 100.
+
+    device=False runs the conversion and the floods on the host (the capture itself is device
+    code); ctx may then be None when points are handed to capture_boundary."""
+
+    def __init__(self, ctx, medium_data, num_steps=100, frame="reference", device=True):
+        if frame not in ("reference", "orthonormal"):
+            raise ValueError('frame must be "reference" or "orthonormal"')
+        if int(num_steps) < 1:
+            raise ValueError("num_steps must be at least 1")
+        self.ctx = ctx
+        self.md = medium_data
+        self.num_steps = int(num_steps)
+        self.frame = frame
+        self.device = bool(device)
+        self.seconds = {}
+        if ctx is not None and getattr(medium_data, "geometry", None) is not None:
+            ctx.set_graph_geometry(medium_data.geometry)
+
+    def bundles(self, equator_step=10.0):
+        """(origin, dir, xv, yv), (n, 3) float32 each: one bundle per sphere point."""
+        md = self.md
+        ctr = np.asarray(md.bounds_center, f32)
+        origins = sphere_surface_points(ctr, f32(md.max_dist_to_center * f32(2)), equator_step)
+        step = f32(md.max_dist_to_center / f32(self.num_steps))
+        dirs, xs, ys = [], [], []
+        for o in origins:
+            d = (ctr - o).astype(f32)
+            basis = d
+            if self.frame == "orthonormal":
+                ln = f32(np.sqrt(f32(f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2]))))
+                basis = (d / ln).astype(f32)
+            xv, yv = coordinate_system(basis)
+            dirs.append(d)
+            xs.append((xv * step).astype(f32))
+            ys.append((yv * step).astype(f32))
+        return origins, np.array(dirs, f32), np.array(xs, f32), np.array(ys, f32)
+
+    def capture_points(self, equator_step=10.0):
+        """CaptureBoundary(equatorStepSize) (:13-62): the captured points, (k, 3) float32 in ray
+        order (bundle, i, j). last_rays holds the number of rays shot."""
+        o, d, xv, yv = self.bundles(equator_step)
+        t0 = time.perf_counter()
+        pts, flag, _ = self.ctx.graph_capture(o, d, xv, yv, self.num_steps)
+        self.seconds["capture"] = time.perf_counter() - t0
+        self.last_rays = len(flag)
+        return np.ascontiguousarray(pts[flag])
+
+    def _count(self, points, spacing):
+        if self.device:
+            return self.ctx.graph_uniform_count(points, spacing)
+        return capi.GraphUniform.from_points(points, np.zeros(len(points), f32), spacing).num_vertices
+
+    def _to_uniform(self, points, spacing):
+        if self.device:
+            return capi.GraphUniform.from_points_device(self.ctx, points, spacing)
+        return capi.GraphUniform.from_points(points, np.zeros(len(points), f32), spacing)
+
+    def bisect_spacing(self, points, wanted_vertices, count=None):
+        """CaptureBoundary(wantedVertices)'s search (:64-91) in float32: spacingGTE1 = count(1)
+        >= wanted; ten steps of middle = min + (max - min) / 2 over [1, 1000], the spacing tried
+        middle / (spacingGTE1 ? 1 : 1000); count > wanted moves min, else max. Returns every
+        spacing tried in order; the last is the graph's."""
+        count = count or (lambda s: self._count(points, s))
+        wanted = int(wanted_vertices)
+        gte1 = count(f32(1)) >= wanted
+        lo, hi, tried = f32(1), f32(1000), []
+        for _ in range(10):
+            middle = f32(lo + f32(f32(hi - lo) / f32(2)))
+            spacing = f32(middle / (f32(1) if gte1 else f32(1000)))
+            tried.append(spacing)
+            if count(spacing) > wanted:
+                lo = middle
+            else:
+                hi = middle
+        return tried
+
+    def capture_boundary(self, spacing=None, wanted_vertices=None, equator_step=10.0, points=None):
+        """CaptureBoundary(spacing, equatorStepSize) (:97-104) or CaptureBoundary(wantedVertices,
+        equatorStepSize) (:64-95): the captured points (or `points`) on the lattice of the
+        spacing, thinned to a single layer. The UniformGraph returned holds the surviving
+        vertices in ascending old id, renumbered from 0; old_to_new maps every vertex of the
+        unthinned graph to its new id or -1, old_ids back; visited is the reference's numVisited,
+        num_captured the vertices before thinning, spacings_tried the bisection's."""
+        if (spacing is None) == (wanted_vertices is None):
+            raise ValueError("capture_boundary: exactly one of spacing and wanted_vertices")
+        if points is None:
+            points = self.capture_points(equator_step)
+        points = np.ascontiguousarray(points, f32).reshape(-1, 3)
+        tried = None
+        t0 = time.perf_counter()
+        if spacing is None:
+            tried = self.bisect_spacing(points, wanted_vertices)
+            spacing = tried[-1]
+        full = self._to_uniform(points, f32(spacing))
+        self.seconds["to_uniform"] = time.perf_counter() - t0
+        g = self.to_single_layer(UniformGraph(full))
+        g.spacings_tried = tried
+        return g
+
+    def to_single_layer(self, graph):
+        """ToSingleLayerAndSaveCast (:122-181) on a UniformGraph: a new graph of the vertices that
+        touch the outside; the flood's state (the cast set) stays with it for fill_inside."""
+        md = self.md
+        vox = capi.GraphVoxels(md.pmin, md.pmax, graph.spacing, graph.coors)
+        t0 = time.perf_counter()
+        levels = vox.single_layer(self.ctx if self.device else None)
+        self.seconds["single_layer"] = time.perf_counter() - t0
+        keep = (vox.vertex_bits() & capi.VOXEL_SINGLE) != 0
+        old_ids = np.nonzero(keep)[0].astype(np.int32)
+        if len(old_ids) == 0:
+            raise ValueError("single layer: no vertex touches the outside")
+        old_to_new = np.full(len(keep), -1, np.int32)
+        old_to_new[old_ids] = np.arange(len(old_ids), dtype=np.int32)
+        g = UniformGraph(capi.GraphUniform(graph.coors[old_ids], np.zeros(len(old_ids), f32), graph.spacing))
+        g.old_to_new, g.old_ids = old_to_new, old_ids
+        g.num_captured = graph.num_vertices
+        g.visited, g.levels = vox.counts()[0], levels
+        g.spacings_tried = None
+        g.voxels = vox
+        return g
+
+    def fill_inside(self, boundary, start=None):
+        """FillInside (:183-225): a UniformGraph of every cell a 6-neighbour flood reaches from
+        the boundary without entering a cast cell. start: a vertex id of `boundary`; None takes
+        the lowest, "all" floods from every vertex, which also fills several disjoint blobs. The
+        reference starts from unordered_map::begin(), which is unspecified, and numbers the
+        filled vertices in the flood's FIFO order from there; here the ids run in ascending
+        (z, y, x). A graph that has not been through to_single_layer goes through it first
+        (:184-186); start is then one of its own ids that survives."""
+        vox = getattr(boundary, "voxels", None) if hasattr(boundary, "old_ids") else None
+        s = start
+        if vox is None:
+            vox = self.to_single_layer(boundary).voxels
+        elif start is not None and start != "all" and start != "lowest":
+            if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= start < len(boundary.old_ids):
+                raise ValueError(f"fill_inside: start {start!r} is no vertex of the boundary")
+            s = int(boundary.old_ids[start])
+        t0 = time.perf_counter()
+        levels = vox.fill(self.ctx if self.device else None, s)
+        self.seconds["fill"] = time.perf_counter() - t0
+        coors = vox.cells_with(capi.VOXEL_FILLED)
+        g = UniformGraph(capi.GraphUniform(coors, np.zeros(len(coors), f32), boundary.spacing))
+        g.levels = levels
+        g.voxels = vox
+        return g
 
 
 def load_index(path):

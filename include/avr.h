@@ -744,6 +744,70 @@ int avr_graph_uniform_trace_device(avr_context *ctx, const avr_graph_uniform *u,
 int avr_graph_render_uniform(avr_context *ctx, const avr_graph_uniform *u, const float graph_from_render[16],
                              int spp_begin, int spp_end, int seed, int view, float light_scale);
 
+/* The voxel boundary, graph::VoxelBoundary (graph/voxels/voxel_boundary.cpp): a medium to a
+ * voxel set in three steps: capture, single layer, fill.
+ *
+ * avr_graph_capture: CaptureBoundary's ray bundles (:13-62) on the device (k_graph_capture, one
+ * lane per ray). Bundle b has origin, dir, xvec, yvec (n_bundles*3 each, the caller's: the
+ * reference takes origin on a sphere around the medium, dir = bounds_center - origin, not
+ * normalised, and (xvec, yvec) = CoordinateSystem(dir) * step); its (2 num_steps + 1)^2 rays
+ * are (i, j) in [-num_steps, num_steps]^2, i outer, from p = (origin + xvec * (float)i) + yvec
+ * * (float)j along dir. Per ray GetHits(primitive) of avr_graph_set_geometry: a miss captures
+ * nothing, and neither does a start inside the primitive (the reference skips to the exit hit;
+ * no medium lies beyond it); a ray from outside moves to its entry (SkipIntersection, no
+ * offset) and runs the medium's majorant DDA with dir as given (SampleRay does not normalise)
+ * and tMax = Infinity; the first segment with sigma_t[0] * majorant != 0 (sigma_t at the
+ * graph tools' defaultLambda) gives the point p + dir * tMin. out_points4: 4 floats per ray in
+ * ray order (bundle, i, j): x, y, z and 1 for a captured point, zeros without one;
+ * *n_captured: how many. Every medium type avr_graph_walks takes; AVR_ERR_STATE without a
+ * medium; AVR_ERR_ARG: a null pointer, n_bundles < 1, num_steps < 0, more than 2^31 - 1 rays.
+ * Host arrays, synchronous.
+ *
+ * avr_graph_uniform_count_device / avr_graph_uniform_from_points_device:
+ * avr_graph_uniform_from_points(reduce 0, lights 0) for points on the device
+ * (k_graph_uniform_insert: one lane per point inserts its voxel key into an open-addressing
+ * set with a 64-bit compare-and-swap and keeps the key's lowest point index with an atomic
+ * min, so the result does not depend on scheduling; ids by a scan in the order of first
+ * appearance): the number of distinct voxels, and the graph with bitwise the host's
+ * coordinates, ids and vertex_of (n, may be NULL). The host routine's AVR_ERR_ARG cases and
+ * messages, the lowest invalid point named.
+ *
+ * avr_graph_voxels_*: the two floods (csrc/avr_graph_voxels.h). The state is one byte per cell
+ * of the dense lattice over FitBounds (util.h:313-317): lo = FitToGraph(pmin) - 1, hi =
+ * FitToGraph(pmax) + 1, inclusive, pmin / pmax the bounds of the medium's primitive; x fastest.
+ * Bits: 1 boundary vertex, 2 outside (visited by the first flood), 4 cast, 8 single-layer
+ * vertex, 16 filled. _create takes the m vertices' lattice coordinates (m*3); AVR_ERR_ARG for
+ * a spacing that is not positive and finite, m < 1, more than 2^31 - 1 cells, a vertex
+ * outside the bounds or repeated.
+ * _single_layer, ToSingleLayerAndSaveCast (:122-181): a 6-neighbour flood from lo over the
+ * cells that are not vertices; a visited cell with a vertex neighbour is cast, a vertex with a
+ * visited neighbour is single-layer. The reference's three-set scheme is a level-synchronous
+ * breadth-first search that visits each cell once; its numVisited is _visited's `visited`.
+ * _fill, FillInside (:183-225): a 6-neighbour flood over every cell that is not cast, from the
+ * single-layer vertex `start` (an index into _create's vertices), from the lowest one (-1) or
+ * from all of them (-2); the reference starts from unordered_map::begin(), which is
+ * unspecified. It runs the single layer first when that has not run (:184-186). AVR_ERR_ARG
+ * for a start that is no single-layer vertex.
+ * ctx NULL runs a flood on the host (plain breadth-first loops); with a context it runs on the
+ * device, one launch per level over a frontier list (k_graph_voxels_level), the frontier count
+ * read back per level, and leaves bytewise the host's state. levels (may be NULL): the levels
+ * run. _state: lo, n (cells per axis) and the state bytes (capacity: the buffer's size; any
+ * of the three may be NULL). _visited: the cells with bit 2, 4, 8 and 16 (each may be NULL). */
+typedef struct avr_graph_voxels avr_graph_voxels;
+int avr_graph_capture(avr_context *ctx, int n_bundles, const float *origin, const float *dir, const float *xvec,
+                      const float *yvec, int num_steps, float *out_points4, long long *n_captured);
+int avr_graph_uniform_count_device(avr_context *ctx, long long n, const float *xyz, float spacing, long long *count);
+int avr_graph_uniform_from_points_device(avr_context *ctx, long long n, const float *xyz, float spacing,
+                                         avr_graph_uniform **out, int *vertex_of);
+int avr_graph_voxels_create(const float pmin[3], const float pmax[3], float spacing, long long m, const int *coors,
+                            avr_graph_voxels **out);
+int avr_graph_voxels_destroy(avr_graph_voxels *v);
+int avr_graph_voxels_single_layer(avr_context *ctx, avr_graph_voxels *v, int *levels);
+int avr_graph_voxels_fill(avr_context *ctx, avr_graph_voxels *v, int start, int *levels);
+int avr_graph_voxels_state(const avr_graph_voxels *v, int lo[3], int n[3], unsigned char *state, long long capacity);
+int avr_graph_voxels_visited(const avr_graph_voxels *v, long long *visited, long long *cast, long long *single_layer,
+                             long long *filled);
+
 /* IntegrationAnalyzer's Analyze (graph/analysis/integration_analyzer.cpp:56-83) for n points
  * already in graph space; host code, no GPU needed. node[i] = 1 when radiusSearch(point,
  * Sqr(vertex_radius)) returns a vertex (d2 < r2 strictly, d2 as avr_graph_index_connect's).

@@ -9,6 +9,9 @@ usage: python tools/graph_maker.py [--scene s-cloud] [--n 64] [--config CONFIG.j
                                    [--precision 9] [--search-ranges device] [--sampler 0] [--seed 0]
                                    [--interface-sphere CX,CY,CZ,R] [--merge host]
                                    [--uniform SPACING [--uniform-reduce first|mean]]
+                                   [--voxels SPACING | --wanted-vertices N] [--equator-step 10]
+                                   [--capture-steps 100] [--fill-start ID|all] [--node-radius R]
+                                   [--voxels-host]
 
 --interface-sphere bounds the medium by a sphere (world space): the scene gets it as its
 interface and the graph is made with the sphere as the primitive (primitive="interface").
@@ -18,6 +21,16 @@ interface and the graph is made with the sphere as the primitive (primitive="int
 vertex's, as in the reference, or their mean) and writes PREFIX_d{depth}_uniform.txt, which
 GraphIntegrator.from_file renders with the uniform branch; such a graph's light already carries
 Inv4Pi, so it takes light_scale=1.
+
+--voxels SPACING (or --wanted-vertices N, the reference's bisection for a spacing) makes the
+uniform graph straight from the medium instead, with no walks and no merge (graph.VoxelBoundary):
+ray bundles from a sphere of points --equator-step degrees apart, (2 --capture-steps + 1)^2 rays
+each, capture the medium's boundary; the points go onto the lattice and are thinned to a single
+layer; a flood from it (--fill-start: a boundary vertex id, the lowest by default, or all) fills
+the inside. The filled points are lit by the light vector alone (the config's
+lightingCalculator values; the node radius is FreeGraphBuilder's default or --node-radius) and
+written to PREFIX_voxels.txt, which graph.load_uniform reads and tools/graph_render_demo.py
+renders; the light already carries Inv4Pi, so it takes light_scale=1.
 
 CONFIG.json is the reference's graph config (graphBuilder / lightingCalculator, util.h:750-812);
 without one the defaults below are used.
@@ -86,7 +99,84 @@ def parser():
                    help="also write PREFIX_d{depth}_uniform.txt, the uniform graph of this spacing")
     p.add_argument("--uniform-reduce", choices=("first", "mean"), default="first",
                    help="the light of a voxel that holds several vertices")
+    p.add_argument("--voxels", type=float, metavar="SPACING",
+                   help="write PREFIX_voxels.txt instead: the voxel boundary of the medium at this spacing, filled and lit")
+    p.add_argument("--wanted-vertices", type=int, metavar="N",
+                   help="as --voxels, with the spacing found by the reference's bisection for N boundary vertices")
+    p.add_argument("--equator-step", type=float, default=10, metavar="DEG", help="degrees between capture sphere points")
+    p.add_argument("--capture-steps", type=int, default=100, metavar="N", help="(2 N + 1)^2 rays per capture bundle")
+    p.add_argument("--fill-start", metavar="ID|all", help="the boundary vertex the fill starts from (default: the lowest)")
+    p.add_argument("--node-radius", type=float, help="the light vector's vertex radius (default: FreeGraphBuilder's)")
+    p.add_argument("--voxels-host", action="store_true",
+                   help="with --voxels: also run the conversion and the floods on the host, compare and time them")
     return p
+
+
+def fill_start(text):
+    """--fill-start: None (the lowest vertex), "all" or a vertex id."""
+    if text is None or text == "all":
+        return text
+    try:
+        return int(text)
+    except ValueError:
+        raise ValueError(f"--fill-start {text!r}: a boundary vertex id or 'all'")
+
+
+def make_voxels(a, ctx, md, in_dir, smp, cfg, seconds):
+    """The --voxels / --wanted-vertices run: capture, single layer, fill, light, write."""
+    from acceleratedvolrenderer_amd import graph
+    if a.voxels is not None and a.wanted_vertices is not None:
+        raise SystemExit("--voxels and --wanted-vertices exclude each other")
+    vb = graph.VoxelBoundary(ctx, md, num_steps=a.capture_steps)
+    points = vb.capture_points(a.equator_step)
+    boundary = vb.capture_boundary(spacing=a.voxels, wanted_vertices=a.wanted_vertices, points=points)
+    filled = vb.fill_inside(boundary, start=fill_start(a.fill_start))
+    seconds.update(vb.seconds)
+    radius = a.node_radius if a.node_radius is not None else float(
+        graph.same_spot_radius(md) * np.float32(cfg.graph_builder.radius_modifier))
+    lc = cfg.lighting_calculator
+    t0 = time.perf_counter()
+    light = ctx.graph_light(smp.struct(), filled.points, in_dir, radius, lc.points_on_radius_light, lc.light_iterations,
+                            md.max_dist_to_center)
+    seconds["light_vector"] = time.perf_counter() - t0
+    lit = graph.UniformGraph(graph.capi.GraphUniform(filled.coors, light, filled.spacing))
+    t0 = time.perf_counter()
+    name = f"{a.out}_voxels.txt"
+    lit.save(name, precision=a.precision)
+    seconds["write"] = time.perf_counter() - t0
+    stats = {
+        "spacing": float(boundary.spacing), "rays": int(vb.last_rays), "captured_points": int(len(points)),
+        "vertices": {"captured": int(boundary.num_captured), "single_layer": int(boundary.num_vertices),
+                     "filled": int(filled.num_vertices)},
+        "visited_cells": int(boundary.visited), "cells": int(boundary.voxels.cells),
+        "levels": {"single_layer": int(boundary.levels), "fill": int(filled.levels)},
+        "capture_rays_per_second": vb.last_rays / max(seconds["capture"], 1e-12),
+        "node_radius": radius, "light_average": float(np.mean(light, dtype=np.float64)), "file": name,
+        "seconds": seconds,
+    }
+    print(f"voxels: {stats['vertices']['captured']} captured, {stats['vertices']['single_layer']} single layer, "
+          f"{stats['vertices']['filled']} filled; {stats['visited_cells']} cells visited")
+    for stage in ("capture", "to_uniform", "single_layer", "fill", "light_vector", "write"):
+        print(f"  {stage}: {seconds[stage]:.4f} s")
+    if a.voxels_host:
+        # the same conversion and floods on the host, for the clock and as a check
+        host = graph.VoxelBoundary(None, md, num_steps=a.capture_steps, device=False)
+        t0 = time.perf_counter()
+        full_d = graph.capi.GraphUniform.from_points_device(ctx, points, boundary.spacing)
+        one_device = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        full_h = graph.capi.GraphUniform.from_points(points, np.zeros(len(points), np.float32), boundary.spacing)
+        one_host = time.perf_counter() - t0
+        hb = host.to_single_layer(graph.UniformGraph(full_h))
+        hf = host.fill_inside(hb, start=fill_start(a.fill_start))
+        same = bool(np.array_equal(full_d.coors, full_h.coors) and np.array_equal(full_d.vertex_of, full_h.vertex_of) and
+                    np.array_equal(hb.voxels.state(), boundary.voxels.state()) and np.array_equal(hf.coors, filled.coors))
+        stats["host"] = {"same_result": same, "levels": {"single_layer": int(hb.levels), "fill": int(hf.levels)},
+                         "seconds": {"from_points": one_host, "from_points_device": one_device,
+                                     "single_layer": host.seconds["single_layer"], "fill": host.seconds["fill"]}}
+        print(f"  host: from_points {one_host:.4f} s (device {one_device:.4f} s), single_layer "
+              f"{host.seconds['single_layer']:.4f} s, fill {host.seconds['fill']:.4f} s; same result: {same}")
+    return stats
 
 
 def main(argv=None):
@@ -109,6 +199,15 @@ def main(argv=None):
     in_dir = (-np.asarray(scene.light_w[0], np.float32)).astype(np.float32)   # the way the light travels
     smp = graph.GraphSampling.for_config(cfg, sampler=a.sampler, seed=a.seed)
     seconds["scene"] = time.perf_counter() - t0
+
+    if a.voxels is not None or a.wanted_vertices is not None:
+        stats = make_voxels(a, ctx, md, in_dir, smp, cfg, seconds)
+        ctx.close()
+        stats["scene"], stats["primitive"] = f"{a.scene} {a.n}^3", primitive
+        with open(f"{a.out}_voxels_stats.json", "w") as fh:
+            json.dump(stats, fh, indent=4)
+            fh.write("\n")
+        return 0
 
     # BuildGraph without the ranges, then ComputeSearchRanges on its own clock
     active = bool(cfg.graph_builder.render_search_range.get("active"))

@@ -20,6 +20,9 @@ the same process: 16 spp, the two alternately, three timed runs each after one w
 median and spread of ms_medium and ms_total, and the share of the 1-spp pass's scatters that
 find a vertex, for both kinds. --voxel-view also times --graph-debug's voxel view once and
 writes its EXR.
+
+--graph-file PATH renders a graph file instead (free or uniform, e.g. tools/graph_maker.py
+--voxels' PREFIX_voxels.txt, made for the same --n): one 16-spp render, its EXR and times.
 """
 import argparse
 import json
@@ -65,6 +68,8 @@ def parser():
     p.add_argument("--uniform", metavar="SPACING", help="also render the uniform graph of this spacing (number, or Nr = N vertex radii)")
     p.add_argument("--uniform-reduce", choices=("first", "mean"), default="first")
     p.add_argument("--voxel-view", action="store_true", help="with --uniform: also render the voxel view")
+    p.add_argument("--graph-file", metavar="PATH",
+                   help="render this graph file (made by tools/graph_maker.py for the same --n) instead of building a graph")
     return p
 
 
@@ -130,6 +135,26 @@ def compare_uniform(a, integ, g, light_scalar, out):
               res["free_16spp"]["ms_medium"]["min"], res["free_16spp"]["ms_medium"]["max"], found["uniform"], found["free"]))
 
 
+def render_file(a, scene, primitive):
+    """--graph-file: render a graph file made for this scene (tools/graph_maker.py's PREFIX_d*.txt,
+    PREFIX_d*_uniform.txt or PREFIX_voxels.txt) at 16 spp; its light carries Inv4Pi, so a
+    uniform graph takes light_scale 1."""
+    from acceleratedvolrenderer_amd import GraphIntegrator
+    integ = GraphIntegrator.from_file(scene, a.graph_file, spp=16, seed=0, primitive=primitive, light_scale=1.0)
+    out = {"scene": f"S-cloud GridMedium {a.n}^3, distant light, {a.width}x{a.height}, zsobol + gaussian",
+           "primitive": primitive, "graph_file": a.graph_file, "vertices": int(integ.index.num_vertices)}
+    integ.render(0, 1)
+    c = integ.last_pass(1)["count"]
+    out["scatters_finding_a_vertex_1spp"] = float(np.mean(c[c >= 0] > 0)) if np.any(c >= 0) else 0.0
+    out["graph_render_16spp"] = timed(integ.ctx, lambda: integ.render(0, 16))
+    rgb, w = integ.film_sums()
+    out["graph_image_mean"] = float(integ.write_image(os.path.join(a.out, "graph_file_16spp.exr"), rgb, w, spp=16).mean())
+    integ.close()
+    with open(os.path.join(a.out, "graph_file_render.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
     primitive = "interface" if a.interface_sphere else "box"
@@ -146,6 +171,9 @@ def main(argv=None):
     scene = Scene(cloud.camera, cloud.film, cloud.medium, cloud.lights[:1], sampler=cloud.sampler,   # the distant light
                   interface_sphere=a.interface_sphere)
 
+    if a.graph_file:
+        render_file(a, scene, primitive)
+        return
     integ = GraphIntegrator(scene, None, spp=16, seed=0, primitive=primitive)
     cfg = graph.Config(
         graph.GraphBuilderConfig(radius_modifier=a.radius_modifier, max_depth=a.max_depth, dimension_steps=a.steps,
