@@ -163,6 +163,70 @@ __device__ __forceinline__ float light_pmf(const DevLights &ls, int k) {
     return float(ls.n) / float(ls.n + 0) / ls.n;
 }
 
+// k_paths' copy of what its handlers read per lane of the first kLdsLights lights' records, with
+// the two values the BVH pick and its PMF derive from the light count (the same float
+// operations, evaluated once per block instead of per lane and batch). A lane reaches them with
+// an LDS read where the device array costs a dependent chain through L2 (list pointer, type,
+// then the fields behind the branch on it). Lights past kLdsLights keep the device array, and so
+// do the image-light instantiations (kStaged false; the only ones with the power sampler): they
+// fill their register budget, and the staged reads cost some of them a wave/SIMD or scratch.
+constexpr int kLdsLights = 4;
+struct LdsLight {
+    int type;
+    float w[3];
+    float scale;
+};
+struct LdsLights {
+    LdsLight rec[kLdsLights];
+    float pInf, pmf;                  // light_pick's pInf and pInf / n (== light_pmf's BVH value)
+};
+__device__ __forceinline__ void stage_lights(const DevLights &ls, LdsLights &s) {
+    const int k = threadIdx.x;
+    if (k < kLdsLights && k < ls.n) {
+        const DevLight &g = ls.list[k];
+        LdsLight &r = s.rec[k];
+        r.type = g.type;
+        r.w[0] = g.w[0]; r.w[1] = g.w[1]; r.w[2] = g.w[2];
+        r.scale = g.scale;
+    }
+    if (k == 0) {
+        s.pInf = float(ls.n) / float(ls.n + 0);
+        s.pmf = s.pInf / ls.n;
+    }
+}
+// type, direction and scale of light k (what NEE and the escape read of a record)
+template <bool kStaged>
+__device__ __forceinline__ int light_type(const DevLights &ls, const LdsLights &s, int k) {
+    return kStaged && k < kLdsLights ? s.rec[k].type : ls.list[k].type;
+}
+template <bool kStaged>
+__device__ __forceinline__ V3 light_dir(const DevLights &ls, const LdsLights &s, int k) {
+    const float *w = kStaged && k < kLdsLights ? s.rec[k].w : ls.list[k].w;
+    return {w[0], w[1], w[2]};
+}
+template <bool kStaged>
+__device__ __forceinline__ float light_scale(const DevLights &ls, const LdsLights &s, int k) {
+    return kStaged && k < kLdsLights ? s.rec[k].scale : ls.list[k].scale;
+}
+// light_pick<false> and light_pmf<false> with the staged values (the same operations on the
+// same values); not staged: the functions above
+template <bool kStaged>
+__device__ __forceinline__ int light_pick_staged(const DevLights &ls, const LdsLights &s, float u, float *pmf) {
+    if constexpr (!kStaged) return light_pick<true>(ls, u, pmf);
+    const int nl = ls.n;
+    const float pInf = s.pInf;
+    if (!(u < pInf)) return -1;
+    int idx = (int)(u / pInf * nl);
+    idx = idx < nl - 1 ? idx : nl - 1;
+    *pmf = s.pmf;
+    return idx;
+}
+template <bool kStaged>
+__device__ __forceinline__ float light_pmf_staged(const DevLights &ls, const LdsLights &s, int k) {
+    if constexpr (!kStaged) return light_pmf<true>(ls, k);
+    return s.pmf;
+}
+
 struct DevCamera {
     int type;                         // 0 orthographic, 1 perspective
     float raster[16];                 // cameraFromRaster (full 4x4; perspective is projective)
@@ -1949,6 +2013,14 @@ __global__ void __launch_bounds__(256) k_bin_scatter(const int *__restrict__ que
 #ifndef AVR_KP_BUFMAJ
 #define AVR_KP_BUFMAJ 1
 #endif
+// Sample ids a wave claims from a work head with one atomic. One claim per refill (32 to 64 ids
+// at the default refill threshold) put more than a million returning atomics per pass of the
+// bench on the eight heads, and every refill waited for its own; of 128, 256 and 512 ids per
+// claim, 256 measured best (profiles/service_round_ab.json): larger claims save few further
+// atomics and cost more at a pass's end, where a wave still holds ids while others have run out.
+#ifndef AVR_KP_CHUNK
+#define AVR_KP_CHUNK 256
+#endif
 // Gray GridMedium without emission or image light: the state that only the event handlers and
 // the refill touch (L, the wavelengths, the path direction, the sampler state, the record index
 // and the NEE light) lives in per-lane LDS arrays instead of registers, and the majorant grid
@@ -2126,8 +2198,10 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
     __shared__ float s_maj[kBufMaj ? 1 : 4096];
     // (a gray medium's sigma_a / sigma_s are one value each: the kernel takes them as scalars)
     constexpr int kSigTabs = kGray ? 0 : 2;
-    constexpr int kLdsLights = 4;
     __shared__ float s_tab[(kSigTabs + kLdsLights) * kNTable];
+    // the same lights' records and the light sampler's per-launch values (stage_lights)
+    constexpr bool kStaged = !kImage;
+    __shared__ LdsLights s_lt;
     // ImageInfiniteLight shadow rays (non-delta NEE): the sampled (u, v), p_l and the phase
     // value per lane, parked here while the lane traces its shadow ray (off the VGPR budget)
     __shared__ float4 s_img[kImage ? 256 : 1];
@@ -2180,6 +2254,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
         for (int k = 0; k < nlds; ++k)
             if (P.lights.list[k].type != 2) s_tab[(kSigTabs + k) * kNTable + i] = P.lights.list[k].L[i];
     }
+    if constexpr (kStaged) stage_lights(P.lights, s_lt);
     __syncthreads();
     const float *tab_sa = s_tab, *tab_ss = s_tab + kNTable;
     auto light_table = [&](int k) -> const float * {
@@ -2207,6 +2282,12 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
 
     int mode = M_FETCH, ev = EV_NONE;
     int g = 0;
+    // the wave's claimed sample ids not handed to a lane yet, and whether a claim found every
+    // range used up (wave-uniform: scalar registers)
+    constexpr int kChunk = AVR_KP_CHUNK;
+    static_assert(kChunk >= 64, "a claim covers at least one refill of a whole wave");
+    int chNext = 0, chEnd = 0;
+    bool drained = false;
     const int maj_sy = m.mres[0], maj_sz = m.mres[0] * m.mres[1], maj_n = maj_sz * m.mres[2];
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t majr = maj_rsrc(P.med.majorant, maj_n);
     // path state (Li, integrators.cpp:966-971)
@@ -2320,10 +2401,11 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 const int nl = P.lights.n;
                 if (nl > 0) {
                     float pmf = 0.f;
-                    const int idx = light_pick<kImage>(P.lights, ul, &pmf);
+                    const int idx = light_pick_staged<kStaged>(P.lights, s_lt, ul, &pmf);
                     if (idx >= 0) {
-                        const DevLight &lt = P.lights.list[idx];
-                        if (kImage && lt.type == 2) {
+                        const int ltype = light_type<kStaged>(P.lights, s_lt, idx);
+                        if (kImage && ltype == 2) {
+                            const DevLight &lt = P.lights.list[idx];
                             // ImageInfiniteLight::SampleLi with the compensated distribution
                             // (lights.h:588-613), shadow ray to 2 x sceneRadius (integrators.cpp:1311-1338)
                             float su, sv, lsPdf;
@@ -2350,9 +2432,9 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                                     AVR_COUNT(nShadow, 4);
                                 }
                             }
-                        } else if (lt.type == 0) {
-                            const V3 wi = {lt.w[0], lt.w[1], lt.w[2]};
-                            const Spec Ls = sample_table(light_table(idx), lambda_index(lam)) * lt.scale;
+                        } else if (ltype == 0) {
+                            const V3 wi = light_dir<kStaged>(P.lights, s_lt, idx);
+                            const Spec Ls = sample_table(light_table(idx), lambda_index(lam)) * light_scale<kStaged>(P.lights, s_lt, idx);
                             const float fval = hg_eval_c(dot(wo, wi), m.hg);
                             if (Ls.nonzero() && fval != 0) {
                                 s_ls[threadIdx.x] = to4(Ls);
@@ -2399,8 +2481,8 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 }
                 Spec contrib = Spec::c(0.f);
                 if (snz(T_ray)) {
-                    const DevLight &lt = P.lights.list[light];
-                    if (kImage && lt.type == 2) {
+                    if (kImage && light_type<kStaged>(P.lights, s_lt, light) == 2) {
+                        const DevLight &lt = P.lights.list[light];
                         // non-delta light: r_l *= r_p * p_l, r_u *= r_p * scatterPDF (1391-1398)
                         const float4 im = s_img[threadIdx.x];
                         const S f_hat = sconst<S>(im.w);
@@ -2410,7 +2492,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                         contrib = smul(Ls, beta * f_hat * T_ray) / savg(sr_l + sr_u);
                     } else {
                         // the delta light's spectrum and f_hat of the spawn (same wo, wi)
-                        const float p_l = light_pmf<kImage>(P.lights, light) * 1.f;
+                        const float p_l = light_pmf_staged<kStaged>(P.lights, s_lt, light) * 1.f;
                         const S f_hat = sconst<S>(s_fhat[threadIdx.x]);
                         const Spec Ls = spec4(s_ls[threadIdx.x]);
                         sr_l = sr_l * (r_u * p_l);
@@ -2524,22 +2606,23 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                     r_l = r_l * (T_maj / sv0(T_maj));
                 }
                 for (int k = 0; k < P.lights.n; ++k) {
-                    const DevLight &lt = P.lights.list[k];
-                    if (lt.type == 0 || (!kImage && lt.type == 2)) continue;
+                    const int ltype = light_type<kStaged>(P.lights, s_lt, k);
+                    if (ltype == 0 || (!kImage && ltype == 2)) continue;
                     Spec Le;
                     float pdfLi = 0.f;
-                    if (kImage && lt.type == 2) {
+                    if (kImage && ltype == 2) {
+                        const DevLight &lt = P.lights.list[k];
                         float eu = 0, evv = 0;
                         Le = image_le_dir(lt, pd, lam, &eu, &evv);
                         if (Le.nonzero() && depth != 0) pdfLi = image_pdf_li(lt, pd);
                     } else {
-                        Le = sample_table(light_table(k), lambda_index(lam)) * lt.scale;
+                        Le = sample_table(light_table(k), lambda_index(lam)) * light_scale<kStaged>(P.lights, s_lt, k);
                     }
                     if (!Le.nonzero()) continue;
                     if (depth == 0) L = L + smul(Le, beta) / savg(r_u);
                     else {
                         // lightSampler.PMF * PDF_Li(prevIntrContext, ray.d, true): 0 for the uniform light
-                        r_l = r_l * (light_pmf<kImage>(P.lights, k) * pdfLi);
+                        r_l = r_l * (light_pmf_staged<kStaged>(P.lights, s_lt, k) * pdfLi);
                         L = L + smul(Le, beta) / savg(r_u + r_l);
                     }
                 }
@@ -2563,34 +2646,45 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
         }
 
         AVR_SEC(1)
-        // =================== refill idle lanes: one atomic per wave on a per-XCD head ======
+        // =================== refill idle lanes from the wave's chunk of a per-XCD head =====
         const uint64_t needMask = __ballot(mode == M_FETCH);
         const uint64_t busyMask = __ballot(mode == M_MEDIUM || mode == M_SHADOW);
         if (needMask && (busyMask == 0 || __popcll(needMask) >= P.refill_min)) {
             [[maybe_unused]] const Params &P = fresh_params();
             [[maybe_unused]] const DevMedium &m = P.med;
             const int cnt = __popcll(needMask);
-            const int leader = __ffsll((long long)needMask) - 1;
-            long long base = 0;
-            int granted = 0, exhausted = 0;
-            if (lane == leader) {
-                exhausted = 1;
-                for (int j = 0; j < 8; ++j) {
-                    const int c = (xcc + j) & 7;
-                    const long long lo = N * c / 8, hi = N * (c + 1) / 8;
-                    if (lo >= hi) continue;
-                    const int old = atomicAdd(P.heads + c, cnt);
-                    if (lo + old < hi) {
-                        base = lo + old;
-                        granted = (int)((hi - base) < cnt ? (hi - base) : cnt);
-                        exhausted = 0;
-                        break;
+            // Served from the wave's chunk [chNext, chEnd) first: n0 ids from what is left of it
+            // and, if that is short, the rest from a chunk of kChunk ids claimed now with one
+            // atomic on a head (the own XCD's range first, then the other seven). A claim that
+            // finds every range used up is the last one: the heads only grow within a pass.
+            const int base0 = chNext, left = chEnd - chNext;
+            const int n0 = left < cnt ? left : cnt;
+            chNext += n0;
+            int base1 = 0, n1 = 0;
+            if (n0 < cnt && !drained) {
+                int cb = 0, ce = 0;
+                if (lane == 0) {
+                    for (int j = 0; j < 8; ++j) {
+                        const int c = (xcc + j) & 7;
+                        const long long lo = N * c / 8, hi = N * (c + 1) / 8;
+                        if (lo >= hi) continue;
+                        const int old = atomicAdd(P.heads + c, kChunk);
+                        if (lo + old < hi) {
+                            cb = (int)(lo + old);
+                            ce = (int)(hi - (lo + old) < kChunk ? hi : lo + old + kChunk);
+                            break;
+                        }
                     }
                 }
+                chNext = __builtin_amdgcn_readfirstlane(cb);
+                chEnd = __builtin_amdgcn_readfirstlane(ce);
+                drained = chNext == chEnd;
+                base1 = chNext;
+                n1 = chEnd - chNext < cnt - n0 ? chEnd - chNext : cnt - n0;
+                chNext += n1;
             }
-            base = __shfl(base, leader);
-            granted = __shfl(granted, leader);
-            exhausted = __shfl(exhausted, leader);
+            // (exhausted: no id left for this wave, here or in any range)
+            const int granted = n0 + n1, exhausted = drained;
             // (parked: v_mbcnt, no lane mask carried in registers; the other instantiations keep
             // the mask their register allocation was tuned with)
             int k;
@@ -2605,7 +2699,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 if (fresh) {
                     AVR_COUNT(nPaths, 1);
                     // ---- a new path from the camera stage (k_paths_camera) ----
-                    const int gn = (int)(base + k);
+                    const int gn = k < n0 ? base0 + k : base1 + (k - n0);
                     const float4 c0 = P.ps.cam0[gn], c1 = P.ps.cam1[gn], c2 = P.ps.cam2[gn];
                     const uint4 c3 = P.ps.cam3[gn];
                     // ZSobol: the first light pick drawn ahead; independent: the PCG32 state

@@ -1,8 +1,13 @@
 """Per-loop-depth instruction census of one kernel in a hipcc -S listing (gfx950).
 
 usage: python tools/isa_loops.py avr.s <mangled-kernel-name> [depth]
+       python tools/isa_loops.py avr.s [mangled-kernel-name] --memory
 Counts VALU / SALU / VMEM / LDS / scratch / branch instructions in the basic blocks the
-compiler annotates as belonging to loops of the given depth (default: the deepest)."""
+compiler annotates as belonging to loops of the given depth (default: the deepest).
+--memory: the far-memory census of the persistent loop (depth >= 1; default kernel: k_paths'
+headline instantiation): global loads, scalar loads, s_waitcnt by the counter they drain to
+zero, and atomics that return a value (a wave waits for those before it can go on). A static
+before / after for changes to the service round that needs no GPU."""
 import re
 import sys
 from collections import Counter
@@ -27,13 +32,42 @@ def blocks(lines):
             if d and not cur:
                 depth = int(d.group(1))
             continue
-        cur.append(s.split()[0])
+        cur.append(s)
     if cur is not None:
         out.append((depth, cur))
     return out
 
 
+HEADLINE = "_ZN3avr7k_pathsILb0ELb1ELi3ELi0ELb0ELb0EEEvNS_6ParamsE"
+
+
+def memory_census(bl, want=1):
+    """Counts over the blocks of loop depth >= want: loads, waits and returning atomics."""
+    c = Counter()
+    for d, ins in bl:
+        if d < want:
+            continue
+        for s in ins:
+            op = s.split()[0]
+            if op.startswith(('global_load', 'buffer_load', 'flat_load')):
+                c['global/buffer loads'] += 1
+            elif op.startswith(('s_load', 's_buffer_load')):
+                c['scalar loads'] += 1
+            elif op.startswith('ds_') and ('read' in op or 'load' in op):
+                c['LDS reads'] += 1
+            elif op == 's_waitcnt':
+                c['s_waitcnt'] += 1
+                for cnt in ('vmcnt', 'lgkmcnt'):
+                    if cnt + '(0)' in s:
+                        c[f's_waitcnt {cnt}(0)'] += 1
+            elif op.startswith(('global_atomic', 'buffer_atomic', 'flat_atomic')):
+                # gfx950 marks an atomic that returns the old value with sc0 (glc before gfx940)
+                c['returning atomics' if re.search(r'\b(sc0|glc)\b', s) else 'atomics without return'] += 1
+    return c
+
+
 def kind(op):
+    op = op.split()[0]
     if op.startswith('scratch_'):
         return 'scratch'
     if op.startswith(('global_', 'buffer_', 'flat_')):
@@ -56,13 +90,18 @@ def kind(op):
 
 
 def main():
-    text = open(sys.argv[1]).read()
-    name = sys.argv[2]
+    args = [a for a in sys.argv[1:] if a != '--memory']
+    text = open(args[0]).read()
+    name = args[1] if len(args) > 1 else HEADLINE
     i = text.index(name + ':')
     j = text.index('.Lfunc_end', i)
     bl = blocks(text[i:j].split('\n'))
+    if '--memory' in sys.argv[1:]:
+        c = memory_census(bl)
+        print(f"{name} depth>=1: " + ", ".join(f"{k} {c[k]}" for k in sorted(c)))
+        return
     maxd = max(d for d, _ in bl)
-    want = int(sys.argv[3]) if len(sys.argv) > 3 else maxd
+    want = int(args[2]) if len(args) > 2 else maxd
     tot = Counter()
     nb = 0
     for d, ops in bl:
