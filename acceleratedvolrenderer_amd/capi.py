@@ -123,6 +123,7 @@ SIGNATURES = {
     "avr_tune_walk": (ctypes.c_int, [ctypes.c_void_p, c_int_p, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_float_p]),
     "avr_set_refill_min": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "avr_set_refill_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_light_sampler": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_dda_budget": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_grid_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -431,6 +432,10 @@ class Context:
 
     def set_refill_min(self, lanes):
         _check(self.lib.avr_set_refill_min(self.h, int(lanes)))
+
+    def set_refill_batch(self, lanes):
+        """Fewest waiting lanes for which a k_paths service round refills (0 = default)."""
+        _check(self.lib.avr_set_refill_batch(self.h, int(lanes)))
 
     def set_sampler_table(self, dims):
         """ZSobol pixel-table dimensions (0 = compute every digit per call)."""

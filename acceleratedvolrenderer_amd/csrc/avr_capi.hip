@@ -275,6 +275,7 @@ struct avr_context {
     size_t zs_atab_cap = 0;
     long long zs_akey[6] = {-1, -1, -1, -1, -1, -1};
     int refill_min = 0;       // 0: the default (32 lanes; 20 for a non-emissive NanoVDB walk, 16 for RGB grids, 48 for a <= 2^3 GridMedium majorant)
+    int refill_batch = 0;     // 0: the default of the medium kind (walk_schedule)
     int dda_budget = 0;       // 0: by majorant resolution (12 cells up to 16^3, 32 for NanoVDB's 64^3)
     int grid_layout = 1;
     bool gray = false;        // sigma_a and sigma_s constant over 360..830 nm      // 1: build the fat (footprint) copy when memory allows, 0: linear only
@@ -859,6 +860,12 @@ int avr_set_refill_min(avr_context *c, int lanes) {
     return AVR_OK;
 }
 
+int avr_set_refill_batch(avr_context *c, int lanes) {
+    if (!c || lanes < 0 || lanes > 64) return fail(AVR_ERR_ARG, "refill batch must be 0..64 lanes (0 = default)");
+    c->refill_batch = lanes;
+    return AVR_OK;
+}
+
 int avr_set_render_mode(avr_context *c, int mode) {
     AVR_QUIESCE(c);
     if (!c || (mode != 0 && mode != 1)) return fail(AVR_ERR_ARG, "render mode must be 0 (replay) or 1 (fast)");
@@ -1395,7 +1402,9 @@ int avr_tune_majorant(avr_context *c, const int *candidates, int n, int spp_begi
 // Msamples/s at 12 / 28 in round 3, 1435 -> 1464 at 16 / 28 in round 5, 1619 -> 1638 at 20 / 28
 // in round 6, profiles/r06_walk_sweep.json); an RGBGridMedium (8 sigmoid taps x 4 wavelengths per
 // lookup, 2 waves / SIMD) at 16 lanes with 32 cells (C5's RGB explosion: 1770 -> 2094 Msamples/s)
-static void walk_schedule(const avr_context *c, int refill, int dda, int *r_eff, int *d_eff) {
+// The third value is the refill batch the kernel takes (Params::refill_batch): the requested one
+// (avr_set_refill_batch), else the kind's default. `refill` is the service threshold.
+static void walk_schedule(const avr_context *c, int refill, int dda, int *r_eff, int *d_eff, int *b_eff = nullptr) {
     const int mres = std::max(c->med.mres[0], std::max(c->med.mres[1], c->med.mres[2]));
     const bool vdbWalk = c->med.type == 3 && !c->med.emissive && mres > 16;
     const bool rgbWalk = c->med.type == 4;
@@ -1406,6 +1415,24 @@ static void walk_schedule(const avr_context *c, int refill, int dda, int *r_eff,
     // coarse 48)
     *r_eff = refill > 0 ? refill : (vdbWalk ? 20 : (rgbWalk ? 16 : (coarse ? 48 : 32)));
     *d_eff = dda > 0 ? dda : (vdbWalk ? 28 : (rgbWalk || mres > 16 ? 32 : 10));
+    // The refill batch: a gray, non-emissive GridMedium (the headline's 16^3 majorant and the coarse
+    // one alike: the parked k_paths<false, true, ...> family)
+    // refills whatever waits at every service round (batch 1; plain bench lines against the
+    // parent's tuned coupled schedule: S-cloud-1024 3083-3086 -> 3188-3192 Msamples/s, fast mode's
+    // 1^3 majorant 4063-4066 -> 4695-4698, profiles/refill_batch_ab.json; batches of 8, 16 or the
+    // threshold fall between). The other kinds keep the coupled schedule, a refill at the service
+    // threshold with every waiting lane counted towards it (a negative Params value): the NanoVDB
+    // walk gains at its default threshold (k_paths 32.14 -> 30.61 ms in one sweep process) but not
+    // against the coupled schedule at 12 lanes that the bench's tuner finds (1775-1781 -> 1761-1767),
+    // and the rest (emissive or chromatic grids, RGB grids, homogeneous media) are not measured.
+    // (the API's values 1..64 cannot name the coupled schedule: a library built with
+    // -DAVR_COUPLED_DEFAULT keeps it for every kind, for A/B runs and the probe counters)
+#ifdef AVR_COUPLED_DEFAULT
+    const bool eager = false;
+#else
+    const bool eager = c->med.type == 0 && c->gray && !c->med.emissive;
+#endif
+    if (b_eff) *b_eff = c->refill_batch > 0 ? c->refill_batch : (eager ? 1 : -*r_eff);
 }
 
 int avr_tune_walk(avr_context *c, const int *refill, int nr, const int *dda, int nd, int spp_begin, int spp_end,

@@ -345,7 +345,11 @@ struct Params {
                                       //   state' = A*state + inc*H (PCG32 advance is linear in inc)
     int sampler_kind;                 // 0 IndependentSampler, 1 ZSobolSampler (kernels templated on it)
     smp::ZSobolParams zs;
-    int refill_min;                   // k_paths: refill a wave once this many lanes are idle
+    int refill_min;                   // k_paths: leave the tracking loop for a service round once this
+                                      //   many lanes can be served (event lanes + a refill batch)
+    int refill_batch;                 // k_paths: a service round refills once this many lanes wait
+                                      //   for a new sample (or no lane is busy); < 0: at -refill_batch
+                                      //   lanes, and the trigger counts every waiting lane (coupled)
     int dda_budget;                   // k_paths: majorant cells a lane may cross per tracking
                                       //   iteration before yielding (bounds DDA divergence)
     int rec_mode;                     // k_film: 1 = read k_paths' records (ps.rec), 0 = wavefront SoA
@@ -2166,6 +2170,15 @@ struct ProbeStats {
 #else
 #define AVR_PROBE(k, v)
 #endif
+// With -DAVR_PROBE_SERVICE as well, slots 4, 5 and 7 count the service round instead: 4 service
+// rounds, 5 lanes served (event lanes at the round's start + lanes refilled), 7 refill runs.
+#if defined(AVR_PROBE_STATS) && defined(AVR_PROBE_SERVICE)
+#define AVR_PROBE_SVC(k, v) probe.add(k, v);
+#define AVR_PROBE_LINES(k, v)
+#else
+#define AVR_PROBE_SVC(k, v)
+#define AVR_PROBE_LINES(k, v) AVR_PROBE(k, v)
+#endif
 
 // NanoVDBMedium (kVdb, media.h:602-685): the same loop over the sparse tree. Its 64^3
 // majorant (1 MiB) does not fit LDS and is read through L2 (per-XCD 4 MiB); the density
@@ -2367,6 +2380,17 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
 #endif
     while (true) {
         AVR_SEC(0)
+        // the schedule, not carried through the tracking loop. Read ahead of the handlers that run
+        // before its first use, whose work hides the scalar loads (read at its uses: NanoVDB
+        // -2 %); the parked instantiations have no scalar register left to hold it over the
+        // handlers (eight more lane spills in the headline kernel) and read it at its uses
+        int rmin = 0, rbatch = 0;
+        if constexpr (!kParked) {
+            rmin = fresh_params().refill_min;
+            rbatch = fresh_params().refill_batch;
+        }
+        AVR_PROBE_SVC(4, 1)
+        AVR_PROBE_SVC(5, __popcll(__ballot(ev != EV_NONE)))
         // =================== batched event handlers (each runs once per batch) ===========
         if (__ballot(ev == EV_SCATTER)) {
             [[maybe_unused]] const Params &P = fresh_params();
@@ -2649,7 +2673,11 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
         // =================== refill idle lanes from the wave's chunk of a per-XCD head =====
         const uint64_t needMask = __ballot(mode == M_FETCH);
         const uint64_t busyMask = __ballot(mode == M_MEDIUM || mode == M_SHADOW);
-        if (needMask && (busyMask == 0 || __popcll(needMask) >= P.refill_min)) {
+        // (a batch of refill_batch waiting lanes, or the wave's last lanes: lanes turn M_DONE only
+        // in here, so the second arm is what ends a pass; refill_batch < 0: the coupled schedule,
+        // a batch of -refill_batch lanes with the waiting lanes counted by the trigger below)
+        if constexpr (kParked) rbatch = fresh_params().refill_batch;
+        if (needMask && (busyMask == 0 || __popcll(needMask) >= (rbatch < 0 ? -rbatch : rbatch))) {
             [[maybe_unused]] const Params &P = fresh_params();
             [[maybe_unused]] const DevMedium &m = P.med;
             const int cnt = __popcll(needMask);
@@ -2685,6 +2713,8 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
             }
             // (exhausted: no id left for this wave, here or in any range)
             const int granted = n0 + n1, exhausted = drained;
+            AVR_PROBE_SVC(7, 1)
+            AVR_PROBE_SVC(5, granted)
             // (parked: v_mbcnt, no lane mask carried in registers; the other instantiations keep
             // the mask their register allocation was tuned with)
             int k;
@@ -2783,13 +2813,19 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
         if (__ballot(mode != M_DONE) == 0) break;
 
         // =================== tracking: advance every busy lane collision by collision ======
-        // until a batch of lanes needs service (events or refill) or none is busy.
+        // until a batch of lanes can be served (events, and a refill batch) or none is busy.
+        // Lanes that wait for a sample in fewer than refill_batch are served by no round, so the
+        // trigger does not count them: their number (fixed while tracking, lanes turn M_FETCH
+        // only in the handlers) is added to the threshold once, here.
+        const int waiting = __popcll(__ballot(mode == M_FETCH));
+        if constexpr (kParked) rmin = fresh_params().refill_min;
+        const int serviceMin = rmin + (rbatch < 0 || waiting >= rbatch ? 0 : waiting);
         while (true) {
             AVR_SEC(3)
             const bool busy = (mode == M_MEDIUM || mode == M_SHADOW) && ev == EV_NONE;
             const uint64_t busyNow = __ballot(busy);
             const uint64_t service = __ballot(mode != M_DONE && !busy);
-            if (busyNow == 0 || __popcll(service) >= P.refill_min) break;
+            if (busyNow == 0 || __popcll(service) >= serviceMin) break;
             ++nIter;
             nActive += __popcll(busyNow);
             if (!busy) continue;
@@ -2892,7 +2928,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
             }
             AVR_SEC(4)
 #ifdef AVR_PROBE_STATS
-            { const uint64_t still = __ballot(walk == 0); AVR_PROBE(7, still != 0) }
+            { [[maybe_unused]] const uint64_t still = __ballot(walk == 0); AVR_PROBE_LINES(7, still != 0) }
 #endif
             const bool segEnd = walk == 2, pend = walk == 1;
             if (segEnd) {
@@ -2948,8 +2984,8 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                                               ((int)__builtin_floorf(psx) + 1);
                         AVR_PROBE(2, 1)
                         AVR_PROBE(3, __popcll(__ballot(1)))
-                        AVR_PROBE(4, ProbeStats::distinct(ent >> 2))
-                        AVR_PROBE(5, ProbeStats::distinct(ent >> 1))
+                        AVR_PROBE_LINES(4, ProbeStats::distinct(ent >> 2))
+                        AVR_PROBE_LINES(5, ProbeStats::distinct(ent >> 1))
                     }
 #endif
                     dens = grid_density(m, pm);

@@ -438,7 +438,7 @@ static int render_pass_persistent(avr_context *c, const RenderCall &rc, long lon
     int r = pass_advance_table(c, base, S);
     if (r) return r;
     p.advance = c->d_advance;
-    walk_schedule(c, c->refill_min, c->dda_budget, &p.refill_min, &p.dda_budget);   // defaults: measured optima
+    walk_schedule(c, c->refill_min, c->dda_budget, &p.refill_min, &p.dda_budget, &p.refill_batch);   // defaults: measured optima
     p.pass_gen = ++c->pass_gen & 0x7fffffff;
     p.pix_order = c->d_pix_order;
     p.cam_quad = cam_quad(base, S, p.zs);

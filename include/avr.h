@@ -121,13 +121,29 @@ int avr_set_pass_table_ahead(avr_context *ctx, int on);
  * avr_pass_overlap_active: whether the last pass took records made ahead. */
 int avr_set_pass_overlap(avr_context *ctx, int on);
 int avr_pass_overlap_active(avr_context *ctx);
-/* k_paths: refill a wave's idle lanes with new samples once at least `lanes` (1..64)
- * are idle (or none is busy); larger values batch the per-event handlers across lanes.
+/* k_paths' wave schedule has two parameters. A wave tracks its busy lanes until a service round
+ * can serve at least `refill_min` lanes (or none is busy); the round runs each event handler
+ * once for every lane that raised the event, and refills the lanes that wait for a new sample
+ * once at least `refill_batch` of them wait (or none is busy). Waiting lanes count towards the
+ * service threshold only when the round will refill them. Neither changes results.
+ * avr_set_refill_min: the service threshold, 1..64 lanes; larger values batch the per-event
+ * handlers across more lanes and leave more lanes idle meanwhile.
  * 0 = default (the measured optima in both render modes: 32; 20 for a non-emissive
  * NanoVDB medium at pbrt's 64^3 majorant, whose longer DDA walks favour smaller batches;
  * 16 for an RGBGridMedium; 48 for a GridMedium majorant of at most 2 cells per axis, e.g.
  * fast mode's tuned 1^3, whose one-cell walks leave the handlers dominant). */
 int avr_set_refill_min(avr_context *ctx, int lanes);
+/* avr_set_refill_batch: the fewest waiting lanes for which a service round refills, 1..64
+ * (1: every round refills whatever waits; a value above the service threshold refills only
+ * when no lane is busy). 0 = default: 1 for a gray, non-emissive GridMedium (measured: idle
+ * lanes cost more than the refill's four loads); every other kind (emissive or chromatic grids,
+ * NanoVDB, RGB grids, homogeneous media) keeps the coupled schedule, which refills at the
+ * service threshold and counts every waiting lane towards it. The coupled schedule is a
+ * default only: no value selects it, and `lanes` equal to the service threshold is not it (the
+ * waiting lanes then do not count towards the threshold). To compare against it on a kind
+ * whose default is 1, build the library with -DAVR_COUPLED_DEFAULT (python -m
+ * acceleratedvolrenderer_amd.build <variant> -DAVR_COUPLED_DEFAULT). AVR_ERR_ARG outside 0..64. */
+int avr_set_refill_batch(avr_context *ctx, int lanes);
 /* k_paths: majorant-grid cells a lane may cross per tracking iteration before yielding to
  * the wave (0 = default: 10 for majorant grids up to 16^3, 32 for finer ones and for
  * RGBGridMedium, 28 for a non-emissive NanoVDB medium at 64^3 — measured optima); bounds the

@@ -8,7 +8,7 @@ escape + end), refill, segment starts, DDA walk, collision (exact candidate + de
 callbacks).
 
 usage: python tools/section_profile.py --build            (CPU, before gpurun)
-       python tools/section_profile.py [--res 1024] [--medium grid|nanovdb] [--steps 3]
+       python tools/section_profile.py [--res 1024] [--medium grid|nanovdb] [--steps 3] [--refill 0] [--batch 0]
 """
 import argparse
 import ctypes
@@ -40,6 +40,8 @@ def main():
     p.add_argument("--pass-size", type=int, default=64, help="sample indices per pass (bench.py: 64)")
     p.add_argument("--variant", default="prof", help="variants/<name> (e.g. profsplit)")
     p.add_argument("--define", action="append", default=[], help="extra -D for --build")
+    p.add_argument("--refill", type=int, default=0, help="service threshold (set_refill_min; 0: default)")
+    p.add_argument("--batch", type=int, default=0, help="refill batch (set_refill_batch; 0: default)")
     a = p.parse_args()
     if a.build:
         return build(a.variant, a.define)
@@ -64,6 +66,9 @@ def main():
     S = a.pass_size
     integ = VolPathIntegrator(scene, maxdepth=scenes.CLOUD_MAXDEPTH, spp=S, device=0)
     lib = capi.load()
+    integ.ctx.set_refill_min(a.refill)
+    if a.batch:
+        integ.ctx.set_refill_batch(a.batch)
     lib.avr_debug_sections.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
     out = (ctypes.c_ulonglong * 8)()
     integ.ctx.render(0, S, 0, scenes.CLOUD_MAXDEPTH)   # warmup (pixel tables)
@@ -78,7 +83,7 @@ def main():
     tot = sum(out[i] for i in range(8))
     res = {NAMES[i]: round(out[i] / tot, 4) for i in range(8)}
     st = integ.stats()
-    print(json.dumps({"variant": a.variant, "medium": a.medium, "res": n, "pixelsamples": a.pixelsamples, "pass_size": S,
+    print(json.dumps({"variant": a.variant, "refill": a.refill, "batch": a.batch, "medium": a.medium, "res": n, "pixelsamples": a.pixelsamples, "pass_size": S,
                       "Msamples_per_s": 1280 * 720 * S * a.steps / dt / 1e6,
                       "section_share": res, "wave_cycles": tot, "loop_iterations": st.get("loop_iterations"),
                       "dda_steps": st.get("medium_dda_steps")}))
