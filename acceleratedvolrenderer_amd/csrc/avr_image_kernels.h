@@ -18,7 +18,8 @@ __global__ void __launch_bounds__(256) k_film_image(DevFilm F, Mat3 M, int fp16,
         float o[3];
         for (int i = 0; i < 3; ++i) o[i] = (M.m[3 * i] * r + M.m[3 * i + 1] * g) + M.m[3 * i + 2] * b;
         if (fp16) {
-            const float mx = fmaxf_(o[0], fmaxf_(o[1], o[2]));
+            // std::max({r, g, b}) (film.cpp:543): max(max(r, g), b), which a NaN r closes and a NaN g skips
+            const float mx = fmaxf_(fmaxf_(o[0], o[1]), o[2]);
             for (int i = 0; i < 3; ++i) {
                 if (mx > 65504.f && o[i] > 65504.f) o[i] = 65504.f;
                 o[i] = (float)(_Float16)o[i];   // IEEE round-to-nearest-even

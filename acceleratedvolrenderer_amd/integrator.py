@@ -18,7 +18,7 @@ import numpy as np
 
 from . import capi, imageio
 from .imgtool import channel_average
-from .scene import film_rgb, GBufferFilm, gbuffer_image
+from .scene import clamp_fp16, film_rgb, GBufferFilm, gbuffer_image
 
 INTEGRATOR_NAMES = ("volpath", "volpathcustom", "volpath_mi355x")
 
@@ -104,7 +104,8 @@ class FilmIntegrator:
         image ("savefp16", default true) the 65504 clamp and the half rounding."""
         img = self.image(rgb_sum, w_sum)
         if fp16:
-            img = np.minimum(img, np.float32(65504)).astype(np.float16).astype(np.float32)
+            with np.errstate(over="ignore"):    # a channel the gate leaves above 65504 rounds to inf
+                img = clamp_fp16(img).astype(np.float16).astype(np.float32)
         return img
 
     def write_image(self, path, rgb_sum=None, w_sum=None, spp=None, render_time=None, mse=None, fp16=True):

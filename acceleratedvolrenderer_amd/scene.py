@@ -521,12 +521,24 @@ class GBufferFilm(RGBFilm):
         return list(self.CHANNELS)
 
 
+def clamp_fp16(rgb):
+    """The fp16 clamp of RGBFilm::GetImage and GBufferFilm::GetImage (film.cpp:543-551, 761-769):
+    channels above 65504 become 65504 where std::max({r, g, b}) > 65504. The initializer-list
+    maximum is `largest = r; if (largest < g) largest = g; if (largest < b) largest = b`: a NaN r
+    stays the maximum and keeps the gate shut (a channel above 65504 beside it is left, and
+    becomes inf in the half image), a NaN g or b is skipped."""
+    m = rgb[..., 0]
+    for c in (1, 2):
+        m = np.where(m < rgb[..., c], rgb[..., c], m)
+    return np.where((m > 65504)[..., None] & (rgb > 65504), np.float32(65504), rgb)
+
+
 def gbuffer_image(film, rgb_sum, w_sum, fp16=True):
     """GBufferFilm::GetImage (film.cpp:688-800), no splats and no visible surfaces:
     (H, W, 25) float32 in GBufferFilm.CHANNELS order."""
     rgb = film_rgb(film, rgb_sum, w_sum)
     if fp16:
-        rgb = np.minimum(rgb, np.float32(65504))
+        rgb = clamp_fp16(rgb)
     out = np.zeros((film.height, film.width, len(GBufferFilm.CHANNELS)), np.float32)
     out[:, :, :3] = rgb
     return out
