@@ -154,6 +154,9 @@ def lib():
         L.oracle_set_libm.argtypes = [ctypes.c_int]
         L.oracle_transmittance4.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, c_float_p, c_float_p,
                                             c_float_p, c_float_p]
+        L.oracle_transmittance4_points.restype = ctypes.c_longlong
+        L.oracle_transmittance4_points.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, c_float_p, c_float_p,
+                                                   c_float_p, c_float_p, ctypes.c_longlong, c_float_p]
         L.oracle_get_libm.restype = ctypes.c_int
         c_int_p = ctypes.POINTER(ctypes.c_int)
         L.oracle_vdb_create.restype = ctypes.c_void_p
@@ -564,6 +567,21 @@ class OracleRun:
         set_libm(self.libm)
         lib().oracle_transmittance4(ctypes.byref(self.s), len(p0), fp(p0), fp(p1), fp(lam), fp(out))
         return out
+
+    def transmittance4_points(self, p0, p1, lam, cap=1 << 20):
+        """transmittance4 and the render-space point of every SamplePoint call, in query order:
+        ((n, 4) transmittances, (calls, 3) points)."""
+        p0 = np.ascontiguousarray(p0, np.float32)
+        p1 = np.ascontiguousarray(p1, np.float32)
+        lam = np.ascontiguousarray(lam, np.float32)
+        out = np.zeros((len(p0), 4), np.float32)
+        pts = np.zeros((int(cap), 3), np.float32)
+        set_libm(self.libm)
+        n = lib().oracle_transmittance4_points(ctypes.byref(self.s), len(p0), fp(p0), fp(p1), fp(lam), fp(out),
+                                               int(cap), fp(pts))
+        if n > cap:
+            raise ValueError(f"{n} lookups exceed the capacity {cap}")
+        return out, pts[:n]
 
     def dda_segments(self, o, d, tmax=np.inf, lambda_u=0.5, max_segs=256):
         o = np.ascontiguousarray(o, np.float32)

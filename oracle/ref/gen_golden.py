@@ -3,6 +3,7 @@
 Test infrastructure only. Builds oracle/_ref/ref_harness from the unmodified
 pbrt-v4 sources under /root/reference (oracle/ref/Makefile), runs it and writes
   tests/golden/ref_vectors.json                — golden vectors (uint32 float bits)
+  tests/golden/hg_edge_vectors.json            — hg_eval / hg_sample at g = 0.0009, -0.0011, -0.99, 1.5
   acceleratedvolrenderer_amd/data/spectra_f32.bin — CIE 1931 x̄ȳz̄, D65 (471 each,
       360..830 nm), sRGB RGBFromXYZ (9), D65 photometric scale, CIE_Y_integral
 The RGB -> spectrum goldens read the sRGB table that the reference's own rgb2spec_opt
@@ -28,6 +29,9 @@ def main():
     out = subprocess.check_output([exe, "--tables", tables, "--rgbtable", rgbtable])
     with open(os.path.join(REPO, "tests", "golden", "ref_vectors.json"), "wb") as f:
         f.write(out)
+    edges = subprocess.check_output([exe, "--hg-edges"])
+    with open(os.path.join(REPO, "tests", "golden", "hg_edge_vectors.json"), "wb") as f:
+        f.write(edges)
     print("wrote", len(out), "bytes of golden vectors and", os.path.getsize(tables), "bytes of tables")
 
 

@@ -88,13 +88,55 @@ static void arr_u64(const std::vector<uint64_t> &v) {
     printf("]");
 }
 
+// hg_eval [cosTheta, g, p] and hg_sample [wo x 3, g, u x 2, wi x 3, pdf] for the given g values
+static void hg_vectors(J &j, const float *gs, int ng) {
+    j.key("hg_eval");
+    printf("[");
+    bool f = true;
+    for (int k = 0; k < ng; ++k)
+        for (int i = 0; i <= 8; ++i) {
+            float g = gs[k], c = -1.f + 0.25f * i;
+            printf("%s[%u,%u,%u]", f ? "" : ",", fb(c), fb(g), fb(HenyeyGreenstein(c, g)));
+            f = false;
+        }
+    printf("]");
+    j.key("hg_sample");
+    printf("[");
+    f = true;
+    const float wos[][3] = {{0.f, 0.f, 1.f}, {0.f, 0.f, -1.f}, {0.36f, -0.48f, 0.8f}, {-0.6f, 0.f, -0.8f}};
+    const float us[][2] = {{0.1f, 0.2f}, {0.5f, 0.5f}, {0.9f, 0.05f}, {0.0f, 0.999f}};
+    for (int k = 0; k < ng; ++k)
+        for (auto &wo : wos)
+            for (auto &u : us) {
+                float g = gs[k];
+                Float pdf;
+                Vector3f wi = SampleHenyeyGreenstein(Vector3f(wo[0], wo[1], wo[2]), g, Point2f(u[0], u[1]), &pdf);
+                printf("%s[%u,%u,%u,%u,%u,%u,%u,%u,%u,%u]", f ? "" : ",", fb(wo[0]), fb(wo[1]), fb(wo[2]),
+                       fb(g), fb(u[0]), fb(u[1]), fb(wi.x), fb(wi.y), fb(wi.z), fb(pdf));
+                f = false;
+            }
+    printf("]");
+}
+
 int main(int argc, char **argv) {
     Allocator alloc;
     Spectra::Init(alloc);
     const char *tablePath = nullptr, *rgbTablePath = nullptr;
+    bool hgEdges = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--tables") && i + 1 < argc) tablePath = argv[++i];
         if (!strcmp(argv[i], "--rgbtable") && i + 1 < argc) rgbTablePath = argv[++i];
+        if (!strcmp(argv[i], "--hg-edges")) hgEdges = true;
+    }
+    if (hgEdges) {
+        // tests/golden/hg_edge_vectors.json, a file of its own so that ref_vectors.json (one line)
+        // keeps its bytes: either side of the |g| < 1e-3 switch, the clamp's lower end, beyond it
+        const float gs[] = {0.0009f, -0.0011f, -0.99f, 1.5f};
+        J j;
+        printf("{");
+        hg_vectors(j, gs, 4);
+        printf("}\n");
+        return 0;
     }
 
     printf("{");
@@ -224,32 +266,8 @@ int main(int argc, char **argv) {
 
     // ---- Henyey-Greenstein --------------------------------------------------
     {
-        j.key("hg_eval");
-        printf("[");
         const float gs[] = {0.f, 0.3f, -0.5f, 0.877f, 0.995f};
-        bool f = true;
-        for (float g : gs)
-            for (int i = 0; i <= 8; ++i) {
-                float c = -1.f + 0.25f * i;
-                printf("%s[%u,%u,%u]", f ? "" : ",", fb(c), fb(g), fb(HenyeyGreenstein(c, g)));
-                f = false;
-            }
-        printf("]");
-        j.key("hg_sample");
-        printf("[");
-        f = true;
-        const float wos[][3] = {{0.f, 0.f, 1.f}, {0.f, 0.f, -1.f}, {0.36f, -0.48f, 0.8f}, {-0.6f, 0.f, -0.8f}};
-        const float us[][2] = {{0.1f, 0.2f}, {0.5f, 0.5f}, {0.9f, 0.05f}, {0.0f, 0.999f}};
-        for (float g : gs)
-            for (auto &wo : wos)
-                for (auto &u : us) {
-                    Float pdf;
-                    Vector3f wi = SampleHenyeyGreenstein(Vector3f(wo[0], wo[1], wo[2]), g, Point2f(u[0], u[1]), &pdf);
-                    printf("%s[%u,%u,%u,%u,%u,%u,%u,%u,%u,%u]", f ? "" : ",", fb(wo[0]), fb(wo[1]), fb(wo[2]),
-                           fb(g), fb(u[0]), fb(u[1]), fb(wi.x), fb(wi.y), fb(wi.z), fb(pdf));
-                    f = false;
-                }
-        printf("]");
+        hg_vectors(j, gs, 5);
     }
 
     // ---- SampledGrid --------------------------------------------------------

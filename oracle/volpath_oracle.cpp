@@ -2141,9 +2141,11 @@ void oracle_transmittance(const OracleScene *s, int n, const float *p0, const fl
     }
 }
 
-// Integrator::Tr at explicit wavelengths (4 per query), all four components.
-void oracle_transmittance4(const OracleScene *s, int n, const float *p0, const float *p1, const float *lambdas,
-                           float *trOut) {
+// Integrator::Tr at explicit wavelengths (4 per query), all four components. With `pts`, the
+// render-space point of every SamplePoint call (each tentative collision, in query order) is
+// written there while fewer than `cap` are held; *count ends at the number of calls.
+static void Transmittance4(const OracleScene *s, int n, const float *p0, const float *p1, const float *lambdas,
+                           float *trOut, long long cap, float *pts, long long *count) {
     SceneView sv(*s);
     for (int i = 0; i < n; ++i) {
         Lambda l;
@@ -2157,7 +2159,11 @@ void oracle_transmittance4(const OracleScene *s, int n, const float *p0, const f
             ray.d = pExit - ray.o;
             float u = rng.Uniform();
             Spec T_maj = SampleT_maj(sv, ray, 1.f, u, rng, l,
-                [&](V3, const MediumProps &mp, Spec sigma_maj, Spec Tm) {
+                [&](V3 p, const MediumProps &mp, Spec sigma_maj, Spec Tm) {
+                    if (pts) {
+                        if (*count < cap) { pts[3 * *count] = p.x; pts[3 * *count + 1] = p.y; pts[3 * *count + 2] = p.z; }
+                        ++*count;
+                    }
                     Spec sigma_n = ClampZero(sigma_maj - mp.sigma_a - mp.sigma_s);
                     float pr = Tm[0] * sigma_maj[0];
                     Tr = Tr * (Tm * sigma_n / pr);
@@ -2171,6 +2177,17 @@ void oracle_transmittance4(const OracleScene *s, int n, const float *p0, const f
         }
         for (int k = 0; k < NS; ++k) trOut[4 * i + k] = Tr.v[k];
     }
+}
+void oracle_transmittance4(const OracleScene *s, int n, const float *p0, const float *p1, const float *lambdas,
+                           float *trOut) {
+    Transmittance4(s, n, p0, p1, lambdas, trOut, 0, nullptr, nullptr);
+}
+// ... and the lookup points (tests): returns the number of SamplePoint calls
+long long oracle_transmittance4_points(const OracleScene *s, int n, const float *p0, const float *p1,
+                                       const float *lambdas, float *trOut, long long cap, float *pts) {
+    long long count = 0;
+    Transmittance4(s, n, p0, p1, lambdas, trOut, cap, pts, &count);
+    return count;
 }
 
 // Majorant DDA segments of one ray (for tests): returns count, writes (tMin, tMax, sigma_maj[0]).

@@ -4,7 +4,9 @@ tests/test_gpu_fast.py runs the fast half of avr_create's kernel table in one fa
 GridMedium, no emission, no image light, box interface, RGBFilm). This module runs it in the
 others: one named case per (medium kind, emission, gray, sampler, image light / power sampler,
 interface shape, film) family, built from the scene builders of the replay tests
-(tests/test_gpu_parity.py, test_gpu_sphere.py, test_gpu_kpaths_parked.py) on their small films.
+(tests/test_gpu_parity.py, test_gpu_sphere.py, test_gpu_kpaths_parked.py) on their small films,
+and two (grid-affine, cloud-affine) behind a rotation, a non-uniform scale and a box that is not
+the unit cube (tests/media_cases.py).
 Each case names, by hand, the instantiation `avr_last_kernel` must report; avr_last_kernel prints
 the flags and not the table slot, so every case also checks what the launched kernel computed:
 
@@ -77,6 +79,8 @@ relative pdf error):
   sphere                   0.057      +0.30      0.9954  0.0e+00 3.8e-05 1.7e-04  -                  6.1e-05     5.0e-07
   convex                   0.140      +0.44      0.9742  0.0e+00 0.0e+00 3.2e-01  -                  6.1e-05     5.0e-07
   spectral                 0.125      +1.03      0.9051  1.7e-04 3.2e-04 6.3e-01  -                  0.0e+00     0.0e+00
+  grid-affine              0.182      -1.93      0.9509  0.0e+00 0.0e+00 5.1e-01  -                  6.1e-05     5.0e-07
+  cloud-affine             0.056      -0.65      0.9935  0.0e+00 0.0e+00 3.5e-07  -                  6.1e-05     5.0e-07
 
   spectral film: bucket sums rel RMS 7.2e-02 against a two-seed noise of 6.5e-01.
   White furnace (grid, homogeneous, NanoVDB): max |L - 1| = 0 over 4096 samples each.
@@ -91,6 +95,9 @@ from typing import Callable, NamedTuple
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import media_cases   # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, SPP = 24, 20, 8
@@ -253,6 +260,12 @@ def _spectral():
     return _with(_grid("chromatic"), film=SpectralFilm(W, H, nbuckets=7, lambdamin=400.0, lambdamax=700.0))
 
 
+def _affine(kind):
+    """tests/media_cases.py's "affine" box: world_from_medium a rotation times a non-uniform scale,
+    the general Bounds3::Offset branch."""
+    return media_cases.scene_for("affine", kind)
+
+
 class Case(NamedTuple):
     id: str
     make: Callable          # (pixelsamples=None) -> Scene; pixelsamples: a ZSobol sampler's, for a longer render
@@ -309,6 +322,9 @@ CASES = [
     Case("sphere", lambda pixelsamples=None: _sphere(), 8, "k_paths<false, false, 0, 0, false, true>"),
     Case("convex", lambda pixelsamples=None: _convex(), 8, "k_paths<false, true, 0, 0, false, true>"),
     Case("spectral", lambda pixelsamples=None: _spectral(), 5, "k_paths<false, false, 0, 0, false, true>"),
+    # a rotation, a non-uniform scale and a box of three different extents (tests/media_cases.py)
+    Case("grid-affine", lambda pixelsamples=None: _affine("gray"), 6, "k_paths<false, true, 0, 0, false, true>"),
+    Case("cloud-affine", lambda pixelsamples=None: _affine("cloud"), 6, "k_paths<false, true, 0, 1, false, true>"),
 ]
 BY_ID = {c.id: c for c in CASES}
 IDS = [c.id for c in CASES]

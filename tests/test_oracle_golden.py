@@ -76,8 +76,20 @@ def test_sample_visible_wavelengths(golden):
         assert pdf.view(np.uint32).tolist() == v[5:9].view(np.uint32).tolist()
 
 
+def _hg_edges():
+    """hg_eval / hg_sample of the reference at g = 0.0009, -0.0011 (either side of the |g| < 1e-3
+    switch), -0.99 and 1.5 (the clamp), in a file of their own (oracle/ref/gen_golden.py)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hg_edge_vectors.json")) as fh:
+        return json.load(fh)
+
+
 def test_henyey_greenstein(golden):
     L = ob.lib()
+    edges = _hg_edges()
+    assert len(edges["hg_eval"]) == 4 * 9 and len(edges["hg_sample"]) == 4 * 16
+    golden = {k: golden[k] + edges[k] for k in ("hg_eval", "hg_sample")}
     for c, g, p in golden["hg_eval"]:
         got = np.float32(L.oracle_hg_eval(float(f([c])[0]), float(f([g])[0])))
         assert got.view(np.uint32) == np.uint32(p)
