@@ -155,6 +155,7 @@ SIGNATURES = {
     "avr_film_set_reference": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int]),
     "avr_film_metric": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p]),
     "avr_last_pass_weights": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_longlong]),
+    "avr_last_pass_rays": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_longlong]),
     "avr_last_kernel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]),
     "avr_transmittance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p, c_float_p,
                                          c_float_p]),
@@ -622,6 +623,17 @@ class Context:
         w = np.zeros(npix * max_samples, np.float32)
         _check(self.lib.avr_last_pass_weights(self.h, _fp(w), len(w)))
         return w
+
+    def last_pass_rays(self, npix, max_samples):
+        """The camera stage's rays of the last persistent pass, indexed as last_pass_samples: the
+        origin after the medium-interface entry (n, 3), the direction (n, 3) and the first segment's
+        free-flight draw (n), n = npix * max_samples (the pass's samples first)."""
+        n = npix * max_samples
+        o = np.zeros((n, 3), np.float32)
+        d = np.zeros((n, 3), np.float32)
+        u = np.zeros(n, np.float32)
+        _check(self.lib.avr_last_pass_rays(self.h, _fp(o), _fp(d), _fp(u), n))
+        return o, d, u
 
     def transmittance(self, p0, p1, lam):
         """Integrator::Tr for n queries: p0, p1 (n, 3) render-space points, lam (n, 4) nm."""

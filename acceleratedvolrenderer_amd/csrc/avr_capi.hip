@@ -2212,6 +2212,32 @@ int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
     return AVR_OK;
 }
 
+int avr_last_pass_rays(avr_context *c, float *o3, float *d3, float *u, long long n_max) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
+    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
+    if (n > 0 && !c->last.persistent)
+        return fail(AVR_ERR_STATE, "the last pass was not a persistent one (the wavefront path consumes its rays)");
+    if (n > 0 && c->last.order_gen != c->order_gen)
+        return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
+    if (n <= 0) return AVR_OK;
+    // the camera stage's records: cam0 {o after interface_entry, u}, cam1 {d, .}
+    std::vector<float> cam0(4 * (size_t)n), cam1(4 * (size_t)n);
+    HIP_TRY(hipMemcpy(cam0.data(), c->set.cam0, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cam1.data(), c->set.cam1, n * sizeof(float4), hipMemcpyDeviceToHost));
+    const long long np = (long long)c->film.width * c->film.height;
+    for (long long i = 0; i < n; ++i) {
+        const size_t src = (size_t)(c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]);
+        for (int k = 0; k < 3; ++k) {
+            if (o3) o3[3 * i + k] = cam0[4 * src + k];
+            if (d3) d3[3 * i + k] = cam1[4 * src + k];
+        }
+        if (u) u[i] = cam0[4 * src + 3];
+    }
+    return AVR_OK;
+}
+
 int avr_film_export_device(avr_context *c, void *dst) {
     if (!c || !c->has_film || !dst) return fail(AVR_ERR_STATE, "no film");
     const size_t np = (size_t)c->film.width * c->film.height;

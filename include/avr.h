@@ -891,6 +891,11 @@ int avr_last_pass_samples(avr_context *ctx, float *L, float *lambda, float *pdf,
  * Both readbacks fail with AVR_ERR_STATE once the pixel order (avr_set_pixel_order, or a new
  * avr_film that drops it) changed after that render: its records are in the old slot order. */
 int avr_last_pass_weights(avr_context *ctx, float *weight, long long n_max);
+/* The camera stage's rays of the last PERSISTENT pass, same indexing and the same pixel-order
+ * rule: the render-space origin after the medium-interface entry (o3, n*3), the direction (d3,
+ * n*3) and the first segment's free-flight draw (u, n). Any output may be NULL. AVR_ERR_STATE
+ * after a wavefront render, whose ray state the path itself consumes. */
+int avr_last_pass_rays(avr_context *ctx, float *o3, float *d3, float *u, long long n_max);
 /* Template arguments of the last k_paths instantiation avr_render launched, as
  * "k_paths<emissive, gray, sampler, medium, image, fast>" (sampler 0 independent, 2 / 3 ZSobol
  * with 32- / 64-bit indices; "" before the first persistent render): lets a profiler pass

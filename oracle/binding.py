@@ -93,6 +93,11 @@ def lib():
         L.oracle_pixel_sample.restype = ctypes.c_int
         L.oracle_pixel_sample.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           c_float_p, c_float_p, c_float_p, c_float_p]
+        L.oracle_camera_ray.restype = None
+        L.oracle_camera_ray.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
+        L.oracle_camera_rays_at.restype = None
+        L.oracle_camera_rays_at.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, c_float_p, c_float_p, c_float_p]
         L.oracle_zsobol.argtypes = [ctypes.c_int] * 7 + [ctypes.c_char_p, c_float_p]
         L.oracle_sobol_fastowen.restype = ctypes.c_float
         L.oracle_sobol_fastowen.argtypes = [ctypes.c_ulonglong, ctypes.c_int, ctypes.c_uint]
@@ -444,6 +449,25 @@ class OracleRun:
         if with_weight:
             return L, lam, pdf, n, w[0]
         return L, lam, pdf, n
+
+    def camera_ray(self, px, py, sample_index):
+        """What pixel_sample computes before its first segment: (o (3) after the interface entry,
+        d (3), u the first segment's free-flight draw, pFilm (2), filter weight)."""
+        o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        u, w = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        pf = np.zeros(2, np.float32)
+        set_libm(self.libm)
+        lib().oracle_camera_ray(ctypes.byref(self.s), px, py, sample_index, fp(o), fp(d), fp(u), fp(pf), fp(w))
+        return o, d, u[0], pf, w[0]
+
+    def camera_rays_at(self, p_film):
+        """The render-space camera rays (o, d: (n, 3)) through raster points p_film (n, 2), before
+        any interface entry."""
+        pf = np.ascontiguousarray(p_film, np.float32).reshape(-1, 2)
+        o, d = np.zeros((len(pf), 3), np.float32), np.zeros((len(pf), 3), np.float32)
+        set_libm(self.libm)
+        lib().oracle_camera_rays_at(ctypes.byref(self.s), len(pf), fp(pf), fp(o), fp(d))
+        return o, d
 
     def render(self, spp0, spp1, nthreads=1):
         f = self.scene.film

@@ -6,6 +6,8 @@ pbrt-v4 sources under /root/reference (oracle/ref/Makefile), runs it and writes
   tests/golden/hg_edge_vectors.json            — hg_eval / hg_sample at g = 0.0009, -0.0011, -0.99, 1.5
   acceleratedvolrenderer_amd/data/spectra_f32.bin — CIE 1931 x̄ȳz̄, D65 (471 each,
       360..830 nm), sRGB RGBFromXYZ (9), D65 photometric scale, CIE_Y_integral
+  tests/golden/camera_ray_vectors.json         — the reference's camera rays of tests/camera_cases.py's cameras
+  tests/golden/gaussian_filter_vectors.json    — GaussianFilter::Sample at that module's radii and sigmas
 The RGB -> spectrum goldens read the sRGB table that the reference's own rgb2spec_opt
 writes into oracle/_ref (Makefile); the table stays there (not committed).
 The spectral tables are published CIE / ITU data as the reference holds them;
@@ -32,6 +34,15 @@ def main():
     edges = subprocess.check_output([exe, "--hg-edges"])
     with open(os.path.join(REPO, "tests", "golden", "hg_edge_vectors.json"), "wb") as f:
         f.write(edges)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    sys.path.insert(0, REPO)
+    import camera_cases
+    rays = subprocess.check_output([exe, "--camera-rays"], input=camera_cases.harness_camera_lines().encode())
+    with open(os.path.join(REPO, "tests", "golden", "camera_ray_vectors.json"), "wb") as f:
+        f.write(rays)
+    filters = subprocess.check_output([exe, "--filters"])
+    with open(os.path.join(REPO, "tests", "golden", "gaussian_filter_vectors.json"), "wb") as f:
+        f.write(filters)
     print("wrote", len(out), "bytes of golden vectors and", os.path.getsize(tables), "bytes of tables")
 
 

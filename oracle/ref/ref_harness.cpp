@@ -16,7 +16,10 @@
 //   GaussianFilter / FilterSampler (filters.h:26-118, filters.cpp:133-147),
 //   Noise/DNoise (util/noise.cpp),
 //   Blackbody (util/spectrum.h:69-80), CIE/D65 tables (util/spectrum.cpp),
-//   sRGB RGBFromXYZ (util/colorspace.cpp).
+//   sRGB RGBFromXYZ (util/colorspace.cpp),
+//   LookAt / Perspective / Orthographic / Scale / Translate / Inverse (util/transform.cpp) composed
+//   as CameraTransform (cameras.cpp:27-57, CameraWorld) and the ProjectiveCamera constructor
+//   (cameras.h:254-273) compose them (--camera-rays).
 // Output: JSON on stdout (golden vectors) and, with --tables <file>, a raw
 // little-endian float32 table file consumed by oracle/ref/gen_golden.py.
 #include <pbrt/util/rng.h>
@@ -118,15 +121,136 @@ static void hg_vectors(J &j, const float *gs, int ng) {
     printf("]");
 }
 
+// --camera-rays: tests/golden/camera_ray_vectors.json. One camera per line of standard input, as
+// tests/camera_cases.py::harness_camera_lines writes them: name, type (0 orthographic, 1
+// perspective), fov, pos, look, up (3 each), mirror, has_window and the window (4), the frame
+// aspect ratio (0: the film's), the film's width and height. Per camera: the reference's own
+// transforms composed as CameraTransform (CameraWorld rendering space) and the ProjectiveCamera
+// constructor compose them, the screen window as Orthographic / PerspectiveCamera::Create choose
+// it, and GenerateRay's three lines (cameras.cpp:284-291, 404-412) at the film's four corners, its
+// centre and 16 fixed raster points: [x, y, o x 3, d x 3] in render space.
+static int camera_rays() {
+    char line[1024];
+    printf("{\"cases\":[");
+    bool firstCase = true;
+    while (fgets(line, sizeof line, stdin)) {
+        char name[64];
+        double v[20];
+        int off = 0;
+        if (sscanf(line, "%63s%n", name, &off) != 1) continue;
+        const char *c = line + off;
+        int got = 0;
+        for (; got < 20; ++got) {
+            char *end;
+            v[got] = strtod(c, &end);
+            if (end == c) break;
+            c = end;
+        }
+        if (got != 20) { fprintf(stderr, "camera %s: %d of 20 values\n", name, got); return 1; }
+        const int type = (int)v[0];
+        const Float fov = v[1];
+        const Point3f pos(v[2], v[3], v[4]), look(v[5], v[6], v[7]);
+        const Vector3f up(v[8], v[9], v[10]);
+        const bool mirror = v[11] != 0, hasWindow = v[12] != 0;
+        const int xres = (int)v[18], yres = (int)v[19];
+        // the scene file's CTM at Camera: [Scale -1 1 1] LookAt
+        Transform cameraFromWorld = LookAt(pos, look, up);
+        if (mirror) cameraFromWorld = Scale(-1, 1, 1) * cameraFromWorld;
+        Transform worldFromCamera = Inverse(cameraFromWorld);
+        // CameraTransform, RenderingCoordinateSystem::CameraWorld
+        Point3f pCam = worldFromCamera(Point3f(0, 0, 0));
+        Transform worldFromRender = Translate(Vector3f(pCam));
+        Transform renderFromWorld = Inverse(worldFromRender);
+        Transform renderFromCamera = renderFromWorld * worldFromCamera;
+        // Create: the screen window
+        Float frame = v[17] > 0 ? Float(v[17]) : Float(xres) / Float(yres);
+        Bounds2f screen;
+        if (frame > 1.f) {
+            screen.pMin.x = -frame; screen.pMax.x = frame; screen.pMin.y = -1.f; screen.pMax.y = 1.f;
+        } else {
+            screen.pMin.x = -1.f; screen.pMax.x = 1.f; screen.pMin.y = -1.f / frame; screen.pMax.y = 1.f / frame;
+        }
+        if (hasWindow) {
+            screen.pMin.x = v[13]; screen.pMax.x = v[14]; screen.pMin.y = v[15]; screen.pMax.y = v[16];
+        }
+        Transform screenFromCamera = type ? Perspective(fov, 1e-2f, 1000.f) : Orthographic(0, 1);
+        // ProjectiveCamera constructor
+        Transform NDCFromScreen = Scale(1 / (screen.pMax.x - screen.pMin.x), 1 / (screen.pMax.y - screen.pMin.y), 1) *
+                                  Translate(Vector3f(-screen.pMin.x, -screen.pMax.y, 0));
+        Transform rasterFromNDC = Scale(xres, -yres, 1);
+        Transform rasterFromScreen = rasterFromNDC * NDCFromScreen;
+        Transform screenFromRaster = Inverse(rasterFromScreen);
+        Transform cameraFromRaster = Inverse(screenFromCamera) * screenFromRaster;
+        std::vector<Point2f> pts = {{0, 0}, {Float(xres), 0}, {0, Float(yres)}, {Float(xres), Float(yres)},
+                                    {xres * 0.5f, yres * 0.5f}};
+        RNG rng(41, 7);
+        for (int i = 0; i < 16; ++i) {
+            Float x = rng.Uniform<Float>() * xres, y = rng.Uniform<Float>() * yres;
+            pts.push_back({x, y});
+        }
+        // the line as read, without its newline
+        line[strcspn(line, "\r\n")] = 0;
+        printf("%s{\"name\":\"%s\",\"line\":\"%s\",\"type\":%d,\"width\":%d,\"height\":%d,\"rays\":[", firstCase ? "" : ",",
+               name, line, type, xres, yres);
+        firstCase = false;
+        for (size_t i = 0; i < pts.size(); ++i) {
+            // GenerateRay
+            Point3f pFilm = Point3f(pts[i].x, pts[i].y, 0);
+            Point3f pCamera = cameraFromRaster(pFilm);
+            Ray ray = type ? Ray(Point3f(0, 0, 0), Normalize(Vector3f(pCamera))) : Ray(pCamera, Vector3f(0, 0, 1));
+            Ray r = renderFromCamera(ray);
+            printf("%s[%u,%u,%u,%u,%u,%u,%u,%u]", i ? "," : "", fb(pts[i].x), fb(pts[i].y), fb(r.o.x), fb(r.o.y), fb(r.o.z),
+                   fb(r.d.x), fb(r.d.y), fb(r.d.z));
+        }
+        printf("]}");
+    }
+    printf("]}\n");
+    return 0;
+}
+
+// [u x 2, p x 2, weight] of GaussianFilter::Sample for 96 points: u = (0, 0), (1 - 2^-24, 1 - 2^-24),
+// (0.5, 0.5), then random
+static void gaussian_filter_samples(const float (*cfg)[3], int n, RNG &rng) {
+    printf("[");
+    for (int c = 0; c < n; ++c) {
+        GaussianFilter gf(Vector2f(cfg[c][0], cfg[c][1]), cfg[c][2]);
+        printf("%s{\"rx\":%u,\"ry\":%u,\"sigma\":%u,\"samples\":[", c ? "," : "", fb(cfg[c][0]), fb(cfg[c][1]),
+               fb(cfg[c][2]));
+        for (int i = 0; i < 96; ++i) {
+            Point2f u(rng.Uniform<Float>(), rng.Uniform<Float>());
+            if (i == 0) u = Point2f(0.f, 0.f);
+            if (i == 1) u = Point2f(0.99999994f, 0.99999994f);
+            if (i == 2) u = Point2f(0.5f, 0.5f);
+            FilterSample fs = gf.Sample(u);
+            printf("%s[%u,%u,%u,%u,%u]", i ? "," : "", fb(u.x), fb(u.y), fb(fs.p.x), fb(fs.p.y), fb(fs.weight));
+        }
+        printf("]}");
+    }
+    printf("]");
+}
+
 int main(int argc, char **argv) {
     Allocator alloc;
     Spectra::Init(alloc);
     const char *tablePath = nullptr, *rgbTablePath = nullptr;
-    bool hgEdges = false;
+    bool hgEdges = false, filters = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--tables") && i + 1 < argc) tablePath = argv[++i];
         if (!strcmp(argv[i], "--rgbtable") && i + 1 < argc) rgbTablePath = argv[++i];
         if (!strcmp(argv[i], "--hg-edges")) hgEdges = true;
+        if (!strcmp(argv[i], "--camera-rays")) return camera_rays();
+        if (!strcmp(argv[i], "--filters")) filters = true;
+    }
+    if (filters) {
+        // tests/golden/gaussian_filter_vectors.json: the radii and sigmas of tests/camera_cases.py's
+        // Gaussian filters (tables that are not square, 128 x 128, 16 x 16, all-zero rows)
+        const float cfg[][3] = {{2.f, 2.f, 0.5f},   {0.75f, 2.5f, 0.4f}, {2.5f, 0.75f, 0.4f}, {1.5f, 1.6f, 0.5f},
+                                {4.f, 4.f, 1.f},    {0.5f, 0.5f, 0.5f},  {1.5f, 1.5f, 0.05f}};
+        RNG rng(13, 5);
+        printf("{\"gaussian_filter\":");
+        gaussian_filter_samples(cfg, 7, rng);
+        printf("}\n");
+        return 0;
     }
     if (hgEdges) {
         // tests/golden/hg_edge_vectors.json, a file of its own so that ref_vectors.json (one line)
@@ -443,24 +567,9 @@ int main(int argc, char **argv) {
     // ---- GaussianFilter sampling (filters.h:80-118, filters.cpp:133-147) -----
     {
         j.key("gaussian_filter");
-        printf("[");
         const float cfg[][3] = {{1.5f, 1.5f, 0.5f}, {0.5f, 0.5f, 0.5f}, {2.f, 1.f, 0.75f}};
         RNG rng(11, 3);
-        for (int c = 0; c < 3; ++c) {
-            GaussianFilter gf(Vector2f(cfg[c][0], cfg[c][1]), cfg[c][2]);
-            printf("%s{\"rx\":%u,\"ry\":%u,\"sigma\":%u,\"samples\":[", c ? "," : "", fb(cfg[c][0]), fb(cfg[c][1]),
-                   fb(cfg[c][2]));
-            for (int i = 0; i < 96; ++i) {
-                Point2f u(rng.Uniform<Float>(), rng.Uniform<Float>());
-                if (i == 0) u = Point2f(0.f, 0.f);
-                if (i == 1) u = Point2f(0.99999994f, 0.99999994f);
-                if (i == 2) u = Point2f(0.5f, 0.5f);
-                FilterSample fs = gf.Sample(u);
-                printf("%s[%u,%u,%u,%u,%u]", i ? "," : "", fb(u.x), fb(u.y), fb(fs.p.x), fb(fs.p.y), fb(fs.weight));
-            }
-            printf("]}");
-        }
-        printf("]");
+        gaussian_filter_samples(cfg, 3, rng);
     }
 
     // ---- Perlin noise (CloudMedium density generator inputs) ---------------

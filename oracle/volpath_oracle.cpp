@@ -1811,9 +1811,22 @@ static Spec Li(const SceneView &sv, Ray ray, Lambda &l, Sampler &sampler, int *n
 
 // RayIntegrator::EvaluatePixelSample — integrators.cpp:235-298 (+ GetCameraSample samplers.h:797-815)
 struct SampleResult { Spec L; Lambda l; float weight; };
-static SampleResult EvaluatePixelSample(const SceneView &sv, int px, int py, int sampleIndex, int *nEvents) {
+// Orthographic / PerspectiveCamera::GenerateRay for a raster point (GenerateRayDifferential's main
+// ray), then RenderFromCamera
+static Ray CameraRayAt(const SceneView &sv, float pFilmX, float pFilmY) {
+    V3 pCamera = XPoint(sv.rasterX.m, V3{pFilmX, pFilmY, 0.f});
+    Ray ray;
+    if (sv.s.camera_type == 0) ray = {pCamera, {0.f, 0.f, 1.f}};
+    else ray = {{0.f, 0.f, 0.f}, Normalize(pCamera)};
+    return XRay(sv.cameraX, ray, nullptr, /*inverse=*/false);
+}
+
+// The camera sample of EvaluatePixelSample, everything before Li: the sampler's wavelength, filter,
+// time and lens draws, the filter sample and the camera ray in render space. pFilm (may be null)
+// receives the raster point.
+static Ray GenerateCameraSample(const SceneView &sv, int px, int py, int sampleIndex, Sampler &sampler, Lambda *lOut,
+                                float *weightOut, float *pFilm) {
     const OracleScene &s = sv.s;
-    Sampler sampler;
     sampler.Start(s, px, py, sampleIndex);
     float lu = sampler.Get1D();
     // Film::SampleWavelengths: RGBFilm SampleVisible, SpectralFilm SampleUniform
@@ -1831,12 +1844,19 @@ static SampleResult EvaluatePixelSample(const SceneView &sv, int px, int py, int
     sampler.Get1D();                      // time
     float ul0, ul1;
     sampler.Get2D(&ul0, &ul1);            // lens
-    // Camera ray (GenerateRayDifferential main ray, then RenderFromCamera)
-    V3 pCamera = XPoint(sv.rasterX.m, V3{pFilmX, pFilmY, 0.f});
-    Ray ray;
-    if (s.camera_type == 0) ray = {pCamera, {0.f, 0.f, 1.f}};
-    else ray = {{0.f, 0.f, 0.f}, Normalize(pCamera)};
-    ray = XRay(sv.cameraX, ray, nullptr, /*inverse=*/false);
+    Ray ray = CameraRayAt(sv, pFilmX, pFilmY);
+    *lOut = l;
+    *weightOut = filterWeight;
+    if (pFilm) { pFilm[0] = pFilmX; pFilm[1] = pFilmY; }
+    return ray;
+}
+
+static SampleResult EvaluatePixelSample(const SceneView &sv, int px, int py, int sampleIndex, int *nEvents) {
+    const OracleScene &s = sv.s;
+    Sampler sampler;
+    Lambda l;
+    float filterWeight;
+    Ray ray = GenerateCameraSample(sv, px, py, sampleIndex, sampler, &l, &filterWeight, nullptr);
     Spec L = Spec::Const(1.f) * Li(sv, ray, l, sampler, nEvents);
     bool bad = false;
     for (int i = 0; i < NS; ++i) if (std::isnan(L.v[i])) bad = true;
@@ -2030,6 +2050,37 @@ int oracle_pixel_sample(const OracleScene *s, int px, int py, int sampleIndex, f
     for (int i = 0; i < NS; ++i) { L[i] = r.L.v[i]; lambda[i] = r.l.lambda[i]; pdf[i] = r.l.pdf[i]; }
     if (weight) *weight = r.weight;
     return nEvents;
+}
+
+// What oracle_pixel_sample computes before its first segment: the render-space camera ray with
+// the origin after the medium-interface entry (o, d), the first segment's free-flight draw (u: the
+// third 1D draw behind the camera sample, after the two that seed the segment's RNG), the raster
+// point (pFilm, 2) and the filter weight. Outputs may be null.
+void oracle_camera_ray(const OracleScene *s, int px, int py, int sampleIndex, float *o, float *d, float *u,
+                       float *pFilm, float *weight) {
+    SceneView sv(*s);
+    Sampler sampler;
+    Lambda l;
+    float w;
+    Ray ray = GenerateCameraSample(sv, px, py, sampleIndex, sampler, &l, &w, pFilm);
+    if (s->boundary) ray.o = InterfaceEntry(*s, ray.o, ray.d);   // Li's first statement
+    sampler.Get1D();
+    sampler.Get1D();
+    const float u0 = sampler.Get1D();
+    if (o) { o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; }
+    if (d) { d[0] = ray.d.x; d[1] = ray.d.y; d[2] = ray.d.z; }
+    if (u) *u = u0;
+    if (weight) *weight = w;
+}
+
+// The render-space camera rays through n raster points (pFilm, n x 2), before any interface entry
+void oracle_camera_rays_at(const OracleScene *s, int n, const float *pFilm, float *o, float *d) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        Ray ray = CameraRayAt(sv, pFilm[2 * i], pFilm[2 * i + 1]);
+        o[3 * i] = ray.o.x; o[3 * i + 1] = ray.o.y; o[3 * i + 2] = ray.o.z;
+        d[3 * i] = ray.d.x; d[3 * i + 1] = ray.d.y; d[3 * i + 2] = ray.d.z;
+    }
 }
 
 // Film accumulation for samples [spp0, spp1) of every pixel; rgbSum[W*H*3], wSum[W*H] (fp64).

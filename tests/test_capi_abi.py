@@ -18,7 +18,7 @@ def declared_symbols():
 def test_header_declares_the_boundary():
     syms = declared_symbols()
     for must in ("avr_context_create", "avr_medium_grid", "avr_lights", "avr_camera", "avr_film", "avr_render",
-                 "avr_film_read", "avr_last_error"):
+                 "avr_film_read", "avr_last_error", "avr_last_pass_rays"):
         assert must in syms
 
 
