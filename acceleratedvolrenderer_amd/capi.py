@@ -186,6 +186,8 @@ SIGNATURES = {
     "avr_get_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AvrStats)]),
     "avr_reset_stats": (ctypes.c_int, [ctypes.c_void_p]),
     "avr_film_read": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
+    "avr_film_pixel_bounds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "avr_film_get_bounds": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p]),
     "avr_film_spectral": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float]),
     "avr_film_read_spectral": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
     "avr_film_spectral_device_ptrs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
@@ -548,6 +550,9 @@ class Context:
         if getattr(film, "nbuckets", 0):
             _check(self.lib.avr_film_spectral(self.h, int(film.nbuckets), float(film.lambdamin),
                                               float(film.lambdamax)))
+        pb = tuple(getattr(film, "pixel_bounds", (0, 0, film.width, film.height)))
+        if pb != (0, 0, film.width, film.height):
+            self.film_pixel_bounds(*pb)
         flt = film.filter
         _check(self.lib.avr_set_filter(self.h, int(flt.type_id), _fp(f32(flt.radius)), float(flt.sigma)))
         _check(self.lib.avr_set_sampler(self.h, int(scene.sampler.type_id), int(scene.sampler.pixelsamples)))
@@ -573,6 +578,17 @@ class Context:
 
     def film_clear(self):
         _check(self.lib.avr_film_clear(self.h))
+
+    def film_pixel_bounds(self, x0, y0, x1, y1):
+        """avr_film_pixel_bounds: render and store the pixels [x0, x1) x [y0, y1) of the film only
+        (the sums are reallocated and zeroed; every npix below is then the bounds' pixel count)."""
+        _check(self.lib.avr_film_pixel_bounds(self.h, int(x0), int(y0), int(x1), int(y1)))
+
+    def film_bounds(self):
+        """(x0, y0, x1, y1) of the film's pixel bounds (avr_film_get_bounds)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        _check(self.lib.avr_film_get_bounds(self.h, *[ctypes.byref(a) for a in v]))
+        return tuple(a.value for a in v)
 
     def render(self, spp_begin, spp_end, seed, max_depth):
         _check(self.lib.avr_render(self.h, int(spp_begin), int(spp_end), int(seed), int(max_depth)))
@@ -880,6 +896,9 @@ class Context:
 
     def film_set_reference(self, reference_rgb, output_from_sensor, fp16=True):
         ref = np.ascontiguousarray(reference_rgb, np.float32)
+        x0, y0, x1, y1 = self.film_bounds()
+        if ref.size != 3 * (x1 - x0) * (y1 - y0):
+            raise ValueError(f"reference image must hold the film's pixel bounds: {(y1 - y0, x1 - x0, 3)}")
         m = np.ascontiguousarray(output_from_sensor, np.float32).reshape(9)
         _check(self.lib.avr_film_set_reference(self.h, _fp(ref), _fp(m), 1 if fp16 else 0))
 

@@ -1307,7 +1307,7 @@ template <typename Setup, typename Restore>
 static int probe_loop(avr_context *c, int n, Setup setup, Restore restore, int spp_begin, int spp_end, int seed,
                       int max_depth, int *bestk, float *ms, int prefer = -1, const std::vector<char> *same = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     const size_t nd = (4 + 2 * (size_t)std::max(0, c->film.nbuckets)) * np;
     double *saved = nullptr;
     HIP_TRY(dalloc(&saved, nd));
@@ -1731,6 +1731,8 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     c->film = {};
     c->film.width = width;
     c->film.height = height;
+    c->film.bw = width;   // the bounds: the whole film (avr_film_pixel_bounds)
+    c->film.bh = height;
     c->film.filter_rx = fr[0];
     c->film.filter_ry = fr[1];
     c->film.xyz = c->d_xyz;
@@ -1741,6 +1743,59 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     HIP_TRY(dalloc(&c->film.w_sum, np));
     c->has_film = true;
     return avr_film_clear(c);
+}
+
+// Film::pixelBounds (film.h:67, film.cpp:97-172): the film's sums, readbacks and per-sample
+// records shrink to [x0, x1) x [y0, y1); samplers and the camera keep the full resolution, so
+// the bounds' pixels get the samples they get in a render of the whole film.
+int avr_film_pixel_bounds(avr_context *c, int x0, int y0, int x1, int y1) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_film) return fail(AVR_ERR_STATE, "pixel bounds need a film (avr_film first)");
+    if (x0 >= x1 || y0 >= y1) return fail(AVR_ERR_ARG, "pixel bounds are empty");
+    if (x0 < 0 || y0 < 0 || x1 > c->film.width || y1 > c->film.height)
+        return fail(AVR_ERR_ARG, "pixel bounds [" + std::to_string(x0) + ", " + std::to_string(x1) + ") x [" +
+                                     std::to_string(y0) + ", " + std::to_string(y1) + ") reach outside the " +
+                                     std::to_string(c->film.width) + " x " + std::to_string(c->film.height) + " film");
+    HIP_TRY(hipSetDevice(c->device));
+    // what was made for the old bounds: the pixel order, the analysis sums, the metric reference,
+    // the ZSobol pixel and level-A tables, and the pass table and camera records built ahead
+    free_pixel_order(c);
+    if (c->d_aacc) (void)hipFree(c->d_aacc);
+    c->d_aacc = nullptr;
+    c->last = LastPass{};
+    if (c->d_reference) (void)hipFree(c->d_reference);
+    if (c->d_image) (void)hipFree(c->d_image);
+    c->d_reference = nullptr;
+    c->d_image = nullptr;
+    c->look.invalidate();
+    c->zs_key[0] = -1;
+    for (long long &k : c->zs_akey) k = -1;
+    if (c->film.rgb_sum) (void)hipFree(c->film.rgb_sum);
+    if (c->film.w_sum) (void)hipFree(c->film.w_sum);
+    if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
+    c->film.rgb_sum = c->film.w_sum = c->film.bucket_sum = c->film.bucket_w = nullptr;
+    c->film.x0 = x0;
+    c->film.y0 = y0;
+    c->film.bw = x1 - x0;
+    c->film.bh = y1 - y0;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
+    HIP_TRY(dalloc(&c->film.rgb_sum, 3 * np));
+    HIP_TRY(dalloc(&c->film.w_sum, np));
+    if (c->film.nbuckets > 0) {
+        const size_t nb = np * c->film.nbuckets;
+        HIP_TRY(dalloc(&c->film.bucket_sum, 2 * nb));
+        c->film.bucket_w = c->film.bucket_sum + nb;
+    }
+    return avr_film_clear(c);
+}
+
+int avr_film_get_bounds(avr_context *c, int *x0, int *y0, int *x1, int *y1) {
+    if (!c || !c->has_film || !x0 || !y0 || !x1 || !y1) return fail(AVR_ERR_STATE, "no film or null argument");
+    *x0 = c->film.x0;
+    *y0 = c->film.y0;
+    *x1 = c->film.x0 + c->film.bw;
+    *y1 = c->film.y0 + c->film.bh;
+    return AVR_OK;
 }
 
 // FilterSampler tables of GaussianFilter(radius, sigma) — filters.h:80-118,
@@ -1825,7 +1880,7 @@ int avr_set_pixel_order(avr_context *c, const int *order, long long n) {
     HIP_TRY(hipSetDevice(c->device));
     free_pixel_order(c);
     if (!order) return AVR_OK;   // scanline
-    const long long np = (long long)c->film.width * c->film.height;
+    const long long np = (long long)c->film.bw * c->film.bh;
     if (n != np) return fail(AVR_ERR_ARG, "pixel order must list every pixel of the film once");
     std::vector<int> slot((size_t)np, -1);
     for (long long j = 0; j < np; ++j) {
@@ -1870,7 +1925,7 @@ int avr_set_sampler(avr_context *c, int kind, int samples_per_pixel) {
 
 int avr_film_clear(avr_context *c) {
     if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     HIP_TRY(hipMemsetAsync(c->film.rgb_sum, 0, 3 * np * sizeof(double), c->stream));
     HIP_TRY(hipMemsetAsync(c->film.w_sum, 0, np * sizeof(double), c->stream));
     if (c->film.nbuckets > 0)
@@ -1893,7 +1948,7 @@ int avr_film_spectral(avr_context *c, int n_buckets, float lambda_min, float lam
     c->film.lmin = lambda_min;
     c->film.lmax = lambda_max;
     if (n_buckets > 0) {
-        const size_t nb = (size_t)c->film.width * c->film.height * n_buckets;
+        const size_t nb = (size_t)c->film.bw * c->film.bh * n_buckets;
         HIP_TRY(dalloc(&c->film.bucket_sum, 2 * nb));
         c->film.bucket_w = c->film.bucket_sum + nb;
     }
@@ -2008,7 +2063,7 @@ int avr_reset_stats(avr_context *c) {
 static constexpr int kMetricBlocks = 1024;
 
 static int film_image(avr_context *c, const avr::Mat3 &M, int fp16, float *d_out) {
-    const long long np = (long long)c->film.width * c->film.height;
+    const long long np = (long long)c->film.bw * c->film.bh;
     hipLaunchKernelGGL(avr::k_film_image, dim3(blocks_for(np, 256, 4096)), dim3(256), 0, c->stream, c->film, M,
                        fp16, d_out);
     HIP_TRY(hipGetLastError());
@@ -2026,7 +2081,7 @@ int avr_film_image_device(avr_context *c, const float out_from_sensor[9], int fp
 int avr_film_set_reference(avr_context *c, const float *reference_rgb, const float out_from_sensor[9], int fp16) {
     if (!c || !c->has_film || !reference_rgb || !out_from_sensor) return fail(AVR_ERR_STATE, "no film or null argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     if (c->d_reference) (void)hipFree(c->d_reference);
     if (c->d_image) (void)hipFree(c->d_image);
     c->d_reference = nullptr;
@@ -2048,7 +2103,7 @@ int avr_film_metric(avr_context *c, int metric, float *out) {
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = film_image(c, c->ref_out_from_sensor, c->ref_fp16, c->d_image))) return rc;
-    const int np = c->film.width * c->film.height;
+    const int np = c->film.bw * c->film.bh;
     double *tot = c->d_metric + (size_t)kMetricBlocks * avr::kMetricSlots;
     hipLaunchKernelGGL(avr::k_metric, dim3(kMetricBlocks), dim3(256), 0, c->stream, c->d_image, c->d_reference, np,
                        metric, c->d_metric);
@@ -2059,7 +2114,7 @@ int avr_film_metric(avr_context *c, int metric, float *out) {
     HIP_TRY(hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // / (Float(xres) * Float(yres)); ME rounds its sums to float first (image.cpp:573-577)
-    const float npix = (float)c->film.width * (float)c->film.height;
+    const float npix = (float)c->film.bw * (float)c->film.bh;
     const int n = metric == 3 ? 9 : 3;
     for (int k = 0; k < n; ++k) out[k] = metric == 3 ? (float)h[k] / npix : (float)(h[k] / npix);
     return AVR_OK;
@@ -2113,7 +2168,7 @@ int avr_flip(avr_context *c, const float *test, const float *ref, int width, int
 
 int avr_film_read(avr_context *c, double *rgb, double *w) {
     if (!c || !c->has_film || !rgb || !w) return fail(AVR_ERR_STATE, "no film");
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     HIP_TRY(hipMemcpyAsync(rgb, c->film.rgb_sum, 3 * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(w, c->film.w_sum, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2123,7 +2178,7 @@ int avr_film_read(avr_context *c, double *rgb, double *w) {
 int avr_film_read_spectral(avr_context *c, double *bucket_sums, double *weight_sums) {
     if (!c || !c->has_film || c->film.nbuckets <= 0) return fail(AVR_ERR_STATE, "no spectral film");
     if (!bucket_sums || !weight_sums) return fail(AVR_ERR_ARG, "null buffer");
-    const size_t nb = (size_t)c->film.width * c->film.height * c->film.nbuckets;
+    const size_t nb = (size_t)c->film.bw * c->film.bh * c->film.nbuckets;
     HIP_TRY(hipMemcpyAsync(bucket_sums, c->film.bucket_sum, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(weight_sums, c->film.bucket_w, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2149,7 +2204,7 @@ int avr_last_pass_samples(avr_context *c, float *L, float *lambda, float *pdf, l
                           int *ns) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film || !L || !lambda || !pdf || !first || !ns) return fail(AVR_ERR_ARG, "null arg");
-    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const long long n = (long long)c->film.bw * c->film.bh * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n > 0 && c->last.persistent && c->last.order_gen != c->order_gen)
         return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
@@ -2166,7 +2221,7 @@ int avr_last_pass_samples(avr_context *c, float *L, float *lambda, float *pdf, l
         }
         HIP_TRY(hipMemcpy(pdf, c->set.cam4, n * sizeof(float4), hipMemcpyDeviceToHost));
         if (!c->h_pix_slot.empty()) {   // slot order -> pixel order
-            const long long np = (long long)c->film.width * c->film.height;
+            const long long np = (long long)c->film.bw * c->film.bh;
             std::vector<float> tmp(4 * (size_t)np);
             for (float *a : {L, lambda, pdf})
                 for (long long sb = 0; sb < n; sb += np) {
@@ -2194,7 +2249,7 @@ int avr_last_kernel(avr_context *c, char *buf, int cap) {
 int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film || !w) return fail(AVR_ERR_ARG, "null arg");
-    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const long long n = (long long)c->film.bw * c->film.bh * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n > 0 && c->last.persistent && c->filter_type != 0 && c->last.order_gen != c->order_gen)
         return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
@@ -2203,7 +2258,7 @@ int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
     } else if (n > 0 && c->last.persistent) {
         std::vector<float> camw((size_t)n);
         HIP_TRY(hipMemcpy(camw.data(), c->set.camw, n * sizeof(float), hipMemcpyDeviceToHost));
-        const long long np = (long long)c->film.width * c->film.height;
+        const long long np = (long long)c->film.bw * c->film.bh;
         for (long long i = 0; i < n; ++i)
             w[i] = camw[c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]];
     } else if (n > 0) {
@@ -2215,7 +2270,7 @@ int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
 int avr_last_pass_rays(avr_context *c, float *o3, float *d3, float *u, long long n_max) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
-    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const long long n = (long long)c->film.bw * c->film.bh * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n > 0 && !c->last.persistent)
         return fail(AVR_ERR_STATE, "the last pass was not a persistent one (the wavefront path consumes its rays)");
@@ -2226,7 +2281,7 @@ int avr_last_pass_rays(avr_context *c, float *o3, float *d3, float *u, long long
     std::vector<float> cam0(4 * (size_t)n), cam1(4 * (size_t)n);
     HIP_TRY(hipMemcpy(cam0.data(), c->set.cam0, n * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cam1.data(), c->set.cam1, n * sizeof(float4), hipMemcpyDeviceToHost));
-    const long long np = (long long)c->film.width * c->film.height;
+    const long long np = (long long)c->film.bw * c->film.bh;
     for (long long i = 0; i < n; ++i) {
         const size_t src = (size_t)(c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]);
         for (int k = 0; k < 3; ++k) {
@@ -2240,7 +2295,7 @@ int avr_last_pass_rays(avr_context *c, float *o3, float *d3, float *u, long long
 
 int avr_film_export_device(avr_context *c, void *dst) {
     if (!c || !c->has_film || !dst) return fail(AVR_ERR_STATE, "no film");
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     double *d = (double *)dst;
     HIP_TRY(hipMemcpyAsync(d, c->film.rgb_sum, 3 * np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d + 3 * np, c->film.w_sum, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -2259,8 +2314,9 @@ int avr_film_reduce_rccl(avr_context **ctxs, int n, int root) {
     for (int i = 0; i < n; ++i) {
         if (!ctxs[i] || !ctxs[i]->has_film) return fail(AVR_ERR_STATE, "film reduce: context without a film");
         const avr::DevFilm &a = ctxs[i]->film, &b = ctxs[root]->film;
-        if (a.width != b.width || a.height != b.height || a.nbuckets != b.nbuckets)
-            return fail(AVR_ERR_ARG, "film reduce: films differ in resolution or buckets");
+        if (a.width != b.width || a.height != b.height || a.nbuckets != b.nbuckets || a.x0 != b.x0 || a.y0 != b.y0 ||
+            a.bw != b.bw || a.bh != b.bh)
+            return fail(AVR_ERR_ARG, "film reduce: films differ in resolution, pixel bounds or buckets");
         for (int j = 0; j < i; ++j)
             if (ctxs[j]->device == ctxs[i]->device) return fail(AVR_ERR_ARG, "film reduce: one context per GPU");
     }
@@ -2287,7 +2343,7 @@ int avr_film_reduce_rccl(avr_context **ctxs, int n, int root) {
     }
     std::vector<ncclComm_t> comms(n);
     for (int i = 0; i < n; ++i) comms[i] = ctxs[i]->comm;
-    const size_t np = (size_t)ctxs[root]->film.width * ctxs[root]->film.height;
+    const size_t np = (size_t)ctxs[root]->film.bw * ctxs[root]->film.bh;
     const size_t nb = (size_t)ctxs[root]->film.nbuckets;
     ncclResult_t r = ncclGroupStart();
     for (int i = 0; r == ncclSuccess && i < n; ++i) {

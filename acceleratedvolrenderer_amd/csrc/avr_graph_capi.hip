@@ -1079,7 +1079,7 @@ int avr_graph_analyze(avr_context *c, const avr_graph_index *idx, const float gr
 int avr_graph_analysis_clear(avr_context *c) {
     if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
     if (!c->d_aacc) return AVR_OK;   // nothing analysed on this film yet: the sums start at zero
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     HIP_TRY(hipMemsetAsync(c->d_aacc, 0, np * sizeof(avr::graph::AnalyzeAcc), c->stream));
     return AVR_OK;
 }
@@ -1088,7 +1088,7 @@ int avr_graph_analysis_read(avr_context *c, unsigned long long *total, unsigned 
                             unsigned long long *search, unsigned long long *in_range, double *range_sum) {
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
-    const size_t np = (size_t)c->film.width * c->film.height;
+    const size_t np = (size_t)c->film.bw * c->film.bh;
     std::vector<avr::graph::AnalyzeAcc> h(np, avr::graph::AnalyzeAcc{0, 0, 0, 0, 0.0});
     if (c->d_aacc) HIP_TRY(hipMemcpy(h.data(), c->d_aacc, np * sizeof(avr::graph::AnalyzeAcc), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < np; ++i) {
@@ -1106,7 +1106,7 @@ int avr_graph_analyze_last_pass(avr_context *c, float *o, float *d, int *counts,
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
     if (c->last.analyze != 2) return fail(AVR_ERR_STATE, "the last render was not avr_graph_analyze's with detail");
-    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const long long n = (long long)c->film.bw * c->film.bh * c->last.S;
     const int md = c->last.analyze_depth;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (max_depth != md) return fail(AVR_ERR_ARG, "max_depth differs from the analysis'");
@@ -1155,7 +1155,7 @@ int avr_graph_last_pass(avr_context *c, float *o, float *d, float *points, int *
     AVR_QUIESCE(c);
     if (!c || !c->has_film) return fail(AVR_ERR_ARG, "null arg");
     if (!c->last.graph) return fail(AVR_ERR_STATE, "the last render was not avr_graph_render's");
-    const long long n = (long long)c->film.width * c->film.height * c->last.S;
+    const long long n = (long long)c->film.bw * c->film.bh * c->last.S;
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n == 0) return AVR_OK;
     std::vector<float4> h((size_t)n);

@@ -10,7 +10,7 @@ namespace avr {
 // round-to-nearest-even half conversion.
 struct Mat3 { float m[9]; };
 __global__ void __launch_bounds__(256) k_film_image(DevFilm F, Mat3 M, int fp16, float *__restrict__ out) {
-    const int np = F.width * F.height;
+    const int np = F.bw * F.bh;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < np; p += gridDim.x * blockDim.x) {
         float r = (float)F.rgb_sum[3 * p], g = (float)F.rgb_sum[3 * p + 1], b = (float)F.rgb_sum[3 * p + 2];
         const float w = (float)F.w_sum[p];

@@ -234,15 +234,19 @@ struct DevCamera {
 };
 
 struct DevFilm {
-    int width, height;
+    int width, height;                // the full resolution: the sampler's and the camera's domain
+    // Pixel bounds [x0, x0 + bw) x [y0, y0 + bh) inside it (pbrt's Film::pixelBounds; the whole
+    // film by default). The kernels walk the bounds' bw * bh pixels and the sums below hold those
+    // only, row-major within the bounds; samplers and cameras take the absolute pixel.
+    int x0, y0, bw, bh;
     float filter_rx, filter_ry;
     int filter_type;                  // 0 BoxFilter, 1 GaussianFilter (FilterSampler tables below)
     smp::FilterTables gauss;
     const float *xyz;                 // 3 x 471
     float imaging_ratio;
     float max_component;
-    double *rgb_sum;                  // W*H*3
-    double *w_sum;                    // W*H
+    double *rgb_sum;                  // bw*bh*3
+    double *w_sum;                    // bw*bh
     // SpectralFilm (film.h:401-530): nbuckets > 0 — uniform wavelengths over [lmin, lmax] and
     // per-pixel bucket sums next to the RGB sums (pixel-major: [pixel * nbuckets + b])
     int nbuckets;
@@ -361,7 +365,7 @@ struct Params {
     const int *pix_order;
     const int *pix_slot;
     FastDiv div_pixels;               // by pass_pixels
-    FastDiv div_width;                // by film.width
+    FastDiv div_width;                // by film.bw
 };
 
 // Kernel arguments re-read where they are used: k_paths' event handlers and collision block and
@@ -1245,7 +1249,7 @@ __device__ __forceinline__ void zsobol_draw_quad(smp::ZSobol &z, const smp::ZSob
     if (pe_ok || (zp.ptab && (int)z.dimension < zp.pdims)) {
         // the pass table (zsobol_pass_entry): the quad computes the varying digits only (those
         // below the perm-fixed digit iTop, the highest one under the pass's plo bits)
-        const uint64_t e = pe_ok ? pe : zp.ptab[(size_t)pm * (size_t)zp.pdims + z.dimension];
+        const uint64_t e = pe_ok ? pe : zp.ptab[(size_t)(pm & zp.rowmask) * (size_t)zp.pdims + z.dimension];
         const int iTop = (zp.plo + pw - 1) >> 1;
         const uint32_t perm = (uint32_t)(e >> 56);
         const uint64_t fx = (e & smp::pass_prefix_mask(zp)) << zp.plo;
@@ -1266,7 +1270,7 @@ __device__ __forceinline__ void zsobol_draw_quad(smp::ZSobol &z, const smp::ZSob
             }
         }
     } else {
-        const uint32_t up = (zp.upper && (int)z.dimension < zp.dmax) ? zp.upper[(size_t)pm * (size_t)zp.dmax + z.dimension]
+        const uint32_t up = (zp.upper && (int)z.dimension < zp.dmax) ? zp.upper[(size_t)(pm & zp.rowmask) * (size_t)zp.dmax + z.dimension]
                                                                        : smp::zsobol_upper(pm, z.dimension, zp);
         const int iHi = smp::zsobol_split(zp) - 1;
         if constexpr (kW == 2) {
@@ -1347,7 +1351,8 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
         // the camera stage and k_paths walk the pass in slot order; slot -> pixel by pix_order
         const int id = s * npix + slot;
         const int pix = P.pix_order ? P.pix_order[slot] : slot;
-        const int py = fdiv(pix, P.div_width), px = fmod_(pix, py, P.div_width);
+        // (pix: the pixel within the film's bounds, the index of the records and sums; px, py: in the film)
+        const int ly = fdiv(pix, P.div_width), px = fmod_(pix, ly, P.div_width) + P.film.x0, py = ly + P.film.y0;
         PathSampler<kSmp> smp;
         if constexpr (kSmp == 0) {
             const uint64_t seq = hash_3u32((uint32_t)px, (uint32_t)py, (uint32_t)P.seed);
@@ -1364,9 +1369,9 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
         [[maybe_unused]] bool pe_ok = false;
         if constexpr (kSmp != 0) {
             if (quad && P.zs.ptab && P.zs.pdims >= 10) {
-                const uint32_t pmk = PathSampler<kSmp>::kW == 2
-                                         ? (uint32_t)((((uint64_t)smp.z.hi << 32) | smp.z.morton) >> P.zs.log2spp)
-                                         : smp.z.morton >> P.zs.log2spp;
+                const uint32_t pmk = (PathSampler<kSmp>::kW == 2
+                                          ? (uint32_t)((((uint64_t)smp.z.hi << 32) | smp.z.morton) >> P.zs.log2spp)
+                                          : smp.z.morton >> P.zs.log2spp) & P.zs.rowmask;
                 // the pixel's compact copy (48 B, pixels consecutive along the wave) when built,
                 // else its pass-table row
                 const ulonglong2 *row = P.zs.ctab ? reinterpret_cast<const ulonglong2 *>(P.zs.ctab + 6 * (size_t)pix)
@@ -1480,7 +1485,7 @@ __global__ void __launch_bounds__(256) k_camera(Params P) {
     const int n = P.pass_pixels * P.pass_samples;
     for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
         const int pix = id % P.pass_pixels, s = id / P.pass_pixels;
-        const int px = pix % P.film.width, py = pix / P.film.width;
+        const int px = pix % P.film.bw + P.film.x0, py = pix / P.film.bw + P.film.y0;
         const int sampleIndex = P.sample_base + s;
         PathSampler<kZSobol> smp;
         smp.start(P, px, py, sampleIndex);
@@ -2747,7 +2752,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                         const int np = kParked ? P.pass_pixels : npix;
                         const int slot = g % np, sIdx = g / np;
                         const int pix = P.pix_order ? P.pix_order[slot] : slot;
-                        smp.start(P, pix % P.film.width, pix / P.film.width, P.sample_base + sIdx);
+                        smp.start(P, pix % P.film.bw + P.film.x0, pix / P.film.bw + P.film.y0, P.sample_base + sIdx);
                         s_ul[threadIdx.x] = ul5;
                         smp.z.dimension = 9;
                     } else {
@@ -3515,26 +3520,28 @@ __global__ void __launch_bounds__(256) k_majorant_rgb(const float4 *__restrict__
     }
 }
 
-// ZSobol pixel table: zsobol_upper for every pixel of the film and the first dmax
-// dimensions, row Morton(pixel) (zp.upper must be null here: the digits are computed).
-__global__ void __launch_bounds__(256) k_zsobol_table(smp::ZSobolParams zp, int width, int height, int dmax,
+// ZSobol pixel table: zsobol_upper for every pixel of the film's bounds (bw x bh pixels from
+// (x0, y0)) and the first dmax dimensions, row Morton(pixel) & zp.rowmask; the digits are those
+// of the pixel's Morton code in the film (zp.upper must be null here: they are computed).
+__global__ void __launch_bounds__(256) k_zsobol_table(smp::ZSobolParams zp, int x0, int y0, int bw, int bh, int dmax,
                                                       uint32_t *__restrict__ table) {
-    const long long n = (long long)width * height * dmax;
+    const long long n = (long long)bw * bh * dmax;
     for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
         const int d = (int)(k % dmax);
         const long long pix = k / dmax;
-        const uint32_t pm = (uint32_t)smp::encode_morton2((uint32_t)(pix % width), (uint32_t)(pix / width));
-        table[(size_t)pm * dmax + d] = smp::zsobol_upper(pm, (uint32_t)d, zp);
+        const uint32_t pm = (uint32_t)smp::encode_morton2((uint32_t)(x0 + pix % bw), (uint32_t)(y0 + pix / bw));
+        table[(size_t)(pm & zp.rowmask) * dmax + d] = smp::zsobol_upper(pm, (uint32_t)d, zp);
     }
 }
 
-// ZSobol pass table: zsobol_pass_entry for every pixel of the film and the first pdims
-// dimensions, for the pass whose sample indices agree with `base` above their low `plo` bits;
-// row Morton(pixel). The pixel digits come from the pixel table (zp.upper) where it covers
+// ZSobol pass table: zsobol_pass_entry for every pixel of the film's bounds (width x height
+// pixels from (x0, y0)) and the first pdims dimensions, for the pass whose sample indices agree
+// with `base` above their low `plo` bits; row Morton(pixel) & zp.rowmask, entries from the
+// pixel's Morton code in the film; `ctab` rows by the pixel's index within the bounds. The pixel digits come from the pixel table (zp.upper) where it covers
 // the dimension. zp.ptab must be null here. Built once per k_paths pass (a few hundred us);
 // with `atab` (the same table built for plo + 2, plo + 2 <= log2spp) each entry is derived
 // from its level-A entry by zsobol_pass_entry_from (one MixBits instead of ~5).
-__global__ void __launch_bounds__(256) k_zsobol_pass_table(smp::ZSobolParams zp, int width, int height, int pdims,
+__global__ void __launch_bounds__(256) k_zsobol_pass_table(smp::ZSobolParams zp, int x0, int y0, int width, int height, int pdims,
                                                            int plo, long long base, uint64_t *__restrict__ table,
                                                            const uint64_t *__restrict__ atab, FastDiv div_pairs,
                                                            FastDiv div_width, uint64_t *__restrict__ ctab) {
@@ -3548,9 +3555,9 @@ __global__ void __launch_bounds__(256) k_zsobol_pass_table(smp::ZSobolParams zp,
         const int pix = fdiv((int)k, div_pairs);
         const int d = 2 * (int)(k - (uint32_t)pix * half);
         const int py = fdiv(pix, div_width);
-        const uint32_t pm = (uint32_t)smp::encode_morton2((uint32_t)(pix - py * width), (uint32_t)py);
+        const uint32_t pm = (uint32_t)smp::encode_morton2((uint32_t)(x0 + pix - py * width), (uint32_t)(y0 + py));
         const uint64_t m = ((uint64_t)pm << zp.log2spp) | (uint64_t)base;
-        const size_t row = (size_t)pm * pdims + d;
+        const size_t row = (size_t)(pm & zp.rowmask) * pdims + d;
         ulonglong2 e;
         if (atab) {
             const ulonglong2 eA = *reinterpret_cast<const ulonglong2 *>(atab + row);
@@ -3560,7 +3567,7 @@ __global__ void __launch_bounds__(256) k_zsobol_pass_table(smp::ZSobolParams zp,
                        : smp::zsobol_pass_entry_from<uint32_t>((uint32_t)m, (uint32_t)d + 1, zp, plo, eA.y);
         } else {
             auto up_of = [&](int dd) -> uint32_t {
-                return (zp.upper && dd < zp.dmax) ? zp.upper[(size_t)pm * zp.dmax + dd] : smp::zsobol_upper(pm, (uint32_t)dd, zp);
+                return (zp.upper && dd < zp.dmax) ? zp.upper[(size_t)(pm & zp.rowmask) * zp.dmax + dd] : smp::zsobol_upper(pm, (uint32_t)dd, zp);
             };
             const uint32_t u0 = up_of(d), u1 = up_of(d + 1);
             e.x = wide ? smp::zsobol_pass_entry<uint64_t>(m, (uint32_t)d, zp, plo, u0)

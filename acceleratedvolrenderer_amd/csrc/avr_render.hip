@@ -10,7 +10,15 @@ static int pass_plo(long long base, int S) {
     while ((base >> plo) != ((base + S - 1) >> plo)) ++plo;
     return plo;
 }
-// what a built table depends on (a table built ahead is used only when the pass's key equals it)
+// The ZSobol tables' rows under the film's pixel bounds and the mask that maps a pixel's Morton
+// code to its row (ZSobolParams::rowmask): Morton(W - 1, H - 1) + 1 rows and the code itself for
+// the whole film, at most 4^ceil(log2 max(bw, bh)) rows for bounds inside it.
+static uint32_t film_rowmask(const avr_context *c, size_t *rows) {
+    const size_t full = (size_t)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
+    return avr::smp::zsobol_rowmask(c->film.bw, c->film.bh, full, rows);
+}
+// what a built table depends on (a table built ahead is used only when the pass's key equals it;
+// avr_film_pixel_bounds drops the tables built ahead, so the bounds are not part of it)
 static void ptab_key(const avr_context *c, const avr::smp::ZSobolParams &zs, long long base, int plo, long long *key) {
     const long long k[kPtabKey] = {base, plo, (long long)zs.log2spp, (long long)zs.seed,
                                    (long long)c->film.width * 65536 + c->film.height, c->zs_pdims,
@@ -22,8 +30,9 @@ static void ptab_key(const avr_context *c, const avr::smp::ZSobolParams &zs, lon
 // d_zs_ptab[buf] stays null (the pixel table / every digit per call serve the pass).
 static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParams &zs, long long base, int plo, int buf,
                       bool two_level) {
-    const long long P = (long long)c->film.width * c->film.height;
-    const size_t prow = (size_t)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
+    const long long P = (long long)c->film.bw * c->film.bh;
+    size_t prow;
+    (void)film_rowmask(c, &prow);
     const size_t need_e = prow * (size_t)c->zs_pdims;
     // the same headroom policy as the fat / bricked density copies: allocate only with >= 8 GiB
     // of HBM to spare
@@ -69,9 +78,10 @@ static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParam
             if (!same) {
                 hipLaunchKernelGGL(avr::k_zsobol_pass_table,
                                    dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s, zs,
-                                   c->film.width, c->film.height, c->zs_pdims, plo + 2, (base >> (plo + 2)) << (plo + 2),
-                                   c->d_zs_atab, (const uint64_t *)nullptr, avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)),
-                                   avr::fastdiv_make((uint32_t)c->film.width), (uint64_t *)nullptr);
+                                   c->film.x0, c->film.y0, c->film.bw, c->film.bh, c->zs_pdims, plo + 2,
+                                   (base >> (plo + 2)) << (plo + 2), c->d_zs_atab, (const uint64_t *)nullptr,
+                                   avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.bw),
+                                   (uint64_t *)nullptr);
                 HIP_TRY(hipGetLastError());
                 for (int k = 0; k < 6; ++k) c->zs_akey[k] = key[k];
             }
@@ -94,8 +104,8 @@ static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParam
     }
     uint64_t *ctab = need_c ? c->d_zs_ctab[buf] : nullptr;
     hipLaunchKernelGGL(avr::k_zsobol_pass_table, dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s,
-                       zs, c->film.width, c->film.height, c->zs_pdims, plo, base, c->d_zs_ptab[buf], atab,
-                       avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.width), ctab);
+                       zs, c->film.x0, c->film.y0, c->film.bw, c->film.bh, c->zs_pdims, plo, base, c->d_zs_ptab[buf], atab,
+                       avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.bw), ctab);
     HIP_TRY(hipGetLastError());
     return AVR_OK;
 }
@@ -141,8 +151,11 @@ static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobo
     }
     HIP_TRY(hipSetDevice(c->device));
     if (c->sampler_kind == 1) {
+        // the tables' rows: by the film's pixel bounds (the sampler's parameters above: by the film)
+        size_t rows;
+        zs.rowmask = film_rowmask(c, &rows);
         // The digits of GetSampleIndex above log2(spp) depend on (pixel, dimension) only:
-        // tabulate them once per film/sampler (k_zsobol_table), so each sampler call computes
+        // tabulate them once per film/bounds/sampler (k_zsobol_table; avr_film_pixel_bounds resets the key), so each sampler call computes
         // the log2(spp)/2 sample digits plus one load instead of all nBase4Digits
         const int key[3] = {c->sampler_spp, c->film.width, c->film.height};
         if (c->zs_key[0] != key[0] || c->zs_key[1] != key[1] || c->zs_key[2] != key[2]) {
@@ -153,17 +166,15 @@ static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobo
             c->d_zs_table = nullptr;
             for (int k = 0; k < 3; ++k) c->zs_key[k] = key[k];
             if (c->zs_dims > 0) {
-                const size_t rows =
-                    (size_t)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
                 if (hipMalloc((void **)&c->d_zs_table, rows * c->zs_dims * sizeof(uint32_t)) != hipSuccess) {
                     (void)hipGetLastError();
                     c->d_zs_table = nullptr;   // no room: every call computes all digits
                 } else {
                     EV_MARK(t0);
-                    hipLaunchKernelGGL(avr::k_zsobol_table, dim3(blocks_for((long long)c->film.width * c->film.height *
+                    hipLaunchKernelGGL(avr::k_zsobol_table, dim3(blocks_for((long long)c->film.bw * c->film.bh *
                                                                             c->zs_dims, 256, 256 * 64)),
-                                       dim3(256), 0, c->stream, zs, c->film.width, c->film.height, c->zs_dims,
-                                       c->d_zs_table);
+                                       dim3(256), 0, c->stream, zs, c->film.x0, c->film.y0, c->film.bw, c->film.bh,
+                                       c->zs_dims, c->d_zs_table);
                     HIP_TRY(hipGetLastError());
                     EV_MARK(t1);
                     c->timed.push_back({t0, t1, &avr_stats::ms_setup, false});
@@ -177,16 +188,17 @@ static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobo
     // only when its camera stage's arguments equal theirs byte for byte)
     std::memset(out, 0, sizeof *out);
     out->log2spp = zs.log2spp; out->nBase4Digits = zs.nBase4Digits; out->seed = zs.seed;
+    out->rowmask = zs.rowmask;
     out->upper = zs.upper; out->dmax = zs.dmax;
     out->ptab = zs.ptab; out->pdims = zs.pdims; out->plo = zs.plo; out->ctab = zs.ctab;
     return AVR_OK;
 }
 
-// A render call's split into passes of S <= Smax sample indices over all P pixels (P * S <=
+// A render call's split into passes of S <= Smax sample indices over the P pixels of the film's bounds (P * S <=
 // max_paths paths in flight), and the samples to allocate for its largest pass
 struct PassPlan { long long P, Smax, need; };
 static int pass_plan(const avr_context *c, bool persistent, int spp_begin, int spp_end, PassPlan *plan) {
-    plan->P = (long long)c->film.width * c->film.height;
+    plan->P = (long long)c->film.bw * c->film.bh;
     if (plan->P > (1ll << 30)) return fail(AVR_ERR_ARG, "film too large");
     const long long maxp = c->max_paths_set ? c->max_paths : (persistent ? (64ll << 20) : c->max_paths);
     plan->Smax = std::max<long long>(1, maxp / plan->P);
@@ -214,7 +226,7 @@ static void pass_params(const avr_context *c, const avr::smp::ZSobolParams &zs, 
     p->seed = seed;
     p->pass_pixels = (int)P;
     p->div_pixels = avr::fastdiv_make((uint32_t)P);
-    p->div_width = avr::fastdiv_make((uint32_t)c->film.width);
+    p->div_width = avr::fastdiv_make((uint32_t)c->film.bw);
     p->pass_samples = S;
     p->sample_base = (int)base;
     p->stats = c->d_stats;
@@ -301,10 +313,11 @@ static int pass_advance_table(avr_context *c, long long base, int S) {
 static int pass_table(avr_context *c, const RenderCall &rc, long long base, int S, avr::Params *p, bool *have,
                       bool *cam_ahead) {
     *have = *cam_ahead = false;
-    // rows = Morton(w-1, h-1) + 1 (up to ~4x the pixels of a non-square film): the table kernel
-    // indexes entries with 32 bits
-    const long long prow =
-        (long long)avr::smp::encode_morton2((uint32_t)c->film.width - 1, (uint32_t)c->film.height - 1) + 1;
+    // rows (film_rowmask): Morton(w-1, h-1) + 1 of the whole film (up to ~4x the pixels of a
+    // non-square one), fewer under pixel bounds: the table kernel indexes entries with 32 bits
+    size_t rows;
+    (void)film_rowmask(c, &rows);
+    const long long prow = (long long)rows;
     if (!(c->sampler_kind == 1 && c->zs_pdims > 0 && rc.plan.P * c->zs_pdims < (1ll << 31) &&
           prow * c->zs_pdims < (1ll << 31)))
         return AVR_OK;

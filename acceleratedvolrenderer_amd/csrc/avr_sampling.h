@@ -101,6 +101,12 @@ constexpr uint64_t kZPermW2 = 0x93634b1b87271e4eull;   // {2,3,0,1} .. {3,0,1,2}
 
 struct ZSobolParams {
     int log2spp, nBase4Digits, seed;
+    // The row of a pixel in the tables below is Morton(pixel) & rowmask. All ones: the row is
+    // the Morton code itself (the whole film). Under film pixel bounds of bw x bh pixels the
+    // host keeps the low ceil(log2 bw) x bits and ceil(log2 bh) y bits: pixels of the bounds
+    // differ there, so the tables have at most 4^ceil(log2 max(bw, bh)) rows wherever the
+    // bounds lie in the film. The entries themselves come from the full Morton code.
+    uint32_t rowmask;
     // Optional table of the pixel-only part of GetSampleIndex (zsobol_upper) for the first
     // `dmax` dimensions, row (Morton(pixel) * dmax + dimension); null = computed per call
     const uint32_t *upper;
@@ -301,13 +307,13 @@ AVR_HD M zsobol_index_pass(M morton, uint32_t dimension, const ZSobolParams &zp,
 template <typename M>
 AVR_HD M zsobol_index(M morton, uint32_t dimension, const ZSobolParams &zp, const uint8_t *zpt = nullptr) {
     if (zp.ptab && (int)dimension < zp.pdims) {
-        const uint32_t pm = (uint32_t)(morton >> zp.log2spp);
-        return zsobol_index_pass<M>(morton, dimension, zp, zp.ptab[(size_t)pm * (size_t)zp.pdims + dimension], zpt);
+        const uint32_t row = (uint32_t)(morton >> zp.log2spp) & zp.rowmask;
+        return zsobol_index_pass<M>(morton, dimension, zp, zp.ptab[(size_t)row * (size_t)zp.pdims + dimension], zpt);
     }
     uint32_t up;
     const uint32_t pm = (uint32_t)(morton >> zp.log2spp);
     if (zp.upper && (int)dimension < zp.dmax)
-        up = zp.upper[(size_t)pm * (size_t)zp.dmax + dimension];
+        up = zp.upper[(size_t)(pm & zp.rowmask) * (size_t)zp.dmax + dimension];
     else
         up = zsobol_upper(pm, dimension, zp);
     return ((M)up << zp.log2spp) | (M)zsobol_lower<M>(morton, dimension, zp);
@@ -393,6 +399,7 @@ inline ZSobolParams zsobol_params(int spp, int width, int height, int seed) {
     const int res = (int)round_up_pow2((uint32_t)(width > height ? width : height));
     zp.nBase4Digits = ilog2((uint32_t)res) + (zp.log2spp + 1) / 2;
     zp.seed = seed;
+    zp.rowmask = 0xffffffffu;
     zp.upper = nullptr;
     zp.dmax = 0;
     zp.ptab = nullptr;
@@ -400,6 +407,22 @@ inline ZSobolParams zsobol_params(int spp, int width, int height, int seed) {
     zp.plo = 0;
     zp.ctab = nullptr;
     return zp;
+}
+
+// The table row mask (ZSobolParams::rowmask) of film pixel bounds of bw x bh pixels, and the rows
+// a table under it needs: pixels of one bounds rectangle differ in their low ceil(log2 bw) x bits
+// or their low ceil(log2 bh) y bits, whose Morton interleave is the mask. `full_rows` =
+// Morton(W - 1, H - 1) + 1, the rows of the whole film: bounds whose mask would not need fewer
+// keep the Morton code as the row (all ones).
+inline uint32_t zsobol_rowmask(int bw, int bh, size_t full_rows, size_t *rows) {
+    const uint32_t mx = bw > 1 ? round_up_pow2((uint32_t)bw) - 1 : 0, my = bh > 1 ? round_up_pow2((uint32_t)bh) - 1 : 0;
+    const uint64_t mask = encode_morton2(mx, my);
+    if (mask + 1 >= (uint64_t)full_rows) {
+        *rows = full_rows;
+        return 0xffffffffu;
+    }
+    *rows = (size_t)mask + 1;
+    return (uint32_t)mask;
 }
 
 // ---------------------------------------------------------------------------

@@ -942,7 +942,7 @@ class GraphIntegrator(FilmIntegrator):
         or -1; with voxel_view p is the lit voxel's chord middle in graph space and count 1 / 0
         where a lit voxel was hit, -1 elsewhere."""
         f = self.scene.film
-        npix = f.width * f.height
+        npix = f.npix    # the film's pixel bounds
         ms = self.spp if max_samples is None else int(max_samples)
         first, ns, L, lam, pdf = self.ctx.last_pass_samples(npix, ms)
         o, d, p, count = self.ctx.graph_last_pass(npix, ms)
@@ -1072,7 +1072,8 @@ class IntegrationAnalyzer:
 
     def result(self):
         f = self.scene.film
-        return GraphAnalysis(f.width, f.height, self.maxdepth, self.spp, *self.ctx.graph_analysis_read(f.width * f.height))
+        # (the maps cover the film's pixel bounds: pixel (x, y) of a map is (x0 + x, y0 + y) of the film)
+        return GraphAnalysis(f.crop_width, f.crop_height, self.maxdepth, self.spp, *self.ctx.graph_analysis_read(f.npix))
 
     def last_pass(self, max_samples=None):
         """The last pass of analyze(detail=True) per sample: dict of first sample index, sample
@@ -1081,7 +1082,7 @@ class IntegrationAnalyzer:
         range_sum (n, maxdepth; zero past count); n = pixels x samples of that pass, element
         s * pixels + pixel."""
         f = self.scene.film
-        npix = f.width * f.height
+        npix = f.npix    # the film's pixel bounds
         ms = self.spp if max_samples is None else int(max_samples)
         o, d, count, p, node, in_range, range_sum = self.ctx.graph_analyze_last_pass(npix, ms, self.maxdepth)
         first, ns, _, lam, _ = self.ctx.last_pass_samples(npix, ms)

@@ -56,6 +56,17 @@ def reduce_film(buf, npix, nbuckets, rank, group=None):
 GRID_LAYOUTS = {"linear": 0, "fat": 1, "brick": 2}
 GRID_LAYOUT_NAMES = {v: k for k, v in GRID_LAYOUTS.items()}
 
+
+def tile_bounds(bounds, tile):
+    """The tiles of (tw, th) pixels that cover bounds = (x0, y0, x1, y1), row by row from its
+    corner, the last of a row or column cut at the bounds: every pixel in exactly one tile."""
+    x0, y0, x1, y1 = (int(v) for v in bounds)
+    tw, th = int(tile[0]), int(tile[1])
+    if tw < 1 or th < 1:
+        raise ValueError("tile sizes must be positive")
+    return [(x, y, min(x + tw, x1), min(y + th, y1)) for y in range(y0, y1, th) for x in range(x0, x1, tw)]
+
+
 class FilmIntegrator:
     """What every integrator here shares: a context (self.ctx) with the scene set, the sample
     loop's entry and the film's readback, image and file output. A subclass sets scene, spp,
@@ -73,16 +84,25 @@ class FilmIntegrator:
         self._render_range(spp_begin, spp_end)
         return self.film_sums()
 
-    def film_sums(self):
+    def set_pixel_bounds(self, bounds):
+        """Render and store the pixels bounds = (x0, y0, x1, y1) of the film from now on
+        (avr_film_pixel_bounds: the sums start at zero); None returns to the whole film. The
+        scene's film carries the bounds, so its images and readbacks follow."""
         f = self.scene.film
-        return self.ctx.film_read(f.width * f.height)
+        b = (0, 0, f.width, f.height) if bounds is None else tuple(int(v) for v in bounds)
+        self.ctx.film_pixel_bounds(*b)
+        f.pixel_bounds = b
+
+    def film_sums(self):
+        """(rgb_sum, w_sum) fp64 of the film's pixel bounds, row-major within them."""
+        return self.ctx.film_read(self.scene.film.npix)
 
     def spectral_sums(self):
-        """SpectralFilm Pixel::bucketSums / weightSums, (W*H, nbuckets) fp64 each."""
+        """SpectralFilm Pixel::bucketSums / weightSums, (pixels of the bounds, nbuckets) fp64 each."""
         f = self.scene.film
         if not getattr(f, "nbuckets", 0):
             raise ValueError("the scene's film is not a SpectralFilm")
-        return self.ctx.film_read_spectral(f.width * f.height, f.nbuckets)
+        return self.ctx.film_read_spectral(f.npix, f.nbuckets)
 
     def spectral_image(self, fp16=True):
         """SpectralFilm::GetImage: (H, W, 3 + nbuckets), channels film.channel_names()."""
@@ -113,6 +133,10 @@ class FilmIntegrator:
         SpectralFilm (film.cpp:955-1028): EXR only, R G B + S0.<lambda>nm channels and the
         spectral layout strings."""
         f = self.scene.film
+        # ImageMetadata::pixelBounds / fullResolution (film.cpp:568-574): the EXR's dataWindow is
+        # the bounds, its displayWindow the whole film
+        x0, y0, x1, y1 = getattr(f, "pixel_bounds", (0, 0, f.width, f.height))
+        win = dict(data_window=(x0, y0, x1 - 1, y1 - 1), display_window=(0, 0, f.width - 1, f.height - 1))
         if getattr(f, "nbuckets", 0):
             if not str(path).lower().endswith(".exr"):
                 raise ValueError(f"{path}: EXR is the only output format supported by the SpectralFilm.")
@@ -121,7 +145,7 @@ class FilmIntegrator:
                 img = img.astype(np.float16).astype(np.float32)
             imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
                               samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
-                              mse=mse, strings={"spectralLayoutVersion": "1.0", "emissiveUnits": "W.m^-2.sr^-1"})
+                              mse=mse, strings={"spectralLayoutVersion": "1.0", "emissiveUnits": "W.m^-2.sr^-1"}, **win)
             return img
         if isinstance(f, GBufferFilm):
             if rgb_sum is None:
@@ -131,14 +155,14 @@ class FilmIntegrator:
                 img = img.astype(np.float16).astype(np.float32)
             imageio.write_exr(path, img, channels=f.channel_names(), half=fp16,
                               samples_per_pixel=spp if spp is not None else self.spp, render_time_seconds=render_time,
-                              mse=mse)
+                              mse=mse, **win)
             return img
         img = self.get_image(rgb_sum, w_sum, fp16)
         if str(path).lower().endswith(".pfm"):
             imageio.write_pfm(path, img)
         else:
             imageio.write_exr(path, img, half=fp16, samples_per_pixel=spp if spp is not None else self.spp,
-                              render_time_seconds=render_time, mse=mse)
+                              render_time_seconds=render_time, mse=mse, **win)
         return img
 
     def close(self):
@@ -195,8 +219,20 @@ class VolPathIntegrator(FilmIntegrator):
                     name=name)
 
     @classmethod
-    def create(cls, name, params, scene, device=0, maxdepth_override=None, **kw):
-        """Integrator::Create-style factory from a pbrt ParameterDictionary-like dict."""
+    def create(cls, name, params, scene, device=0, maxdepth_override=None, pixelbounds_override=None,
+               cropwindow_override=None, pixel=None, **kw):
+        """Integrator::Create-style factory from a pbrt ParameterDictionary-like dict.
+
+        pixelbounds_override (x0, x1, y0, y1) and cropwindow_override (x0, x1, y0, y1 fractions)
+        are pbrt's --pixelbounds and --cropwindow, which reach the film with pbrt's precedence
+        (scene.resolve_pixel_bounds); pixel=(x, y) is --pixel, the one-pixel bounds. They set the
+        scene film's pixel_bounds before the film is made on the device."""
+        if pixel is not None:
+            if pixelbounds_override is not None:
+                raise ValueError("pixel and pixelbounds_override are one option (--pixel sets the pixel bounds)")
+            pixelbounds_override = (int(pixel[0]), int(pixel[0]) + 1, int(pixel[1]), int(pixel[1]) + 1)
+        if pixelbounds_override is not None or cropwindow_override is not None:
+            scene.film.apply_overrides(pixelbounds_override, cropwindow_override)
         return cls(scene, device=device, **cls.create_params(name, params, maxdepth_override), **kw)
 
     def tune_majorant(self, candidates=(1, 2, 4, 8, 16), probe=(0, 64)):
@@ -215,10 +251,12 @@ class VolPathIntegrator(FilmIntegrator):
         """A pixel order for avr_set_pixel_order (the north star's "sorted ray
         packets"): pixels sorted by the majorant cell where the ray through the pixel centre
         enters the medium's bounds (pixels whose ray misses them last), scanline order within a
-        cell. Host arithmetic in f64 (an ordering heuristic, not a sample)."""
+        cell. Host arithmetic in f64 (an ordering heuristic, not a sample). The pixels are those of
+        the film's pixel bounds, numbered row-major within them."""
         sc = self.scene
         f = sc.film
-        y, x = np.mgrid[0:f.height, 0:f.width]
+        bx0, by0, bx1, by1 = f.pixel_bounds
+        y, x = np.mgrid[by0:by1, bx0:bx1]
         pr = np.stack([x.ravel() + 0.5, y.ravel() + 0.5, np.zeros(x.size), np.ones(x.size)], 1)
         pc = pr @ np.asarray(sc.camera_from_raster, np.float64).T
         pc = pc[:, :3] / pc[:, 3:4]
@@ -256,8 +294,8 @@ class VolPathIntegrator(FilmIntegrator):
         f = self.scene.film
         if mse_reference is not None:
             ref = np.asarray(mse_reference, np.float32)
-            if ref.shape != (f.height, f.width, 3):
-                raise ValueError(f"reference image must be {(f.height, f.width, 3)}")
+            if ref.shape != (f.crop_height, f.crop_width, 3):
+                raise ValueError(f"reference image must be {(f.crop_height, f.crop_width, 3)}")
             self.ctx.film_set_reference(ref, f.output_from_sensor, fp16=True)
         self.ctx.film_clear()
         log = []
@@ -299,6 +337,51 @@ class VolPathIntegrator(FilmIntegrator):
             self.ctx.render(lo, hi, self.seed, self.maxdepth)
         f = self.scene.film
         nb = int(getattr(f, "nbuckets", 0))
-        buf = torch.empty(film_buffer_size(f.width * f.height, nb), dtype=torch.float64, device=f"cuda:{self.device}")
+        buf = torch.empty(film_buffer_size(f.npix, nb), dtype=torch.float64, device=f"cuda:{self.device}")
         self.ctx.film_export_device(buf.data_ptr())
-        return reduce_film(buf, f.width * f.height, nb, rank, group)
+        return reduce_film(buf, f.npix, nb, rank, group)
+
+    def render_tiles(self, tile, ranges=None):
+        """Render the film's pixel bounds tile by tile ((tw, th) pixels, tile_bounds) through the
+        pixel bounds and assemble the fp64 sums of all of them on the host: the way to render a
+        film whose per-sample buffers (pixels x pass samples) do not fit the device. ranges: the
+        (spp_begin, spp_end) calls issued per tile, default one call of all spp; with the ranges
+        of an untiled render the sums are bit-identical to its. Returns (rgb_sum, w_sum) shaped
+        like film_sums() of the bounds; the bounds are restored afterwards (the device film is
+        then empty)."""
+        f = self.scene.film
+        whole = tuple(f.pixel_bounds)
+        x0, y0, x1, y1 = whole
+        ranges = [(0, self.spp)] if ranges is None else [(int(a), int(b)) for a, b in ranges]
+        rgb = np.zeros((y1 - y0, x1 - x0, 3), np.float64)
+        w = np.zeros((y1 - y0, x1 - x0), np.float64)
+        try:
+            for tb in tile_bounds(whole, tile):
+                self.set_pixel_bounds(tb)
+                for a, b in ranges:
+                    self._render_range(a, b)
+                trgb, tw = self.film_sums()
+                ys, xs = slice(tb[1] - y0, tb[3] - y0), slice(tb[0] - x0, tb[2] - x0)
+                rgb[ys, xs] = trgb.reshape(tb[3] - tb[1], tb[2] - tb[0], 3)
+                w[ys, xs] = tw.reshape(tb[3] - tb[1], tb[2] - tb[0])
+        finally:
+            self.set_pixel_bounds(whole)
+        return rgb.reshape(-1), w.reshape(-1)
+
+    def replay_sample(self, px, py, sample_index):
+        """One pixel sample again, pbrt's --debugstart: renders sample `sample_index` of pixel
+        (px, py) alone through one-pixel bounds and returns its record (L, lambda, pdf, weight):
+        three (4,) float32 arrays and the filter weight, bit for bit what a render of the whole
+        film records for it. The bounds are restored afterwards (the device film is then empty)."""
+        f = self.scene.film
+        if not (0 <= int(px) < f.width and 0 <= int(py) < f.height):
+            raise ValueError(f"pixel {(px, py)} outside the {f.width} x {f.height} film")
+        whole = tuple(f.pixel_bounds)
+        try:
+            self.set_pixel_bounds((int(px), int(py), int(px) + 1, int(py) + 1))
+            self._render_range(int(sample_index), int(sample_index) + 1)
+            _, _, L, lam, pdf = self.ctx.last_pass_samples(1, 1)
+            wt = self.ctx.last_pass_weights(1, 1)
+        finally:
+            self.set_pixel_bounds(whole)
+        return L[0].copy(), lam[0].copy(), pdf[0].copy(), np.float32(wt[0])

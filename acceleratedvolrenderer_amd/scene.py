@@ -13,6 +13,7 @@ boundary (no BSDF; rays cross it without scattering, interaction.cpp:91-97).
 See DESIGN.md "Scene model" for why that is exact for VolPath's sampling.
 """
 import math
+import warnings
 
 import numpy as np
 
@@ -461,14 +462,89 @@ class ZSobolSampler:
         self.seed = seed
 
 
+def crop_to_bounds(xres, yres, crop):
+    """FilmBaseParameters' crop window -> pixel bounds (film.cpp:134-137, 162-165):
+    ceil(float32(res) * float32(c)) per edge, the product rounded to float32 as pbrt's Float
+    arithmetic does (1280 x 0.1 is 128 there; the f64 product is just above 128 and would give
+    129). crop = (x0, x1, y0, y1) within [0, 1]. Returns (x0, y0, x1, y1)."""
+    f = lambda res, c: int(math.ceil(np.float32(np.float32(res) * np.float32(c))))
+    return (f(xres, crop[0]), f(yres, crop[2]), f(xres, crop[1]), f(yres, crop[3]))
+
+
+def _intersect_bounds(b, xres, yres, what):
+    """Intersect(newBounds, image) with pbrt's warning when it clamps (film.cpp:101-104, 115-118)."""
+    x0, x1, y0, y1 = (int(v) for v in b)
+    c = (max(x0, 0), max(y0, 0), min(x1, xres), min(y1, yres))
+    if c != (x0, y0, x1, y1):
+        warnings.warn(f"Supplied {what} extend beyond image resolution. Clamping.", stacklevel=4)
+    return c
+
+
+def resolve_pixel_bounds(xres, yres, cropwindow=None, pixelbounds=None, cropwindow_override=None,
+                         pixelbounds_override=None):
+    """Film::pixelBounds from its four sources, FilmBaseParameters' constructor (film.cpp:97-172):
+    the film's "pixelbounds" (x0 x1 y0 y1, intersected with the image, a warning when clamped)
+    and "cropwindow" (x0 x1 y0 y1 fractions, each pair sorted and clamped to [0, 1]) and the
+    command line's --pixelbounds and --cropwindow (the *_override arguments, same orders). The
+    film's cropwindow wins over the film's pixelbounds, a pixel-bounds override over the film's
+    cropwindow, a crop-window override over everything. Returns (x0, y0, x1, y1); empty bounds
+    raise (ErrorExit "Degenerate pixel bounds", film.cpp:171)."""
+    xres, yres = int(xres), int(yres)
+    for name, v in (("pixelbounds", pixelbounds), ("cropwindow", cropwindow), ("pixelbounds", pixelbounds_override),
+                    ("cropwindow", cropwindow_override)):
+        if v is not None and len(v) != 4:
+            raise ValueError(f'{len(v)} values supplied for "{name}". Expected 4.')
+    b = (0, 0, xres, yres)
+    if pixelbounds_override is not None:
+        b = _intersect_bounds(pixelbounds_override, xres, yres, "pixel bounds")
+        if pixelbounds is not None:
+            warnings.warn("Both pixel bounds on the command line and in the film were specified. Using the command line's.",
+                          stacklevel=3)
+    elif pixelbounds is not None:
+        b = _intersect_bounds(pixelbounds, xres, yres, "pixel bounds")
+    if cropwindow_override is not None:
+        c = [float(v) for v in cropwindow_override]
+        k = [min(max(v, 0.0), 1.0) for v in c]
+        if k != c:
+            warnings.warn(f'Film crop window {c} is not in [0,1] range; did you mean to use "pixelbounds"? '
+                          "Clamping to valid range.", stacklevel=3)
+        b = crop_to_bounds(xres, yres, k)
+        if cropwindow is not None:
+            warnings.warn("Crop window supplied on command line will override crop window specified with Film.",
+                          stacklevel=3)
+        if pixelbounds_override is not None or pixelbounds is not None:
+            warnings.warn("Both pixel bounds and crop window were specified. Using the crop window.", stacklevel=3)
+    elif cropwindow is not None:
+        if pixelbounds_override is not None:
+            warnings.warn('Ignoring "cropwindow" since pixel bounds were specified on the command line.', stacklevel=3)
+        else:
+            if pixelbounds is not None:
+                warnings.warn("Both pixel bounds and crop window were specified. Using the crop window.", stacklevel=3)
+            c = [np.float32(v) for v in cropwindow]
+            k = np.clip([min(c[0], c[1]), max(c[0], c[1]), min(c[2], c[3]), max(c[2], c[3])], np.float32(0),
+                        np.float32(1))
+            b = crop_to_bounds(xres, yres, k)
+    if b[0] >= b[2] or b[1] >= b[3]:
+        raise ValueError(f"Degenerate pixel bounds provided to film: [ {b[0]}, {b[1]} ] - [ {b[2]}, {b[3]} ].")
+    return tuple(int(v) for v in b)
+
+
 class RGBFilm:
     """RGBFilm (film.h:232-316) with the cie1931 PixelSensor (film.cpp:212-250) and a box
-    (default here) or Gaussian pixel filter."""
+    (default here) or Gaussian pixel filter.
+
+    width and height are the full resolution (the sampler's and the camera's domain);
+    pixel_bounds = (x0, y0, x1, y1), from "cropwindow" / "pixelbounds" (resolve_pixel_bounds), are
+    the pixels rendered and stored: sums, images and per-sample records are crop_height x
+    crop_width, row-major within the bounds."""
 
     def __init__(self, xresolution=1280, yresolution=720, filter_radius=(0.5, 0.5), iso=100.0, exposure_time=1.0,
-                 maxcomponentvalue=math.inf, filter=None):
+                 maxcomponentvalue=math.inf, filter=None, cropwindow=None, pixelbounds=None):
         self.width = int(xresolution)
         self.height = int(yresolution)
+        self.cropwindow = None if cropwindow is None else tuple(float(v) for v in cropwindow)
+        self.pixelbounds = None if pixelbounds is None else tuple(int(v) for v in pixelbounds)
+        self.pixel_bounds = resolve_pixel_bounds(self.width, self.height, self.cropwindow, self.pixelbounds)
         self.filter = filter if filter is not None else BoxFilter(filter_radius)
         self.filter_radius = self.filter.radius
         self.imaging_ratio = np.float32(np.float32(exposure_time) * np.float32(iso) / np.float32(100))
@@ -476,6 +552,31 @@ class RGBFilm:
         self.sensor = spectra.sensor_cie1931()
         # outputRGBFromSensorRGB = colorSpace->RGBFromXYZ * XYZFromSensorRGB (film.cpp:496), cie1931: I
         self.output_from_sensor = spectra.TABLES["srgb_rgb_from_xyz"].astype(np.float32)
+
+    @property
+    def crop_width(self):
+        return self.pixel_bounds[2] - self.pixel_bounds[0]
+
+    @property
+    def crop_height(self):
+        return self.pixel_bounds[3] - self.pixel_bounds[1]
+
+    @property
+    def npix(self):
+        """Pixels of the bounds: what the film stores."""
+        return self.crop_width * self.crop_height
+
+    def apply_overrides(self, pixelbounds_override=None, cropwindow_override=None):
+        """pbrt's --pixelbounds / --cropwindow: pixel_bounds resolved again from the film's own
+        parameters and the overrides (None, None returns to the film's own). Returns the bounds."""
+        self.pixel_bounds = resolve_pixel_bounds(self.width, self.height, self.cropwindow, self.pixelbounds,
+                                                 cropwindow_override, pixelbounds_override)
+        return self.pixel_bounds
+
+    def crop_slice(self):
+        """The bounds as an index into a (height, width, ...) array of the whole film."""
+        x0, y0, x1, y1 = self.pixel_bounds
+        return (slice(y0, y1), slice(x0, x1))
 
 
 class SpectralFilm(RGBFilm):
@@ -521,6 +622,11 @@ class GBufferFilm(RGBFilm):
         return list(self.CHANNELS)
 
 
+def _crop_shape(film):
+    """(rows, columns) of what a film stores: its pixel bounds (a film object without them: all of it)."""
+    return getattr(film, "crop_height", film.height), getattr(film, "crop_width", film.width)
+
+
 def clamp_fp16(rgb):
     """The fp16 clamp of RGBFilm::GetImage and GBufferFilm::GetImage (film.cpp:543-551, 761-769):
     channels above 65504 become 65504 where std::max({r, g, b}) > 65504. The initializer-list
@@ -535,11 +641,11 @@ def clamp_fp16(rgb):
 
 def gbuffer_image(film, rgb_sum, w_sum, fp16=True):
     """GBufferFilm::GetImage (film.cpp:688-800), no splats and no visible surfaces:
-    (H, W, 25) float32 in GBufferFilm.CHANNELS order."""
+    (H, W, 25) float32 (of the pixel bounds) in GBufferFilm.CHANNELS order."""
     rgb = film_rgb(film, rgb_sum, w_sum)
     if fp16:
         rgb = clamp_fp16(rgb)
-    out = np.zeros((film.height, film.width, len(GBufferFilm.CHANNELS)), np.float32)
+    out = np.zeros((*_crop_shape(film), len(GBufferFilm.CHANNELS)), np.float32)
     out[:, :, :3] = rgb
     return out
 
@@ -549,8 +655,8 @@ def spectral_image(film, rgb_sum, w_sum, bucket_sums, weight_sums, fp16=True):
     rgb = film_rgb(film, rgb_sum, w_sum)
     if fp16:
         rgb = np.minimum(rgb, np.float32(65504))
-    bs = np.asarray(bucket_sums, np.float64).reshape(film.height, film.width, film.nbuckets)
-    bw = np.asarray(weight_sums, np.float64).reshape(film.height, film.width, film.nbuckets)
+    bs = np.asarray(bucket_sums, np.float64).reshape(*_crop_shape(film), film.nbuckets)
+    bw = np.asarray(weight_sums, np.float64).reshape(*_crop_shape(film), film.nbuckets)
     with np.errstate(divide="ignore", invalid="ignore"):
         c = np.where(bw > 0, (bs / np.where(bw > 0, bw, 1)).astype(np.float32), np.float32(0))
     if fp16:
@@ -660,7 +766,8 @@ class Scene:
 
 
 def film_rgb(film, rgb_sum, w_sum):
-    """RGBFilm::GetPixelRGB (film.h:258-274) in float32, no splats: returns (H, W, 3)."""
+    """RGBFilm::GetPixelRGB (film.h:258-274) in float32, no splats: returns (H, W, 3) of the
+    film's pixel bounds."""
     rgb = np.asarray(rgb_sum, np.float64).reshape(-1, 3).astype(np.float32)
     w = np.asarray(w_sum, np.float64).reshape(-1).astype(np.float32)
     nz = w != 0
@@ -670,4 +777,4 @@ def film_rgb(film, rgb_sum, w_sum):
     for r in range(3):
         out[:, r] = ((m[r, 0] * rgb[:, 0] + m[r, 1] * rgb[:, 1]).astype(np.float32) + m[r, 2] * rgb[:, 2]).astype(
             np.float32)
-    return out.reshape(film.height, film.width, 3)
+    return out.reshape(*_crop_shape(film), 3)

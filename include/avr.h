@@ -361,6 +361,22 @@ int avr_camera(avr_context *ctx, int type, const float camera_from_raster[16], c
 int avr_film(avr_context *ctx, int width, int height, const float filter_radius[2], const float *sensor_rgb,
              float imaging_ratio, float max_component_value);
 int avr_film_clear(avr_context *ctx);
+/* Film::pixelBounds (film.h:67; "cropwindow" / "pixelbounds", film.cpp:97-172): after avr_film,
+ * whose width and height stay the full resolution, render only the pixels [x0, x1) x [y0, y1).
+ * Samplers, pixel filter and camera keep taking the absolute pixel and the full resolution
+ * (ZSobolSampler, samplers.h:228-238; ImageTileIntegrator::Render, cpu/integrators.cpp:109,170),
+ * so the bounds' pixels receive, sample for sample, what they receive in a render of the whole
+ * film. Everything this header sizes by "W*H" is from then on sized by the bounds' pixel count
+ * (x1-x0)*(y1-y0), row-major within the bounds: the film sums and every readback of them, the
+ * per-sample records of the avr_last_pass_* and graph readbacks, images, references and metrics,
+ * the export buffer and the pixel order. The call reallocates and zeroes the sums (a
+ * SpectralFilm's buckets too, in whichever order avr_film_spectral and this call come) and drops
+ * the pixel order, the analysis sums, the metric reference and whatever was built ahead for the
+ * old bounds. avr_film resets the bounds to the whole film. Bounds that are empty or reach
+ * outside the film: AVR_ERR_ARG (clamping is the caller's, as it is Film::Create's in pbrt);
+ * before avr_film: AVR_ERR_STATE. */
+int avr_film_pixel_bounds(avr_context *ctx, int x0, int y0, int x1, int y1);
+int avr_film_get_bounds(avr_context *ctx, int *x0, int *y0, int *x1, int *y1);
 /* Pixel filter for later renders (GetCameraSample, samplers.h:797-815): type 0 BoxFilter
  * (filters.h:48-77, radius), 1 GaussianFilter(radius, sigma) (filters.h:80-118; sampled with
  * FilterSampler's tabulated distribution, filters.cpp:133-147, weight f/pdf; radius <= 4).

@@ -193,6 +193,10 @@ class Mi355xVolPathIntegrator : public Integrator {
         CheckAvr(avr_film(ctx, res.x, res.y, radius, rgbBar.data(), sensor->ImagingRatio(),
                           film->MaxComponentValue()),
                  "avr_film");
+        // Film::PixelBounds() ("cropwindow" / "pixelbounds", already clamped by pbrt): the device
+        // film renders and stores those pixels only, sampled as in the full-resolution render
+        const Bounds2i pb = film->PixelBounds();
+        CheckAvr(avr_film_pixel_bounds(ctx, pb.pMin.x, pb.pMin.y, pb.pMax.x, pb.pMax.y), "avr_film_pixel_bounds");
         if (GaussianFilter *gf = filter.CastOrNullptr<GaussianFilter>())
             CheckAvr(avr_set_filter(ctx, 1, radius, gf->Sigma()), "avr_set_filter");
         else if (!filter.Is<BoxFilter>())
@@ -209,7 +213,7 @@ class Mi355xVolPathIntegrator : public Integrator {
 
         // render every sample index, then merge the fp64 sums into pbrt's film
         CheckAvr(avr_render(ctx, 0, spp, Options->seed, maxDepth), "avr_render");
-        const Bounds2i pb = film->PixelBounds();
+        // (the sums are bounds-sized, row-major within the bounds: Bounds2i's iteration order)
         std::vector<double> rgb(3 * (size_t)pb.Area()), w((size_t)pb.Area());
         CheckAvr(avr_film_read(ctx, rgb.data(), w.data()), "avr_film_read");
         size_t i = 0;
