@@ -147,6 +147,8 @@ SIGNATURES = {
     "avr_lights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_float_p, c_float_p, c_float_p,
                                   ctypes.c_float]),
     "avr_camera": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p]),
+    "avr_camera_lens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float]),
+    "avr_camera_spherical": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p]),
     "avr_light_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p,
                                        c_float_p, c_float_p]),
     "avr_flip": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
@@ -466,8 +468,33 @@ class Context:
             if t is not None and hasattr(t, "data_ptr") and t.device.index != self.device:
                 raise ValueError(f"grid tensor on {t.device}, but the context runs on cuda:{self.device}")
 
+    def set_camera(self, scene):
+        """Upload the scene's camera alone: avr_camera and its lens (a radius of 0 is the pinhole), or
+        avr_camera_spherical. A Scene's render space is world space moved to the camera's position,
+        and medium, lights and interface of the scene set last were uploaded in it: `scene` must have
+        the same render_from_world (a camera at the same position; pose, kind and lens may differ),
+        else ValueError — use set_scene for a camera that moved."""
+        rfw = getattr(self, "_render_from_world", None)
+        if rfw is not None and not np.array_equal(rfw, np.asarray(scene.render_from_world, np.float64)):
+            raise ValueError("set_camera: the camera's position differs from the scene's set last (its render space "
+                             "would disagree with the uploaded medium and lights): use set_scene")
+        cam = scene.camera
+        f32 = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))
+        if int(cam.type_id) == 2:
+            _check(self.lib.avr_camera_spherical(self.h, int(cam.mapping_id), _fp(f32(scene.render_from_camera))))
+            return
+        _check(self.lib.avr_camera(self.h, int(cam.type_id), _fp(f32(scene.camera_from_raster)),
+                                   _fp(f32(scene.render_from_camera))))
+        if float(getattr(cam, "lensradius", 0.0)) > 0:
+            self.set_camera_lens(cam.lensradius, cam.focaldistance)
+
+    def set_camera_lens(self, lensradius, focaldistance=1e6):
+        """avr_camera_lens: the thin lens of the camera set last (radius 0: the pinhole)."""
+        _check(self.lib.avr_camera_lens(self.h, float(lensradius), float(focaldistance)))
+
     def set_scene(self, scene):
         med = scene.medium
+        self._render_from_world = np.array(scene.render_from_world, np.float64)
         self._check_device([getattr(med, "device_density", None)] +
                            ([med.rgb_sigma_a, med.rgb_sigma_s, med.rgb_Le] if getattr(med, "type_id", 0) == 4 else []))
         mres = np.asarray(med.majorant_res, np.int32)
@@ -542,8 +569,7 @@ class Context:
                         f32(scene.light_lfr[i])]
                 self._keep += arrs
                 _check(self.lib.avr_light_image(self.h, i, int(light.res), *[_fp(a) for a in arrs]))
-        _check(self.lib.avr_camera(self.h, int(scene.camera.type_id), _fp(f32(scene.camera_from_raster)),
-                                   _fp(f32(scene.render_from_camera))))
+        self.set_camera(scene)
         film = scene.film
         _check(self.lib.avr_film(self.h, film.width, film.height, _fp(f32(film.filter_radius)), _fp(f32(film.sensor)),
                                  float(film.imaging_ratio), float(film.max_component_value)))

@@ -1710,6 +1710,36 @@ int avr_camera(avr_context *c, int type, const float cfr[16], const float rfc[16
     c->cam.type = type;
     for (int i = 0; i < 16; ++i) c->cam.raster[i] = cfr[i];
     copy_xf(c->cam.render_from_camera, rfc);
+    c->cam.lens_radius = 0.f;   // the pinhole (avr_camera_lens sets a lens)
+    c->cam.focal_distance = 1e6f;
+    c->cam.mapping = 0;
+    c->has_camera = true;
+    return AVR_OK;
+}
+
+int avr_camera_lens(avr_context *c, float lens_radius, float focal_distance) {
+    if (!c) return fail(AVR_ERR_ARG, "null context");
+    if (!(lens_radius >= 0.f) || !std::isfinite(lens_radius)) return fail(AVR_ERR_ARG, "lens radius must be finite and >= 0");
+    if (!(focal_distance > 0.f)) return fail(AVR_ERR_ARG, "focal distance must be > 0");
+    if (!c->has_camera) return fail(AVR_ERR_STATE, "the lens needs a camera (avr_camera first)");
+    if (c->cam.type == avr::cam::kSpherical) return fail(AVR_ERR_ARG, "a spherical camera has no lens");
+    AVR_QUIESCE(c);   // camera records made ahead for the old lens are dropped
+    c->cam.lens_radius = lens_radius;
+    c->cam.focal_distance = focal_distance;
+    return AVR_OK;
+}
+
+int avr_camera_spherical(avr_context *c, int mapping, const float rfc[16]) {
+    if (!c || (mapping != avr::cam::kEqualArea && mapping != avr::cam::kEquiRectangular) || !rfc)
+        return fail(AVR_ERR_ARG, "bad spherical camera (mapping: 0 equalarea, 1 equirectangular)");
+    if (!affine(rfc)) return fail(AVR_ERR_ARG, "render_from_camera must be affine");
+    AVR_QUIESCE(c);   // camera records made ahead for the old camera are dropped
+    c->cam.type = avr::cam::kSpherical;
+    for (int i = 0; i < 16; ++i) c->cam.raster[i] = (i % 5 == 0) ? 1.f : 0.f;   // unused: pFilm maps directly
+    copy_xf(c->cam.render_from_camera, rfc);
+    c->cam.lens_radius = 0.f;
+    c->cam.focal_distance = 1e6f;
+    c->cam.mapping = mapping;
     c->has_camera = true;
     return AVR_OK;
 }

@@ -21,6 +21,7 @@
 #include "avr_sampling.h"
 #include "avr_vdb.h"
 #include "avr_envmap.h"
+#include "avr_camera.h"
 #include "avr_flip.h"
 #include "avr_boundary.h"
 
@@ -228,10 +229,31 @@ __device__ __forceinline__ float light_pmf_staged(const DevLights &ls, const Lds
 }
 
 struct DevCamera {
-    int type;                         // 0 orthographic, 1 perspective
+    int type;                         // 0 orthographic, 1 perspective, 2 spherical (avr_camera.h)
     float raster[16];                 // cameraFromRaster (full 4x4; perspective is projective)
     Xf render_from_camera;
+    // Beyond the pinholes (avr_camera_lens, avr_camera_spherical): the projective cameras' thin
+    // lens (lens_radius > 0) and the spherical camera's mapping. The host launches the camera
+    // kernels' kCam = 1 instantiations when camera_general() holds, the pinholes' own otherwise.
+    float lens_radius, focal_distance;
+    int mapping;                      // spherical: 0 equal-area, 1 equirectangular
+    int pad_;
 };
+inline bool camera_general(const DevCamera &c) { return c.type == cam::kSpherical || c.lens_radius > 0; }
+// The camera-space ray of the general cameras from the pinhole's ray, pFilm and the lens draw
+// (l0, l1): Orthographic/PerspectiveCamera::GenerateRay with a lens (cameras.cpp:284-306,
+// 404-427), SphericalCamera::GenerateRay (cameras.cpp:610-630); resx, resy: the full resolution
+__device__ __forceinline__ Ray camera_general_ray(const DevCamera &c, Ray pin, float pFilmX, float pFilmY, int resx,
+                                                  int resy, float l0, float l1) {
+    float o[3] = {pin.o.x, pin.o.y, pin.o.z}, d[3] = {pin.d.x, pin.d.y, pin.d.z};
+    if (c.type == cam::kSpherical) {
+        o[0] = o[1] = o[2] = 0.f;
+        cam::spherical_dir(c.mapping, pFilmX, pFilmY, resx, resy, d);
+    } else if (c.lens_radius > 0) {
+        cam::thin_lens(c.lens_radius, c.focal_distance, l0, l1, o, d);
+    }
+    return {{o[0], o[1], o[2]}, {d[0], d[1], d[2]}};
+}
 
 struct DevFilm {
     int width, height;                // the full resolution: the sampler's and the camera's domain
@@ -962,6 +984,17 @@ __device__ __forceinline__ void camera_sample(const Params &P, Smp &smp, int px,
     float l0, l1;
     smp.get2d(P, &l0, &l1);       // lens
 }
+// the same, handing out the lens draw (the general cameras, kCam = 1)
+template <typename Smp>
+__device__ __forceinline__ void camera_sample_lens(const Params &P, Smp &smp, int px, int py, float *pFilmX,
+                                                   float *pFilmY, float *weight, float *l0, float *l1,
+                                                   const smp::FilterTables *ft = nullptr) {
+    float fu0, fu1;
+    smp.get2d(P, &fu0, &fu1);
+    camera_filter(P, px, py, fu0, fu1, pFilmX, pFilmY, weight, ft);
+    smp.get1d(P);                 // time
+    smp.get2d(P, l0, l1);         // lens
+}
 
 // Cooperative ZSobol draws in k_paths' service rounds. Each lane with `req` needs N draws at
 // its dimension + off[j] (a 2D draw where two[j]); the wave's N * popc(req) draws are spread
@@ -1300,6 +1333,10 @@ __device__ __forceinline__ void zsobol_draw_quad(smp::ZSobol &z, const smp::ZSob
 // 64 B per new path instead of running this per service round with most lanes idle, and
 // k_film reads the wavelengths, pdfs and filter weight instead of re-deriving them.
 // kSmp: 0 IndependentSampler, 2 / 3 ZSobolSampler with 32- / 64-bit indices.
+// kCam: 0 the pinholes; 1 the general cameras (camera_general: a thin lens or the spherical
+// camera, avr_camera.h), which also draw the lens sample at dimensions 4 and 5 — in each of the
+// three ZSobol index paths, so the draws after it stay at dimensions 6..9. The pinholes'
+// instantiations hold none of it.
 // The camera stage's ZSobol draws read Hash(dimension, seed) and its wavelength math the
 // canonical tables from LDS. The wavelength pdfs are evaluated by k_film from the wavelengths
 // (the same canonical function on the same floats, so the same bits) instead of being carried
@@ -1308,7 +1345,7 @@ __device__ __forceinline__ void zsobol_draw_quad(smp::ZSobol &z, const smp::ZSob
 #ifndef AVR_CAM_WAVES
 #define AVR_CAM_WAVES 1   // minimum waves per SIMD asked of k_paths_camera (1: the compiler's choice)
 #endif
-template <int kSmp, bool kFast>
+template <int kSmp, bool kFast, int kCam = 0>
 __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) {
     const Params &P = Pk;
     __shared__ float s_filt[kFiltLds];
@@ -1366,6 +1403,7 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
         // 6..9) loaded up front by three 16-B loads of the pixel's row, so the draws wait for
         // one memory round trip instead of six in sequence
         [[maybe_unused]] uint64_t pe0 = 0, pe1 = 0, pe6 = 0, pe7 = 0, pe8 = 0, pe9 = 0;
+        [[maybe_unused]] uint64_t pe4 = 0;   // kCam: the lens draw's entry (dimension 4)
         [[maybe_unused]] bool pe_ok = false;
         if constexpr (kSmp != 0) {
             if (quad && P.zs.ptab && P.zs.pdims >= 10) {
@@ -1378,6 +1416,8 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
                                                   : reinterpret_cast<const ulonglong2 *>(P.zs.ptab + (size_t)pmk * (size_t)P.zs.pdims);
                 const ulonglong2 r01 = row[0], r67 = row[P.zs.ctab ? 1 : 3], r89 = row[P.zs.ctab ? 2 : 4];
                 pe0 = r01.x; pe1 = r01.y; pe6 = r67.x; pe7 = r67.y; pe8 = r89.x; pe9 = r89.y;
+                // (the compact copy holds the pinholes' six entries only: dimension 4 from the row)
+                if constexpr (kCam != 0) pe4 = P.zs.ptab[(size_t)pmk * (size_t)P.zs.pdims + 4];
                 pe_ok = true;
             }
         }
@@ -1396,6 +1436,7 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
         // ZSobol quads whose pass varies at most two base-4 digits: the six draws as three pairs
         // of indices (zsobol_index_quad_pair), each pair one round of MixBits for the quad
         [[maybe_unused]] float pu[7] = {};   // ulam, fu0, fu1, h0, h1, u, ulight
+        [[maybe_unused]] float lens0 = 0.f, lens1 = 0.f;   // kCam: the lens draw (dimensions 4, 5)
         bool paired = false;
         if constexpr (kSmp != 0) {
             if (pe_ok && ((P.zs.plo + (P.zs.log2spp & 1) - 1) >> 1) - (P.zs.log2spp & 1) <= 2) {
@@ -1413,6 +1454,11 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
                 zsobol_finish<M>(i7, 8, P.zs, false, &pu[4], &dummy, dh);
                 zsobol_finish<M>(i8, 9, P.zs, false, &pu[5], &dummy, dh);
                 zsobol_finish<M>(i9, 10, P.zs, false, &pu[6], &dummy, dh);
+                if constexpr (kCam != 0) {   // the lens draw: one more pair round, both halves dimension 4
+                    M i4, i4b;
+                    zsobol_index_quad_pair<M>(m, P.zs, 4, pe4, 4, pe4, &i4, &i4b, s_zpt);
+                    zsobol_finish<M>(i4, 6, P.zs, true, &lens0, &lens1, dh);
+                }
                 smp.z.dimension = 10;
                 paired = true;
             }
@@ -1436,7 +1482,22 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
             } else {
                 camera_filter(P, px, py, fu0, fu1, &pFilmX, &pFilmY, &fweight, nullptr);
             }
-            if (!paired) smp.z.dimension += 3;   // time (1D) and lens (2D): drawn by pbrt, unused by pinholes
+            if constexpr (kCam != 0) {
+                if (!paired) {
+                    smp.z.dimension += 1;        // time (1D): drawn by pbrt, unused
+                    if (quad) zsobol_draw_quad<PathSampler<kSmp>::kW>(smp.z, P.zs, true, &lens0, &lens1, s_cdh, pe4, pe_ok);
+                    else smp.get2d(P, &lens0, &lens1);
+                }
+            } else {
+                if (!paired) smp.z.dimension += 3;   // time (1D) and lens (2D): drawn by pbrt, unused by pinholes
+            }
+        } else if constexpr (kCam != 0) {
+            if (ftab_lds) {
+                const smp::FilterTables ft = filter_lds_tables(P.film.gauss, s_filt);
+                camera_sample_lens(P, smp, px, py, &pFilmX, &pFilmY, &fweight, &lens0, &lens1, &ft);
+            } else {
+                camera_sample_lens(P, smp, px, py, &pFilmX, &pFilmY, &fweight, &lens0, &lens1, nullptr);
+            }
         } else {
             if (ftab_lds) {
                 const smp::FilterTables ft = filter_lds_tables(P.film.gauss, s_filt);
@@ -1453,6 +1514,8 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
         Ray ray;
         if (P.cam.type == 0) ray = {pCam, {0.f, 0.f, 1.f}};
         else ray = {{0.f, 0.f, 0.f}, normalize(pCam)};
+        if constexpr (kCam != 0)
+            ray = camera_general_ray(P.cam, ray, pFilmX, pFilmY, P.film.width, P.film.height, lens0, lens1);
         ray = xf_ray(P.cam.render_from_camera, ray, nullptr, /*forward=*/true);
         const V3 o = P.med.boundary ? interface_entry(P.med, ray.o, ray.d) : ray.o;
         // first medium segment: RNG from two sampler dims, u from a third (984-989)
@@ -1480,7 +1543,8 @@ __global__ void __launch_bounds__(256, AVR_CAM_WAVES) k_paths_camera(Params Pk) 
 // Camera rays — RayIntegrator::EvaluatePixelSample (cpu/integrators.cpp:235-268),
 // GetCameraSample (samplers.h:797-815), BoxFilter::Sample (filters.h:67-70),
 // Orthographic/PerspectiveCamera::GenerateRay (cameras.cpp:284-306, 404-427)
-template <bool kZSobol>
+// kCam: as k_paths_camera's (1: the general cameras; the lens draw is GetCameraSample's own)
+template <bool kZSobol, int kCam = 0>
 __global__ void __launch_bounds__(256) k_camera(Params P) {
     const int n = P.pass_pixels * P.pass_samples;
     for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
@@ -1495,7 +1559,9 @@ __global__ void __launch_bounds__(256) k_camera(Params P) {
         lam.pdf = {film_lambda_pdf(P.film, lam.l.v0), film_lambda_pdf(P.film, lam.l.v1),
                    film_lambda_pdf(P.film, lam.l.v2), film_lambda_pdf(P.film, lam.l.v3)};
         float pFilmX, pFilmY, fweight;
-        camera_sample(P, smp, px, py, &pFilmX, &pFilmY, &fweight);
+        [[maybe_unused]] float lens0 = 0.f, lens1 = 0.f;
+        if constexpr (kCam != 0) camera_sample_lens(P, smp, px, py, &pFilmX, &pFilmY, &fweight, &lens0, &lens1);
+        else camera_sample(P, smp, px, py, &pFilmX, &pFilmY, &fweight);
         if (P.film.filter_type != 0) P.ps.weight[id] = fweight;
         const float *r = P.cam.raster;
         float xp = r[0] * pFilmX + r[1] * pFilmY + r[2] * 0.f + r[3];
@@ -1507,6 +1573,8 @@ __global__ void __launch_bounds__(256) k_camera(Params P) {
         Ray ray;
         if (P.cam.type == 0) ray = {pCam, {0.f, 0.f, 1.f}};
         else ray = {{0.f, 0.f, 0.f}, normalize(pCam)};
+        if constexpr (kCam != 0)
+            ray = camera_general_ray(P.cam, ray, pFilmX, pFilmY, P.film.width, P.film.height, lens0, lens1);
         ray = xf_ray(P.cam.render_from_camera, ray, nullptr, /*forward=*/true);
         if (P.med.boundary) ray.o = interface_entry(P.med, ray.o, ray.d);
         P.ps.o[id] = to4(ray.o);

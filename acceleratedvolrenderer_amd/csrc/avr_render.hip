@@ -243,8 +243,13 @@ static PassKernel camera_stage_kernel(const avr_context *c, const avr::smp::ZSob
     static const PassKernel kcam[2][3] = {
         {avr::k_paths_camera<0, false>, avr::k_paths_camera<2, false>, avr::k_paths_camera<3, false>},
         {avr::k_paths_camera<0, true>, avr::k_paths_camera<2, true>, avr::k_paths_camera<3, true>}};
+    // the general cameras (a thin lens, the spherical camera): their own instantiations, so that the
+    // pinholes' hold none of it
+    static const PassKernel kgen[2][3] = {
+        {avr::k_paths_camera<0, false, 1>, avr::k_paths_camera<2, false, 1>, avr::k_paths_camera<3, false, 1>},
+        {avr::k_paths_camera<0, true, 1>, avr::k_paths_camera<2, true, 1>, avr::k_paths_camera<3, true, 1>}};
     const int sv = avr::kp::sampler_index(avr::kp::sampler_arg(c->sampler_kind, avr::smp::zsobol_wide(zs)));
-    return kcam[c->render_mode ? 1 : 0][sv];
+    return (avr::camera_general(c->cam) ? kgen : kcam)[c->render_mode ? 1 : 0][sv];
 }
 
 // k_film over the pass's pixels, timed into ms_film from event `from` (-1: from here). fast: the
@@ -267,8 +272,10 @@ static int launch_film(avr_context *c, const avr::Params &p, bool fast, int from
 static int launch_camera(avr_context *c, const avr::Params &p, int *end = nullptr) {
     const long long n0 = (long long)p.pass_pixels * p.pass_samples;
     EV_MARK(c0);
-    if (c->sampler_kind) hipLaunchKernelGGL(avr::k_camera<true>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL(avr::k_camera<false>, dim3(blocks_for(n0)), dim3(256), 0, c->stream, p);
+    static const PassKernel kcam[2][2] = {{avr::k_camera<false>, avr::k_camera<true>},
+                                          {avr::k_camera<false, 1>, avr::k_camera<true, 1>}};
+    hipLaunchKernelGGL(kcam[avr::camera_general(c->cam) ? 1 : 0][c->sampler_kind ? 1 : 0], dim3(blocks_for(n0)), dim3(256),
+                       0, c->stream, p);
     HIP_TRY(hipGetLastError());
     EV_MARK(c1);
     c->timed.push_back({c0, c1, &avr_stats::ms_camera, false});

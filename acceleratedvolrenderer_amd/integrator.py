@@ -67,6 +67,73 @@ def tile_bounds(bounds, tile):
     return [(x, y, min(x + tw, x1), min(y + th, y1)) for y in range(y0, y1, th) for x in range(x0, x1, tw)]
 
 
+def spherical_directions(mapping, u, v):
+    """SphericalCamera's camera-space directions (cameras.cpp:610-630) at uv in float64: the
+    equirectangular map, or WrapEqualAreaSquare and EqualAreaSquareToSphere (util/math.cpp:292-315,
+    363-379), then y and z swapped."""
+    u, v = np.array(u, np.float64), np.array(v, np.float64)
+    if mapping == "equirectangular":
+        th, ph = np.pi * v, 2 * np.pi * u
+        d = np.stack([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)], 1)
+    else:
+        m = u < 0
+        u, v = np.where(m, -u, u), np.where(m, 1 - v, v)
+        m = ~m & (u > 1)
+        u, v = np.where(m, 2 - u, u), np.where(m, 1 - v, v)
+        m = v < 0
+        u, v = np.where(m, 1 - u, u), np.where(m, -v, v)
+        m = ~m & (v > 1)
+        u, v = np.where(m, 1 - u, u), np.where(m, 2 - v, v)
+        a, b = 2 * u - 1, 2 * v - 1
+        ap, bp = np.abs(a), np.abs(b)
+        sd = 1 - (ap + bp)
+        r = 1 - np.abs(sd)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            phi = np.where(r == 0, 1.0, (bp - ap) / r + 1) * np.pi / 4
+        z = np.copysign(1 - r * r, sd)
+        k = r * np.sqrt(np.maximum(2 - r * r, 0))
+        d = np.stack([np.copysign(np.cos(phi), a) * k, np.copysign(np.sin(phi), b) * k, z], 1)
+    return d[:, [0, 2, 1]]
+
+
+def entry_cell_order(sc):
+    """A pixel order for avr_set_pixel_order (the north star's "sorted ray
+    packets"): pixels sorted by the majorant cell where the ray through the pixel centre
+    enters the medium's bounds (pixels whose ray misses them last), scanline order within a
+    cell. Host arithmetic in f64 (an ordering heuristic, not a sample). The pixels are those of
+    the film's pixel bounds, numbered row-major within them. A thin lens' pixel-centre ray is the
+    one through the lens centre (the pinhole's); the spherical camera's is its direction."""
+    f = sc.film
+    bx0, by0, bx1, by1 = f.pixel_bounds
+    y, x = np.mgrid[by0:by1, bx0:bx1]
+    pr = np.stack([x.ravel() + 0.5, y.ravel() + 0.5, np.zeros(x.size), np.ones(x.size)], 1)
+    pc = pr @ np.asarray(sc.camera_from_raster, np.float64).T
+    pc = pc[:, :3] / pc[:, 3:4]
+    if int(sc.camera.type_id) == 2:    # spherical: uv = pFilm / the full resolution (cameras.cpp:610-630)
+        o_c, d_c = np.zeros_like(pc), spherical_directions(sc.camera.mapping, pr[:, 0] / f.width, pr[:, 1] / f.height)
+    elif int(sc.camera.type_id) == 0:  # orthographic: origin on the film plane, along +z
+        o_c, d_c = pc, np.tile([0.0, 0.0, 1.0], (len(pc), 1))
+    else:
+        o_c, d_c = np.zeros_like(pc), pc / np.linalg.norm(pc, axis=1, keepdims=True)
+    rfc = np.asarray(sc.render_from_camera, np.float64)
+    mfr = np.asarray(sc.medium_from_render, np.float64)
+    m = mfr @ rfc
+    o = o_c @ m[:3, :3].T + m[:3, 3]
+    d = d_c @ m[:3, :3].T
+    b = np.asarray(sc.medium.bounds, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t0 = (b[:3] - o) / d
+        t1 = (b[3:] - o) / d
+    tn = np.nanmax(np.minimum(t0, t1), axis=1)
+    tf = np.nanmin(np.maximum(t0, t1), axis=1)
+    hit = (tf >= np.maximum(tn, 0)) & np.isfinite(tn)
+    p = o + d * np.maximum(tn, 0)[:, None]
+    res = np.asarray(sc.medium.majorant_res, np.int64)
+    c = np.clip(((p - b[:3]) / (b[3:] - b[:3]) * res).astype(np.int64), 0, res - 1)
+    key = np.where(hit, (c[:, 2] * res[1] + c[:, 1]) * res[0] + c[:, 0], res.prod())
+    return np.argsort(key, kind="stable").astype(np.int32)
+
+
 class FilmIntegrator:
     """What every integrator here shares: a context (self.ctx) with the scene set, the sample
     loop's entry and the film's readback, image and file output. A subclass sets scene, spp,
@@ -248,39 +315,8 @@ class VolPathIntegrator(FilmIntegrator):
         return chosen, {c[0]: float(t) for c, t in zip(cands, ms)}
 
     def entry_cell_order(self):
-        """A pixel order for avr_set_pixel_order (the north star's "sorted ray
-        packets"): pixels sorted by the majorant cell where the ray through the pixel centre
-        enters the medium's bounds (pixels whose ray misses them last), scanline order within a
-        cell. Host arithmetic in f64 (an ordering heuristic, not a sample). The pixels are those of
-        the film's pixel bounds, numbered row-major within them."""
-        sc = self.scene
-        f = sc.film
-        bx0, by0, bx1, by1 = f.pixel_bounds
-        y, x = np.mgrid[by0:by1, bx0:bx1]
-        pr = np.stack([x.ravel() + 0.5, y.ravel() + 0.5, np.zeros(x.size), np.ones(x.size)], 1)
-        pc = pr @ np.asarray(sc.camera_from_raster, np.float64).T
-        pc = pc[:, :3] / pc[:, 3:4]
-        if int(sc.camera.type_id) == 0:    # orthographic: origin on the film plane, along +z
-            o_c, d_c = pc, np.tile([0.0, 0.0, 1.0], (len(pc), 1))
-        else:
-            o_c, d_c = np.zeros_like(pc), pc / np.linalg.norm(pc, axis=1, keepdims=True)
-        rfc = np.asarray(sc.render_from_camera, np.float64)
-        mfr = np.asarray(sc.medium_from_render, np.float64)
-        m = mfr @ rfc
-        o = o_c @ m[:3, :3].T + m[:3, 3]
-        d = d_c @ m[:3, :3].T
-        b = np.asarray(sc.medium.bounds, np.float64)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t0 = (b[:3] - o) / d
-            t1 = (b[3:] - o) / d
-        tn = np.nanmax(np.minimum(t0, t1), axis=1)
-        tf = np.nanmin(np.maximum(t0, t1), axis=1)
-        hit = (tf >= np.maximum(tn, 0)) & np.isfinite(tn)
-        p = o + d * np.maximum(tn, 0)[:, None]
-        res = np.asarray(sc.medium.majorant_res, np.int64)
-        c = np.clip(((p - b[:3]) / (b[3:] - b[:3]) * res).astype(np.int64), 0, res - 1)
-        key = np.where(hit, (c[:, 2] * res[1] + c[:, 1]) * res[0] + c[:, 0], res.prod())
-        return np.argsort(key, kind="stable").astype(np.int32)
+        """A pixel order for avr_set_pixel_order: entry_cell_order(scene) of this integrator's scene."""
+        return entry_cell_order(self.scene)
 
     def _render_range(self, spp_begin, spp_end):
         self.ctx.render(spp_begin, spp_end, self.seed, self.maxdepth)

@@ -369,11 +369,19 @@ class _ProjectiveCamera:
     type_id = -1
 
     def __init__(self, pos=(0, 0, 0), look=(0, 0, 1), up=(0, 1, 0), screenwindow=None, frameaspectratio=None,
-                 camera_from_world=None):
+                 camera_from_world=None, lensradius=0.0, focaldistance=1e6):
+        """lensradius, focaldistance: the thin lens of ProjectiveCamera (cameras.cpp:292-303,
+        413-424; Create's defaults, cameras.cpp:368, 494); radius 0 is the pinhole."""
         self.camera_from_world = (xf.look_at(pos, look, up) if camera_from_world is None
                                   else np.asarray(camera_from_world, np.float64))
         self.screenwindow = screenwindow
         self.frameaspectratio = frameaspectratio
+        self.lensradius = float(lensradius)
+        self.focaldistance = float(focaldistance)
+        if not (math.isfinite(self.lensradius) and self.lensradius >= 0):
+            raise ValueError("lensradius must be finite and >= 0")
+        if not self.focaldistance > 0:
+            raise ValueError("focaldistance must be > 0")
 
     def _screen(self, xres, yres):
         frame = self.frameaspectratio if self.frameaspectratio is not None else xres / yres
@@ -415,6 +423,29 @@ class PerspectiveCamera(_ProjectiveCamera):
 
     def screen_from_camera(self):
         return xf.perspective(self.fov, 1e-2, 1000.0)
+
+
+class SphericalCamera(_ProjectiveCamera):
+    """SphericalCamera (cameras.h:380-410, cameras.cpp:610-687): the whole sphere of directions
+    over the film's full resolution, mapping "equalarea" (the octahedral square of
+    ImageInfiniteLight) or "equirectangular". Like pbrt's Create it accepts lensradius,
+    focaldistance, screenwindow and frameaspectratio and ignores them."""
+    type_id = 2
+    MAPPINGS = {"equalarea": 0, "equirectangular": 1}
+
+    def __init__(self, mapping="equalarea", **kw):
+        if mapping not in self.MAPPINGS:
+            raise ValueError(f'unknown mapping for spherical camera {mapping!r} (must be "equalarea" or "equirectangular")')
+        kw.pop("lensradius", None)       # (void)lensradius; (void)focaldistance; cameras.cpp:671-672
+        kw.pop("focaldistance", None)
+        super().__init__(**kw)
+        self.mapping = mapping
+        self.mapping_id = self.MAPPINGS[mapping]
+        self.lensradius, self.focaldistance = 0.0, 1e6
+
+    def camera_from_raster(self, xres, yres):
+        """Unused by the spherical camera (pFilm / FullResolution maps to the sphere directly)."""
+        return np.eye(4)
 
 
 class BoxFilter:

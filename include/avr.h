@@ -355,6 +355,16 @@ int avr_light_sampler(avr_context *ctx, int kind);
  * camera_from_raster: full 4x4 (projective for perspective); render_from_camera: affine 4x4. */
 int avr_camera(avr_context *ctx, int type, const float camera_from_raster[16], const float render_from_camera[16]);
 
+/* The projective cameras' thin lens (lensradius / focaldistance, cameras.cpp:292-303, 413-424):
+ * call after avr_camera, which resets to the pinhole; radius 0 is the pinhole. The lens sample is
+ * GetCameraSample's (sampler dimensions 4 and 5). AVR_ERR_ARG: a negative or non-finite radius, a
+ * focal distance <= 0 or NaN, a spherical camera; AVR_ERR_STATE: no camera yet. */
+int avr_camera_lens(avr_context *ctx, float lens_radius, float focal_distance);
+
+/* SphericalCamera (cameras.cpp:610-687) in place of avr_camera: mapping 0 equalarea, 1
+ * equirectangular; uv = pFilm / the film's full resolution; render_from_camera: affine 4x4. */
+int avr_camera_spherical(avr_context *ctx, int mapping, const float render_from_camera[16]);
+
 /* RGBFilm with a box filter and a PixelSensor (film.h:95-100, 232-316): sensor_rgb is the
  * 3 x 471 r̄ḡb̄ (cie1931: X, Y, Z) tables, imaging_ratio = exposureTime*ISO/100.
  * Allocates and zeroes the fp64 film sums (3 + 1 doubles per pixel). */

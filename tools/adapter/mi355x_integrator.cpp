@@ -163,19 +163,33 @@ class Mi355xVolPathIntegrator : public Integrator {
         UploadLights(ctx, lights, aggregate.Bounds());
 
         // camera: cameraFromRaster (cameras.h:272) and renderFromCamera at t = 0
+        // the thin lens: ProjectiveCamera's protected lensRadius / focalDistance (cameras.h:279)
         float cfr[16], rfc[16];
         int camType = 1;
+        Float lensRadius = 0, focalDistance = 1e6f;
+        SphericalCamera *sc = camera.CastOrNullptr<SphericalCamera>();
         if (PerspectiveCamera *pc = camera.CastOrNullptr<PerspectiveCamera>()) {
             ToRowMajor(pc->CameraFromRaster().GetMatrix(), cfr);
+            lensRadius = pc->LensRadius();
+            focalDistance = pc->FocalDistance();
         } else if (OrthographicCamera *oc = camera.CastOrNullptr<OrthographicCamera>()) {
             ToRowMajor(oc->CameraFromRaster().GetMatrix(), cfr);
+            lensRadius = oc->LensRadius();
+            focalDistance = oc->FocalDistance();
             camType = 0;
-        } else {
-            ErrorExit("volpath_mi355x: perspective or orthographic cameras only");
+        } else if (!sc) {
+            ErrorExit("volpath_mi355x: perspective, orthographic or spherical cameras only");
         }
         const CameraTransform &ct = camera.GetCameraTransform();
         ToRowMajor(Inverse(ct.CameraFromRender(0.f)).GetMatrix(), rfc);
-        CheckAvr(avr_camera(ctx, camType, cfr, rfc), "avr_camera");
+        if (sc) {
+            // avr.h: 0 equalarea, 1 equirectangular (SphericalCamera::Mapping lists them the other way round)
+            CheckAvr(avr_camera_spherical(ctx, sc->IsEqualArea() ? 0 : 1, rfc),
+                     "avr_camera_spherical");
+        } else {
+            CheckAvr(avr_camera(ctx, camType, cfr, rfc), "avr_camera");
+            if (lensRadius > 0) CheckAvr(avr_camera_lens(ctx, lensRadius, focalDistance), "avr_camera_lens");
+        }
 
         // film: RGBFilm + its PixelSensor (film.h:95-100, 232-316) and filter
         RGBFilm *film = camera.GetFilm().CastOrNullptr<RGBFilm>();

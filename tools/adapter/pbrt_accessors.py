@@ -54,7 +54,10 @@ ACCESSORS = {
         ]),
     ],
     "cameras.h": [
-        ("ProjectiveCamera", ["const Transform &CameraFromRaster() const { return cameraFromRaster; }"]),
+        ("ProjectiveCamera", ["const Transform &CameraFromRaster() const { return cameraFromRaster; }",
+                              "Float LensRadius() const { return lensRadius; }",
+                              "Float FocalDistance() const { return focalDistance; }"]),
+        ("SphericalCamera", ["bool IsEqualArea() const { return mapping == EqualArea; }"]),
     ],
     "lights.h": [
         ("UniformInfiniteLight", [
