@@ -125,6 +125,9 @@ SIGNATURES = {
     "avr_set_refill_min": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_refill_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_light_sampler": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "avr_light_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [c_float_p] * 8),
+    "avr_light_pick": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p]),
+    "avr_light_sampler_table": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_int_p]),
     "avr_set_dda_budget": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_grid_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_grid_layout_active": (ctypes.c_int, [ctypes.c_void_p]),
@@ -434,6 +437,34 @@ class Context:
     def set_light_sampler(self, kind):
         """0: "bvh" / "uniform" (identical for infinite lights); 1: "power" (avr_light_sampler)."""
         _check(self.lib.avr_light_sampler(self.h, int(kind)))
+
+    def light_probe(self, index, u2, w3, lambda4):
+        """avr_light_probe of light `index`: (wi (n, 3), pdf of the sample (n), Ls (n, 4), PDF_Li (n),
+        Le (n, 4)) for n (u0, u1), escaping directions and wavelength sets."""
+        u2 = np.ascontiguousarray(u2, np.float32).reshape(-1, 2)
+        w3 = np.ascontiguousarray(w3, np.float32).reshape(-1, 3)
+        lam = np.ascontiguousarray(lambda4, np.float32).reshape(-1, 4)
+        n = len(u2)
+        if len(w3) != n or len(lam) != n:
+            raise ValueError("light_probe: u2, w3 and lambda4 need one row per probe")
+        wi, ps, Ls = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 4), np.float32)
+        pl, Le = np.zeros(n, np.float32), np.zeros((n, 4), np.float32)
+        _check(self.lib.avr_light_probe(self.h, int(index), n, _fp(u2), _fp(w3), _fp(lam), _fp(wi), _fp(ps), _fp(Ls),
+                                        _fp(pl), _fp(Le)))
+        return wi, ps, Ls, pl, Le
+
+    def light_pick(self, u):
+        """avr_light_pick: (index (-1: none), pmf) of the light sampler's pick per draw."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1)
+        idx, pmf = np.zeros(len(u), np.int32), np.zeros(len(u), np.float32)
+        _check(self.lib.avr_light_pick(self.h, len(u), _fp(u), idx.ctypes.data_as(c_int_p), _fp(pmf)))
+        return idx, pmf
+
+    def light_sampler_table(self, n):
+        """avr_light_sampler_table of the n lights: (q, p, alias)."""
+        q, p, alias = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        _check(self.lib.avr_light_sampler_table(self.h, _fp(q), _fp(p), alias.ctypes.data_as(c_int_p)))
+        return q, p, alias
 
     def set_refill_min(self, lanes):
         _check(self.lib.avr_set_refill_min(self.h, int(lanes)))

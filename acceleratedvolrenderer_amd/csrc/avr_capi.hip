@@ -230,7 +230,7 @@ struct avr_context {
     bool phi_ok[avr::kMaxLights] = {};
     int light_sampler = 0;
     void *d_light_img[avr::kMaxLights] = {};
-    int n_image_lights = 0, image_lights_ready = 0;
+    int n_image_lights = 0;
     // film image / --mse-reference-image state
     float *d_image = nullptr, *d_reference = nullptr;
     double *d_metric = nullptr;      // kMetricBlocks * kMetricSlots partials + kMetricSlots totals
@@ -1625,7 +1625,6 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
     c->lights.scene_radius = scene_radius;
     c->n_image_lights = 0;
     for (int i = 0; i < n; ++i) c->n_image_lights += types[i] == 2 ? 1 : 0;
-    c->image_lights_ready = 0;
     for (int i = 0; i < avr::kMaxLights; ++i) {
         c->phi_ok[i] = i < n && types[i] != 2;
         c->h_phi[i] = c->phi_ok[i] ? phi_table_light(types[i], L + (size_t)i * avr::kNTable, scale[i], scene_radius) : 0.f;
@@ -1698,10 +1697,85 @@ int avr_light_image(avr_context *c, int index, int res, const float *pixel_coeff
         }
     HIP_TRY(hipMemcpyAsync(c->d_lights, c->h_lights, sizeof(c->h_lights), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    ++c->image_lights_ready;
     c->h_phi[index] = phi_image_light(pixel_coeffs, res, illuminant, L.scale, c->lights.scene_radius);
     c->phi_ok[index] = true;
     return update_light_sampler(c);
+}
+
+// Whether every type-2 light of the list has its image (avr_light_image)
+static bool image_lights_complete(const avr_context *c) {
+    for (int i = 0; i < c->lights.n; ++i)
+        if (c->h_lights[i].type == 2 && !c->d_light_img[i]) return false;
+    return true;
+}
+
+int avr_light_probe(avr_context *c, int index, int n, const float *u2, const float *w3, const float *lambda4,
+                    float *wi3, float *pdf_sample, float *Ls4, float *pdf_li, float *Le4) {
+    AVR_QUIESCE(c);
+    if (!c || index < 0 || index >= c->lights.n) return fail(AVR_ERR_ARG, "avr_light_probe: index must name a light");
+    if (n < 0 || n > 1 << 20 || (n > 0 && (!u2 || !w3 || !lambda4))) return fail(AVR_ERR_ARG, "avr_light_probe: bad probe arrays");
+    if (!image_lights_complete(c)) return fail(AVR_ERR_STATE, "image light without avr_light_image");
+    if (n == 0) return AVR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t N = (size_t)n;
+    float *d = nullptr;
+    HIP_TRY(dalloc(&d, N * 22));
+    float *du = d, *dw = d + 2 * N, *dl = d + 5 * N, *dwi = d + 9 * N, *dps = d + 12 * N, *dLs = d + 13 * N,
+          *dpl = d + 17 * N, *dLe = d + 18 * N;
+    hipError_t e = hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw, w3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_light_probe, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du, dw,
+                           dl, dwi, dps, dLs, dpl, dLe);
+        e = hipGetLastError();
+    }
+    const struct { float *host; const float *dev; size_t k; } outs[] = {{wi3, dwi, 3}, {pdf_sample, dps, 1}, {Ls4, dLs, 4},
+                                                                       {pdf_li, dpl, 1}, {Le4, dLe, 4}};
+    for (const auto &o : outs)
+        if (e == hipSuccess && o.host)
+            e = hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+}
+
+int avr_light_pick(avr_context *c, int n, const float *u, int *idx, float *pmf) {
+    AVR_QUIESCE(c);
+    if (!c || n < 0 || n > 1 << 20 || (n > 0 && (!u || !idx || !pmf))) return fail(AVR_ERR_ARG, "avr_light_pick: bad arrays");
+    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+        return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
+    if (n == 0) return AVR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t N = (size_t)n;
+    float *d = nullptr;
+    HIP_TRY(dalloc(&d, N * 3));
+    float *du = d, *dp = d + N;
+    int *di = (int *)(d + 2 * N);
+    hipError_t e = hipMemcpyAsync(du, u, N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_light_pick, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, n, du, di, dp);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(idx, di, N * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(pmf, dp, N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+}
+
+int avr_light_sampler_table(avr_context *c, float *q, float *p, int *alias) {
+    if (!c || (c->lights.n > 0 && (!q || !p || !alias))) return fail(AVR_ERR_ARG, "avr_light_sampler_table: null arg");
+    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+        return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
+    for (int i = 0; i < c->lights.n; ++i) {
+        q[i] = c->h_lights[i].aq;
+        p[i] = c->h_lights[i].ap;
+        alias[i] = c->h_lights[i].alias;
+    }
+    return AVR_OK;
 }
 
 int avr_camera(avr_context *c, int type, const float cfr[16], const float rfc[16]) {

@@ -3414,6 +3414,67 @@ __global__ void __launch_bounds__(256) k_transmittance(Params P, long long n, co
 }
 
 // ---------------------------------------------------------------------------
+// The light stage on its own (avr_light_probe): what the path kernels compute of one light before
+// a path enters, through the functions they call. One probe per lane: SampleLi with
+// allowIncompletePDF = true at (u0, u1) (wi, its pdf, Ls; a uniform infinite light and a zero map
+// pdf report no sample: pdf 0), and PDF_Li and Le of the escaping direction w. Any output may be
+// null.
+__global__ void __launch_bounds__(256) k_light_probe(DevLights ls, int index, int n, const float *__restrict__ u2,
+                                                     const float *__restrict__ w3, const float *__restrict__ lambda,
+                                                     float *__restrict__ wi3, float *__restrict__ pdf_sample,
+                                                     float *__restrict__ Ls4, float *__restrict__ pdf_li,
+                                                     float *__restrict__ Le4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || index < 0 || index >= ls.n) return;
+    const DevLight &lt = ls.list[index];
+    const Spec lamv = {lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]};
+    const LambdaIdx li = lambda_index(lamv);
+    V3 wi = {0.f, 0.f, 0.f};
+    Spec Ls = Spec::c(0.f);
+    float lsPdf = 0.f;
+    if (lt.type == 0) {
+        wi = {lt.w[0], lt.w[1], lt.w[2]};
+        Ls = sample_table(lt.L, li) * lt.scale;
+        lsPdf = 1.f;
+    } else if (lt.type == 2) {
+        float su, sv;
+        env::distrib_sample(lt.dist, u2[2 * i], u2[2 * i + 1], &su, &sv, &lsPdf);
+        if (lsPdf != 0) {
+            V3 wl;
+            env::square_to_sphere(su, sv, &wl.x, &wl.y, &wl.z);
+            wi = xf_vec3(lt.rfl, wl);
+            lsPdf = lsPdf / (4 * kPi);
+            Ls = image_le(lt, su, sv, lamv);
+        }
+    }
+    if (wi3) { wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z; }
+    if (pdf_sample) pdf_sample[i] = lsPdf;
+    if (Ls4) { Ls4[4 * i] = Ls.v0; Ls4[4 * i + 1] = Ls.v1; Ls4[4 * i + 2] = Ls.v2; Ls4[4 * i + 3] = Ls.v3; }
+    const V3 d = {w3[3 * i], w3[3 * i + 1], w3[3 * i + 2]};
+    Spec Le = Spec::c(0.f);
+    float pLi = 0.f;
+    if (lt.type == 1) {
+        Le = sample_table(lt.L, li) * lt.scale;
+    } else if (lt.type == 2) {
+        float eu, ev;
+        Le = image_le_dir(lt, d, lamv, &eu, &ev);
+        pLi = image_pdf_li(lt, d);
+    }
+    if (pdf_li) pdf_li[i] = pLi;
+    if (Le4) { Le4[4 * i] = Le.v0; Le4[4 * i + 1] = Le.v1; Le4[4 * i + 2] = Le.v2; Le4[4 * i + 3] = Le.v3; }
+}
+// light_pick<true> for n draws (avr_light_pick): the index (-1: no light) and its PMF
+__global__ void __launch_bounds__(256) k_light_pick(DevLights ls, int n, const float *__restrict__ u, int *__restrict__ idx,
+                                                    float *__restrict__ pmf) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float p = 0.f;
+    const int k = ls.n > 0 ? light_pick<true>(ls, u[i], &p) : -1;
+    idx[i] = k;
+    pmf[i] = k >= 0 ? p : 0.f;
+}
+
+// ---------------------------------------------------------------------------
 // MajorantGrid build — GridMedium ctor (media.cpp:229, 241-246): each cell is
 // SampledGrid::MaxValue over MajorantGrid::VoxelBounds (containers.h:838-857).
 // One workgroup per majorant cell; wave max-reduction, then LDS.

@@ -575,7 +575,9 @@ extern "C" int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, 
     if (!c) return fail(AVR_ERR_ARG, "null context");
     if (!c->has_medium || !c->has_camera || !c->has_film) return fail(AVR_ERR_STATE, "medium, camera and film required");
     if (spp_begin < 0 || spp_end < spp_begin || max_depth < 0) return fail(AVR_ERR_ARG, "bad sample range");
-    if (c->image_lights_ready < c->n_image_lights) return fail(AVR_ERR_STATE, "image light without avr_light_image");
+    // every type-2 light needs its own image: a count of avr_light_image calls would let a map
+    // replaced twice stand in for one never given, whose img and dist are null
+    if (!image_lights_complete(c)) return fail(AVR_ERR_STATE, "image light without avr_light_image");
     if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
         return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
     RenderCall rc;

@@ -288,12 +288,16 @@ class DistantLight:
 
 
 class UniformInfiniteLight:
-    """"infinite" light with constant L (lights.cpp:1529-1566); scale /= SpectrumToPhotometric."""
+    """"infinite" light with constant L (lights.cpp:1529-1566); scale /= SpectrumToPhotometric, and
+    with "illuminance" E_v > 0 scale *= E_v / Pi (the illuminance of a uniform hemisphere)."""
     type_id = 1
 
-    def __init__(self, L=None, scale=1.0):
+    def __init__(self, L=None, scale=1.0, illuminance=None):
         self.L = spectra.TABLES["D65"].copy() if L is None else spectra.as_table(L, 1.0)
-        self.scale = np.float32(np.float32(scale) / spectra.spectrum_to_photometric(self.L))
+        sc = np.float32(np.float32(scale) / spectra.spectrum_to_photometric(self.L))
+        if illuminance is not None and illuminance > 0:
+            sc = np.float32(sc * np.float32(np.float32(illuminance) / np.float32(math.pi)))
+        self.scale = sc
 
     def render_direction(self, render_from_world):
         return np.zeros(3, np.float32)
@@ -328,7 +332,7 @@ class ImageInfiniteLight:
                            ).astype(np.float32)
         sc = np.float32(np.float32(scale) / spectra.spectrum_to_photometric(self.illuminant))
         if illuminance is not None and illuminance > 0:
-            sc = np.float32(sc * np.float32(illuminance) / np.float32(self._illuminance(img)))
+            sc = np.float32(sc * np.float32(np.float32(illuminance) / self._illuminance(img)))
         self.scale = sc
         self.L = np.zeros(spectra.N, np.float32)
         self.world_from_light = np.eye(4) if world_from_light is None else np.asarray(world_from_light, np.float64)
@@ -340,26 +344,30 @@ class ImageInfiniteLight:
         self.distribution = np.ascontiguousarray((avg / np.float32(3)).astype(np.float32))
 
     @staticmethod
-    def _illuminance(img):
-        """Upper-hemisphere illuminance of the map (lights.cpp:1621-1641) with the colour
-        space's LuminanceVector (row Y of XYZFromRGB); accumulated in f64."""
+    def _cos_theta(res):
+        """cos(theta) = z of EqualAreaSquareToSphere at the pixel centres of a res x res map, float32
+        (util/math.cpp: z = copysign(1 - r^2, 1 - (|u| + |v|)))."""
+        f32 = np.float32
+        c = ((np.arange(res, dtype=np.float32) + f32(0.5)) / f32(res)).astype(np.float32)
+        uu, vv = np.meshgrid(f32(2) * c - f32(1), f32(2) * c - f32(1))
+        sd = f32(1) - (np.abs(uu) + np.abs(vv))
+        r = f32(1) - np.abs(sd)
+        return np.copysign(f32(1) - r * r, sd).astype(np.float32)
+
+    @classmethod
+    def _illuminance(cls, img):
+        """Upper-hemisphere illuminance of the map (lights.cpp:1621-1641) with the colour space's
+        LuminanceVector (row Y of XYZFromRGB), in the reference's float order: per pixel (rows y,
+        then x) of the upper hemisphere and per channel, illuminance += value * lum * cos(theta),
+        then * 2 Pi / res^2."""
+        f32 = np.float32
         res = img.shape[0]
-        lum = np.linalg.inv(spectra.TABLES["srgb_rgb_from_xyz"].astype(np.float64))[1]
-        total = 0.0
-        for y in range(res):
-            v = (y + 0.5) / res
-            for x in range(res):
-                u = (x + 0.5) / res
-                uu, vv = 2 * u - 1, 2 * v - 1
-                up, vp = abs(uu), abs(vv)
-                sd = 1 - (up + vp)
-                r = 1 - abs(sd)
-                phi = (1 if r == 0 else (vp - up) / r + 1) * math.pi / 4
-                z = math.copysign(1 - r * r, sd)
-                if z <= 0:
-                    continue
-                total += float(np.dot(img[y, x].astype(np.float64), lum)) * z
-        return total * 2 * math.pi / (res * res)
+        lum = np.linalg.inv(spectra.TABLES["srgb_rgb_from_xyz"].astype(np.float64))[1].astype(np.float32)
+        z = cls._cos_theta(res)
+        up = z > 0
+        terms = ((img[up] * lum).astype(np.float32) * z[up][:, None]).astype(np.float32).reshape(-1)
+        total = np.cumsum(terms, dtype=np.float32)[-1] if terms.size else f32(0)   # sequential float sum
+        return f32(total * f32(f32(f32(2) * f32(math.pi)) / f32(res * res)))
 
     def render_direction(self, render_from_world):
         return np.zeros(3, np.float32)

@@ -351,6 +351,26 @@ int avr_light_image(avr_context *ctx, int index, int res, const float *pixel_coe
  * render needs every image light's avr_light_image first. */
 int avr_light_sampler(avr_context *ctx, int kind);
 
+/* Readbacks of the light stage (replay checks; no render path uses them).
+ * avr_light_probe runs, for light `index` of the last avr_lights call and n probes, the device
+ * functions the path kernels call: SampleLi with allowIncompletePDF = true at (u0, u1) (u2, n*2)
+ * gives the render-space wi (wi3, n*3), its pdf (pdf_sample, n) and Ls (Ls4, n*4) at the
+ * wavelengths lambda4 (n*4); PDF_Li and Le of the escaping render-space direction w3 (n*3) give
+ * pdf_li (n) and Le4 (n*4). A distant light samples its direction with pdf 1 and has PDF_Li and Le
+ * 0; a uniform infinite light reports no sample (pdf_sample 0, wi and Ls 0), PDF_Li 0 and
+ * Le = scale * L(lambda); an image light whose map pdf is 0 at (u0, u1) reports no sample. Any
+ * output may be NULL. AVR_ERR_STATE while a type-2 light lacks its avr_light_image.
+ * avr_light_probe and avr_light_pick change no result but are no free readbacks: like every call that
+ * touches the light list they wait for the context's streams and drop camera records made ahead
+ * for the next pass, which that pass then makes again.
+ * avr_light_pick: the light sampler's pick for n draws u: idx (n; -1: no light) and its PMF (n).
+ * avr_light_sampler_table (host only): per light the sampler's bin {q, p, alias}: the AliasTable
+ * of the power sampler, or q = 1, p = 1 / n, alias = -1 for "bvh" / "uniform". */
+int avr_light_probe(avr_context *ctx, int index, int n, const float *u2, const float *w3, const float *lambda4,
+                    float *wi3, float *pdf_sample, float *Ls4, float *pdf_li, float *Le4);
+int avr_light_pick(avr_context *ctx, int n, const float *u, int *idx, float *pmf);
+int avr_light_sampler_table(avr_context *ctx, float *q, float *p, int *alias);
+
 /* Camera: type 0 orthographic, 1 perspective (cameras.cpp:284-306, 404-427).
  * camera_from_raster: full 4x4 (projective for perspective); render_from_camera: affine 4x4. */
 int avr_camera(avr_context *ctx, int type, const float camera_from_raster[16], const float render_from_camera[16]);

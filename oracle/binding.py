@@ -79,6 +79,7 @@ class OracleScene(ctypes.Structure):
         ("film_nbuckets", ctypes.c_int), ("film_lambda_min", ctypes.c_float), ("film_lambda_max", ctypes.c_float),
         ("boundary", ctypes.c_int), ("sphere", ctypes.c_float * 4), ("n_planes", ctypes.c_int), ("planes", c_float_p),
         ("light_sampler", ctypes.c_int),
+        ("light_variant", ctypes.c_int),
     ]
 
 
@@ -93,6 +94,18 @@ def lib():
         L.oracle_pixel_sample.restype = ctypes.c_int
         L.oracle_pixel_sample.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           c_float_p, c_float_p, c_float_p, c_float_p]
+        c_int_p = ctypes.POINTER(ctypes.c_int)
+        for name, args in (("oracle_light_sample", [ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p,
+                                                    c_float_p, c_float_p]),
+                           ("oracle_light_pdf", [ctypes.c_int, ctypes.c_int, c_float_p, c_float_p]),
+                           ("oracle_light_le", [ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, c_float_p]),
+                           ("oracle_light_sampler_table", [c_float_p, c_float_p, c_int_p]),
+                           ("oracle_light_pick", [ctypes.c_int, c_float_p, c_int_p, c_float_p])):
+            getattr(L, name).restype = None
+            getattr(L, name).argtypes = [ctypes.POINTER(OracleScene)] + args
+        L.oracle_alias_table.restype = None
+        L.oracle_alias_table.argtypes = [ctypes.c_int, c_float_p, c_float_p, c_float_p, c_int_p, ctypes.c_int, c_float_p,
+                                         c_int_p, c_float_p]
         L.oracle_camera_ray.restype = None
         L.oracle_camera_ray.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
@@ -323,6 +336,21 @@ def vdb_majorant(dtree, bounds, res=(64, 64, 64)):
     return out
 
 
+def alias_table(weights, u):
+    """PowerLightSampler's AliasTable over the light weights (at most 8): (q, p, alias) and
+    AliasTable::Sample's (index, pmf) for the draws u."""
+    w = np.ascontiguousarray(weights, np.float32)
+    u = np.ascontiguousarray(u, np.float32)
+    n = len(w)
+    if not 1 <= n <= 8:
+        raise ValueError("1..8 weights")
+    q, p, alias = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+    idx, pmf = np.zeros(len(u), np.int32), np.zeros(len(u), np.float32)
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    lib().oracle_alias_table(n, fp(w), fp(q), fp(p), ip(alias), len(u), fp(u), ip(idx), fp(pmf))
+    return (q, p, alias), (idx, pmf)
+
+
 class OracleRun:
     """Holds an OracleScene and the numpy buffers it points into."""
 
@@ -449,6 +477,50 @@ class OracleRun:
         if with_weight:
             return L, lam, pdf, n, w[0]
         return L, lam, pdf, n
+
+    def light_sample(self, index, u2, lambda4):
+        """SampleLi(allowIncompletePDF = true) of light `index` for n (u0, u1) and wavelength sets:
+        wi (n, 3), pdf (n; 0: no sample), Ls (n, 4)."""
+        u2 = np.ascontiguousarray(u2, np.float32).reshape(-1, 2)
+        lam = np.ascontiguousarray(lambda4, np.float32).reshape(-1, 4)
+        n = len(u2)
+        wi, pdf, Ls = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 4), np.float32)
+        set_libm(self.libm)
+        lib().oracle_light_sample(ctypes.byref(self.s), int(index), n, fp(u2), fp(lam), fp(wi), fp(pdf), fp(Ls))
+        return wi, pdf, Ls
+
+    def light_pdf(self, index, w3):
+        """PDF_Li(w, allowIncompletePDF = true) of light `index` for n render-space directions."""
+        w3 = np.ascontiguousarray(w3, np.float32).reshape(-1, 3)
+        pdf = np.zeros(len(w3), np.float32)
+        set_libm(self.libm)
+        lib().oracle_light_pdf(ctypes.byref(self.s), int(index), len(w3), fp(w3), fp(pdf))
+        return pdf
+
+    def light_le(self, index, w3, lambda4):
+        """Le of light `index` along n escaping render-space directions: (n, 4)."""
+        w3 = np.ascontiguousarray(w3, np.float32).reshape(-1, 3)
+        lam = np.ascontiguousarray(lambda4, np.float32).reshape(-1, 4)
+        Le = np.zeros((len(w3), 4), np.float32)
+        set_libm(self.libm)
+        lib().oracle_light_le(ctypes.byref(self.s), int(index), len(w3), fp(w3), fp(lam), fp(Le))
+        return Le
+
+    def light_sampler_table(self):
+        """(q, p, alias) of the light sampler over the scene's lights."""
+        n = int(self.s.nlights)
+        q, p, alias = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        set_libm(self.libm)
+        lib().oracle_light_sampler_table(ctypes.byref(self.s), fp(q), fp(p), alias.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return q, p, alias
+
+    def light_pick(self, u):
+        """SampleLd's light pick for n draws: (index (-1: none), pmf)."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1)
+        idx, pmf = np.zeros(len(u), np.int32), np.zeros(len(u), np.float32)
+        set_libm(self.libm)
+        lib().oracle_light_pick(ctypes.byref(self.s), len(u), fp(u), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), fp(pmf))
+        return idx, pmf
 
     def camera_ray(self, px, py, sample_index):
         """What pixel_sample computes before its first segment: (o (3) after the interface entry,

@@ -8,6 +8,8 @@ pbrt-v4 sources under /root/reference (oracle/ref/Makefile), runs it and writes
       360..830 nm), sRGB RGBFromXYZ (9), D65 photometric scale, CIE_Y_integral
   tests/golden/camera_ray_vectors.json         — the reference's camera rays of tests/camera_cases.py's cameras
   tests/golden/gaussian_filter_vectors.json    — GaussianFilter::Sample at that module's radii and sigmas
+  tests/golden/light_vectors.json              — the reference's light stage at tests/light_cases.py's maps,
+      transforms, probes, alias weights, spectra and distant lights
 The RGB -> spectrum goldens read the sRGB table that the reference's own rgb2spec_opt
 writes into oracle/_ref (Makefile); the table stays there (not committed).
 The spectral tables are published CIE / ITU data as the reference holds them;
@@ -43,6 +45,11 @@ def main():
     filters = subprocess.check_output([exe, "--filters"])
     with open(os.path.join(REPO, "tests", "golden", "gaussian_filter_vectors.json"), "wb") as f:
         f.write(filters)
+    import light_cases
+    lights = subprocess.check_output([exe, "--rgbtable", rgbtable, "--lights"],
+                                     input=light_cases.harness_light_lines().encode())
+    with open(os.path.join(REPO, "tests", "golden", "light_vectors.json"), "wb") as f:
+        f.write(lights)
     print("wrote", len(out), "bytes of golden vectors and", os.path.getsize(tables), "bytes of tables")
 
 

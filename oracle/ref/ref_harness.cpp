@@ -19,7 +19,12 @@
 //   sRGB RGBFromXYZ (util/colorspace.cpp),
 //   LookAt / Perspective / Orthographic / Scale / Translate / Inverse (util/transform.cpp) composed
 //   as CameraTransform (cameras.cpp:27-57, CameraWorld) and the ProjectiveCamera constructor
-//   (cameras.h:254-273) compose them (--camera-rays).
+//   (cameras.h:254-273) compose them (--camera-rays),
+//   PiecewiseConstant2D, EqualAreaSquareToSphere / EqualAreaSphereToSquare, RemapPixelCoords,
+//   RGBIlluminantSpectrum, Transform, CoordinateSystem, AliasTable, SpectrumToPhotometric and
+//   BlackbodySpectrum composed as ImageInfiniteLight (lights.h:552-640, lights.cpp:1007-1060), its
+//   Create (lights.cpp:1620-1648), DistantLight::Create (lights.cpp:246-276) and PowerLightSampler
+//   (lightsamplers.cpp:76-96) compose them (--lights).
 // Output: JSON on stdout (golden vectors) and, with --tables <file>, a raw
 // little-endian float32 table file consumed by oracle/ref/gen_golden.py.
 #include <pbrt/util/rng.h>
@@ -39,6 +44,10 @@
 
 #include <cstdio>
 #include <cstring>
+#include <iostream>
+#include <map>
+#include <numeric>
+#include <sstream>
 #include <vector>
 #include <string>
 
@@ -229,18 +238,240 @@ static void gaussian_filter_samples(const float (*cfg)[3], int n, RNG &rng) {
     printf("]");
 }
 
+// --lights: tests/golden/light_vectors.json. Standard input as tests/light_cases.py::
+// harness_light_lines writes it, floats as uint32 bits, one command per line:
+//   cam x y z                      the camera position (CameraWorld: renderFromWorld = Translate(-cam))
+//   lambda n bits(4n)              the wavelength sets (probe i uses set i mod n)
+//   map NAME res bits(3 res^2)     an RGB map, rows y then x
+//   xf NAME bits(16)               a worldFromLight matrix, row-major
+//   u MAP n bits(2n)               the (u0, u1) probes of a map
+//   pair MAP XF k bits(2k) n bits(3n)  a (map, transform) pair: SampleLi at k (u0, u1), PDF_Li and Le at n
+//                                  render-space directions
+//   alias NAME n bits(n) m bits(m) light weights and the draws
+//   photometric NAME kind value    SpectrumToPhotometric of BlackbodySpectrum(value) (kind b),
+//                                  ConstantSpectrum(value) (kind c) or the colour space's illuminant (kind d)
+//   distant NAME XF|- from(3) to(3)  DistantLight::Create's direction
+// The reference's Image and lights.cpp need OpenEXR and the other absent submodules, so their
+// few lines are composed here from the reference's own functions, in their order.
+static float uf(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+static std::vector<float> read_floats(std::istringstream &in, size_t n) {
+    std::vector<float> v(n);
+    for (size_t i = 0; i < n; ++i) { uint32_t b = 0; in >> b; v[i] = uf(b); }
+    return v;
+}
+struct LightMap {
+    int res = 0;
+    std::vector<float> rgb;    // 3 res^2
+    std::vector<float> u;      // 2 n
+    std::vector<Float> comp;   // the compensated function
+};
+static int light_vectors(const char *rgbTablePath, Allocator alloc) {
+    std::vector<float> zNodes, coeffs;
+    if (!rgbTablePath || !ReadRgbTable(rgbTablePath, zNodes, coeffs)) { fprintf(stderr, "--lights needs --rgbtable\n"); return 1; }
+    RGBToSpectrumTable table(zNodes.data(), (const RGBToSpectrumTable::CoefficientArray *)coeffs.data());
+    Spectrum d65 = GetNamedSpectrum("stdillum-D65");
+    RGBColorSpace srgb(Point2f(.64, .33), Point2f(.3, .6), Point2f(.15, .06), d65, &table, alloc);
+    // Create: scale /= SpectrumToPhotometric(&colorSpace->illuminant)
+    const Float lightScale = Float(1) / SpectrumToPhotometric(&srgb.illuminant);
+    std::map<std::string, LightMap> maps;
+    std::map<std::string, Transform> xfs;
+    std::vector<float> lambdas;
+    Transform renderFromWorld;
+    std::string line, sect[7];
+    auto add = [&](int k, const std::string &item) { sect[k] += (sect[k].empty() ? "" : ",") + item; };
+    // a float array as a JSON string: base64 of its little-endian float32 bytes
+    auto bits = [](const std::vector<float> &v) {
+        static const char *tab = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+        std::string raw((const char *)v.data(), v.size() * 4), o = "\"";
+        for (size_t i = 0; i < raw.size(); i += 3) {
+            uint32_t x = 0;
+            const size_t k = std::min<size_t>(3, raw.size() - i);
+            for (size_t j = 0; j < 3; ++j) x = (x << 8) | (j < k ? (unsigned char)raw[i + j] : 0);
+            for (size_t j = 0; j < 4; ++j) o += j <= k ? tab[(x >> (18 - 6 * j)) & 63] : '=';
+        }
+        return o + "\"";
+    };
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string cmd, name;
+        in >> cmd;
+        if (cmd == "cam") {
+            std::vector<float> c = read_floats(in, 3);
+            renderFromWorld = Inverse(Translate(Vector3f(c[0], c[1], c[2])));
+        } else if (cmd == "lambda") {
+            size_t n; in >> n;
+            lambdas = read_floats(in, 4 * n);
+        } else if (cmd == "map") {
+            LightMap m;
+            in >> name >> m.res;
+            const int res = m.res;
+            m.rgb = read_floats(in, 3 * (size_t)res * res);
+            // Image::GetSamplingDistribution (util/image.h:451-470): ImageChannelValues::Average, dxdA = 1
+            std::vector<Float> d((size_t)res * res);
+            for (size_t i = 0; i < d.size(); ++i) {
+                Float sum = 0;
+                for (int c = 0; c < 3; ++c) sum += m.rgb[3 * i + c];
+                d[i] = sum / 3;
+            }
+            // the compensated distribution (lights.cpp:1031-1038)
+            Float average = std::accumulate(d.begin(), d.end(), 0.) / d.size();
+            for (Float &v : d) v = std::max<Float>(v - average, 0);
+            if (std::all_of(d.begin(), d.end(), [](Float v) { return v == 0; })) std::fill(d.begin(), d.end(), Float(1));
+            m.comp = d;
+            // Create's upper-hemisphere illuminance (lights.cpp:1620-1648)
+            float illuminance = 0;
+            RGB lum = srgb.LuminanceVector();
+            for (int y = 0; y < res; ++y) {
+                float v = (float(y) + 0.5f) / float(res);
+                for (int x = 0; x < res; ++x) {
+                    Float u = (x + 0.5f) / res;
+                    Vector3f w = EqualAreaSquareToSphere(Point2f(u, v));
+                    if (w.z <= 0) continue;
+                    for (int c = 0; c < 3; ++c) illuminance += m.rgb[3 * ((size_t)y * res + x) + c] * lum[c] * CosTheta(w);
+                }
+            }
+            illuminance *= 2 * Pi / (res * res);
+            add(0, "\"" + name + "\":{\"res\":" + std::to_string(res) + ",\"func\":" +
+                       bits(std::vector<float>(d.begin(), d.end())) + ",\"k_e\":" + std::to_string(fb(illuminance)) + "}");
+            maps[name] = m;
+        } else if (cmd == "xf") {
+            in >> name;
+            std::vector<float> v = read_floats(in, 16);
+            Float mm[4][4];
+            for (int i = 0; i < 16; ++i) mm[i / 4][i % 4] = v[i];
+            Transform rfl = renderFromWorld * Transform(mm);
+            xfs[name] = rfl;
+            std::vector<float> a, b;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) { a.push_back(rfl.GetMatrix()[r][c]); b.push_back(rfl.GetInverseMatrix()[r][c]); }
+            add(1, "\"" + name + "\":{\"rfl\":" + bits(a) + ",\"lfr\":" + bits(b) + "}");
+        } else if (cmd == "u") {
+            size_t n;
+            in >> name >> n;
+            LightMap &m = maps[name];
+            m.u = read_floats(in, 2 * n);
+            PiecewiseConstant2D dist(pstd::span<const Float>(m.comp), m.res, m.res, Bounds2f(Point2f(0, 0), Point2f(1, 1)), alloc);
+            std::vector<float> out;   // [su, sv, pdf, PDF(su, sv)] per probe
+            for (size_t i = 0; i < n; ++i) {
+                Float pdf = 0;
+                Point2f uv = dist.Sample(Point2f(m.u[2 * i], m.u[2 * i + 1]), &pdf);
+                out.insert(out.end(), {uv.x, uv.y, pdf, dist.PDF(uv)});
+            }
+            add(2, "\"" + name + "\":" + bits(out));
+        } else if (cmd == "pair") {
+            std::string xn;
+            size_t n, nu;
+            in >> name >> xn >> nu;
+            std::vector<float> pu = read_floats(in, 2 * nu);
+            in >> n;
+            std::vector<float> dirs = read_floats(in, 3 * n);
+            const LightMap &m = maps[name];
+            const Transform &renderFromLight = xfs[xn];
+            const int res = m.res;
+            PiecewiseConstant2D comp(pstd::span<const Float>(m.comp), res, res, Bounds2f(Point2f(0, 0), Point2f(1, 1)), alloc);
+            const size_t nl = lambdas.size() / 4;
+            // ImageLe (lights.h:620-627): LookupNearestChannel with WrapMode::OctahedralSphere
+            auto imageLe = [&](Point2f uv, size_t probe, std::vector<float> &out) {
+                Point2i pi(uv.x * res, uv.y * res);
+                RGB rgb(0, 0, 0);
+                if (RemapPixelCoords(&pi, Point2i(res, res), WrapMode::OctahedralSphere))
+                    for (int c = 0; c < 3; ++c) rgb[c] = m.rgb[3 * ((size_t)pi.y * res + pi.x) + c];
+                RGBIlluminantSpectrum spec(srgb, ClampZero(rgb));
+                for (int k = 0; k < 4; ++k) out.push_back(lightScale * spec(lambdas[4 * (probe % nl) + k]));
+            };
+            std::vector<float> wi, pdf, Ls, pli, Le;
+            for (size_t i = 0; i < nu; ++i) {   // SampleLi, allowIncompletePDF = true
+                Float mapPDF = 0;
+                Point2f uv = comp.Sample(Point2f(pu[2 * i], pu[2 * i + 1]), &mapPDF);
+                if (mapPDF == 0) {
+                    wi.insert(wi.end(), {0.f, 0.f, 0.f}); pdf.push_back(0.f); Ls.insert(Ls.end(), {0.f, 0.f, 0.f, 0.f});
+                    continue;
+                }
+                Vector3f wLight = EqualAreaSquareToSphere(uv);
+                Vector3f w = renderFromLight(wLight);
+                wi.insert(wi.end(), {w.x, w.y, w.z});
+                pdf.push_back(mapPDF / (4 * Pi));
+                imageLe(uv, i, Ls);
+            }
+            for (size_t i = 0; i < n; ++i) {
+                Vector3f w(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+                // PDF_Li (lights.cpp:1042-1052)
+                Vector3f wLight = renderFromLight.ApplyInverse(w);
+                pli.push_back(comp.PDF(EqualAreaSphereToSquare(wLight)) / (4 * Pi));
+                // Le (lights.h:581-585)
+                Vector3f wn = Normalize(renderFromLight.ApplyInverse(w));
+                imageLe(EqualAreaSphereToSquare(wn), i, Le);
+            }
+            add(3, "\"" + name + "+" + xn + "\":{\"wi\":" + bits(wi) + ",\"pdf\":" + bits(pdf) +
+                       ",\"Ls\":" + bits(Ls) + ",\"pdf_li\":" + bits(pli) + ",\"Le\":" + bits(Le) + "}");
+        } else if (cmd == "alias") {
+            size_t n, mDraws;
+            in >> name >> n;
+            std::vector<float> w = read_floats(in, n);
+            in >> mDraws;
+            std::vector<float> us = read_floats(in, mDraws);
+            // PowerLightSampler (lightsamplers.cpp:89-92)
+            std::vector<Float> lightPower(w.begin(), w.end());
+            if (std::accumulate(lightPower.begin(), lightPower.end(), 0.f) == 0.f)
+                std::fill(lightPower.begin(), lightPower.end(), 1.f);
+            AliasTable at(lightPower, alloc);
+            std::vector<float> pmf, spmf;
+            std::string idx = "[";
+            for (size_t i = 0; i < n; ++i) pmf.push_back(at.PMF((int)i));
+            for (size_t i = 0; i < mDraws; ++i) {
+                Float p = 0;
+                int k = at.Sample(us[i], &p);
+                idx += (i ? "," : "") + std::to_string(k);
+                spmf.push_back(p);
+            }
+            add(4, "\"" + name + "\":{\"p\":" + bits(pmf) + ",\"pick\":" + idx +
+                       "],\"pmf\":" + bits(spmf) + "}");
+        } else if (cmd == "photometric") {
+            std::string kind;
+            double value;
+            in >> name >> kind >> value;
+            Float y;
+            if (kind == "d") y = SpectrumToPhotometric(&srgb.illuminant);
+            else if (kind == "b") { BlackbodySpectrum bb((Float)value); y = SpectrumToPhotometric(&bb); }
+            else { ConstantSpectrum cs((Float)value); y = SpectrumToPhotometric(&cs); }
+            add(5, "\"" + name + "\":" + std::to_string(fb(y)));
+        } else if (cmd == "distant") {
+            std::string xn;
+            in >> name >> xn;
+            std::vector<float> ft = read_floats(in, 6);
+            Transform renderFromLight = xn == "-" ? renderFromWorld : xfs[xn];
+            // DistantLight::Create (lights.cpp:254-263), then lights.h:287
+            Vector3f w = Normalize(Point3f(ft[0], ft[1], ft[2]) - Point3f(ft[3], ft[4], ft[5]));
+            Vector3f v1, v2;
+            CoordinateSystem(w, &v1, &v2);
+            Float mm[4][4] = {v1.x, v2.x, w.x, 0, v1.y, v2.y, w.y, 0, v1.z, v2.z, w.z, 0, 0, 0, 0, 1};
+            Transform t(mm);
+            Transform finalRenderFromLight = renderFromLight * t;
+            Vector3f wi = Normalize(finalRenderFromLight(Vector3f(0, 0, 1)));
+            add(6, "\"" + name + "\":" + bits({wi.x, wi.y, wi.z}));
+        }
+    }
+    printf("{\"scale\":%u,\"lambda\":%s", fb(lightScale), bits(lambdas).c_str());
+    const char *names[7] = {"maps", "transforms", "samples", "pairs", "alias", "photometric", "distant"};
+    for (int k = 0; k < 7; ++k) printf(",\"%s\":{%s}", names[k], sect[k].c_str());
+    printf("}\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     Allocator alloc;
     Spectra::Init(alloc);
     const char *tablePath = nullptr, *rgbTablePath = nullptr;
-    bool hgEdges = false, filters = false;
+    bool hgEdges = false, filters = false, lights = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--tables") && i + 1 < argc) tablePath = argv[++i];
         if (!strcmp(argv[i], "--rgbtable") && i + 1 < argc) rgbTablePath = argv[++i];
         if (!strcmp(argv[i], "--hg-edges")) hgEdges = true;
         if (!strcmp(argv[i], "--camera-rays")) return camera_rays();
         if (!strcmp(argv[i], "--filters")) filters = true;
+        if (!strcmp(argv[i], "--lights")) lights = true;
     }
+    if (lights) return light_vectors(rgbTablePath, alloc);
     if (filters) {
         // tests/golden/gaussian_filter_vectors.json: the radii and sigmas of tests/camera_cases.py's
         // Gaussian filters (tables that are not square, 128 x 128, 16 x 16, all-zero rows)

@@ -938,6 +938,10 @@ typedef struct OracleScene {
     const float *planes;
     // VolPath's "lightsampler": 0 bvh / uniform (identical for infinite lights), 1 power
     int light_sampler;
+    // 0: the image lights as the reference has them. The wrong formulas of tests/light_cases.py's
+    // sensitivity conditions: bit 0 samples the uncompensated distribution, bit 1 looks the pixel
+    // up with res - 1
+    int light_variant;
 } OracleScene;
 
 }  // extern "C"
@@ -1301,11 +1305,14 @@ struct ImageLight {
     int res = 0;
     PC2D compensated;
     const float *rfl = nullptr, *lfr = nullptr;
-    void Build(const float *image, int r, const float *dist, const float *rfl_, const float *lfr_) {
+    int lookupRes = 0;
+    void Build(const float *image, int r, const float *dist, const float *rfl_, const float *lfr_, int variant = 0) {
         img = image; res = r; rfl = rfl_; lfr = lfr_;
+        lookupRes = (variant & 2) && r > 1 ? r - 1 : r;
         const size_t n = (size_t)r * r;
         std::vector<float> d(dist, dist + n);
         float average = std::accumulate(d.begin(), d.end(), 0.) / d.size();   // lights.cpp:1031
+        if (variant & 1) average = 0;
         for (float &v : d) v = std::max<float>(v - average, 0);
         if (std::all_of(d.begin(), d.end(), [](float v) { return v == 0; })) std::fill(d.begin(), d.end(), 1.f);
         compensated.Build(d.data(), r, r);
@@ -1315,7 +1322,7 @@ struct ImageLight {
                 m[6] * v.x + m[7] * v.y + m[8] * v.z};
     }
     Spec ImageLe(float u, float v, const Lambda &l, const float *illum, float scale) const {   // lights.h:620-627
-        const float *c = img + 4 * (size_t)OctahedralPixel(u, v, res);
+        const float *c = img + 4 * (size_t)OctahedralPixel(u, v, lookupRes);
         Rsp rsp{c[0], c[1], c[2]};
         Spec s;
         for (int i = 0; i < NS; ++i) s.v[i] = c[3] * rsp(l.lambda[i]);
@@ -1357,9 +1364,12 @@ struct PowerSampler {
         return w.Average();
     }
     void Build(const OracleScene &s, const ImageLight *img) {
-        const int n = s.nlights;
-        std::vector<float> w(n);
-        for (int i = 0; i < n; ++i) w[i] = Weight(s, img, i);
+        std::vector<float> w(s.nlights);
+        for (int i = 0; i < s.nlights; ++i) w[i] = Weight(s, img, i);
+        BuildFromWeights(w);
+    }
+    void BuildFromWeights(std::vector<float> w) {   // lightsamplers.cpp:89-92, then AliasTable's constructor
+        const int n = (int)w.size();
         if (std::accumulate(w.begin(), w.end(), 0.f) == 0.f) std::fill(w.begin(), w.end(), 1.f);
         const float sum = std::accumulate(w.begin(), w.end(), 0.);
         for (int i = 0; i < n; ++i) p[i] = w[i] / sum;
@@ -1404,7 +1414,8 @@ struct SceneView {
         if (sc.filter_type == 1) gauss.Build(sc.filter_radius[0], sc.filter_radius[1], sc.filter_sigma);
         for (int i = 0; i < sc.nlights; ++i)
             if (sc.light_type[i] == 2)
-                img[i].Build(sc.light_img[i], sc.light_res[i], sc.light_dist[i], sc.light_rfl[i], sc.light_lfr[i]);
+                img[i].Build(sc.light_img[i], sc.light_res[i], sc.light_dist[i], sc.light_rfl[i], sc.light_lfr[i],
+                             sc.light_variant);
         if (sc.light_sampler == 1 && sc.nlights > 0) power.Build(sc, img);
         for (int i = 0; i < 16; ++i) {
             mediumX.m[i / 4][i % 4] = sc.render_from_medium[i];
@@ -2039,6 +2050,101 @@ void oracle_build_majorant(const float *density, int nx, int ny, int nz, int rx,
                          {float(x + 1) / rx, float(y + 1) / ry, float(z + 1) / rz}};
                 out[x + rx * (y + ry * z)] = g.MaxValue(b);
             }
+}
+
+// The light stage on its own (tests/light_cases.py): what SampleLd and the escape loop compute of
+// light `index` before the path enters. oracle_light_sample: LightSampleContext-free SampleLi with
+// allowIncompletePDF = true for n (u0, u1) and wavelength sets: wi (3), pdf, Ls (4); a light that
+// returns no sample (a uniform infinite light, a zero map pdf) reports pdf 0 and zeros.
+void oracle_light_sample(const OracleScene *s, int index, int n, const float *u2, const float *lambda4, float *wi3,
+                         float *pdf, float *Ls4) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        Lambda l;
+        for (int k = 0; k < NS; ++k) l.lambda[k] = lambda4[4 * i + k], l.pdf[k] = 1;
+        V3 wi = {0, 0, 0};
+        Spec Ls = Spec::Const(0.f);
+        float p = 0;
+        if (s->light_type[index] == 0) {
+            wi = {s->light_w[index][0], s->light_w[index][1], s->light_w[index][2]};
+            Ls = s->light_scale[index] * SampleDense(s->light_L[index], l);
+            p = 1;
+        } else if (s->light_type[index] == 2) {
+            const ImageLight &il = sv.img[index];
+            float su, sv_, mapPDF = 0;
+            il.compensated.Sample(u2[2 * i], u2[2 * i + 1], &su, &sv_, &mapPDF);
+            if (mapPDF != 0) {
+                wi = ImageLight::Mul(il.rfl, EqualAreaSquareToSphere(su, sv_));
+                p = mapPDF / (4 * Pi);
+                Ls = il.ImageLe(su, sv_, l, s->light_illuminant, s->light_scale[index]);
+            }
+        }
+        wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z;
+        pdf[i] = p;
+        for (int k = 0; k < NS; ++k) Ls4[4 * i + k] = Ls.v[k];
+    }
+}
+// PDF_Li(ctx, w, allowIncompletePDF = true) of n render-space directions (0 for a distant or a
+// uniform infinite light)
+void oracle_light_pdf(const OracleScene *s, int index, int n, const float *w3, float *pdf) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        pdf[i] = 0;
+        if (s->light_type[index] != 2) continue;
+        const ImageLight &il = sv.img[index];
+        float eu, ev;
+        EqualAreaSphereToSquare(ImageLight::Mul(il.lfr, V3{w3[3 * i], w3[3 * i + 1], w3[3 * i + 2]}), &eu, &ev);
+        pdf[i] = il.compensated.PDF(eu, ev) / (4 * Pi);
+    }
+}
+// Le(ray) of n render-space directions and wavelength sets (0 for a distant light)
+void oracle_light_le(const OracleScene *s, int index, int n, const float *w3, const float *lambda4, float *Le4) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        Lambda l;
+        for (int k = 0; k < NS; ++k) l.lambda[k] = lambda4[4 * i + k], l.pdf[k] = 1;
+        Spec Le = Spec::Const(0.f);
+        if (s->light_type[index] == 1) {
+            Le = s->light_scale[index] * SampleDense(s->light_L[index], l);
+        } else if (s->light_type[index] == 2) {
+            const ImageLight &il = sv.img[index];
+            V3 wl = Normalize(ImageLight::Mul(il.lfr, V3{w3[3 * i], w3[3 * i + 1], w3[3 * i + 2]}));
+            float eu, ev;
+            EqualAreaSphereToSquare(wl, &eu, &ev);
+            Le = il.ImageLe(eu, ev, l, s->light_illuminant, s->light_scale[index]);
+        }
+        for (int k = 0; k < NS; ++k) Le4[4 * i + k] = Le.v[k];
+    }
+}
+// The light sampler's table over the scene's lights: the AliasTable bins {q, p, alias} of the
+// power sampler, or q = 1, p = 1 / n, alias = -1 for the BVH / uniform pick
+void oracle_light_sampler_table(const OracleScene *s, float *q, float *p, int *alias) {
+    SceneView sv(*s);
+    for (int i = 0; i < s->nlights; ++i) {
+        if (s->light_sampler == 1) q[i] = sv.power.q[i], p[i] = sv.power.p[i], alias[i] = sv.power.alias[i];
+        else q[i] = 1, p[i] = float(s->nlights) / float(s->nlights + 0) / s->nlights, alias[i] = -1;
+    }
+}
+// PowerLightSampler's AliasTable over n <= 8 given light weights: the bins {q, p, alias} and
+// AliasTable::Sample for m draws
+void oracle_alias_table(int n, const float *w, float *q, float *p, int *alias, int m, const float *u, int *idx,
+                        float *pmf) {
+    PowerSampler ps;
+    ps.BuildFromWeights(std::vector<float>(w, w + n));
+    for (int i = 0; i < n; ++i) q[i] = ps.q[i], p[i] = ps.p[i], alias[i] = ps.alias[i];
+    for (int i = 0; i < m; ++i) idx[i] = ps.Sample(n, u[i], &pmf[i]);
+}
+// The light pick of SampleLd for n draws: index (-1: none) and PMF
+void oracle_light_pick(const OracleScene *s, int n, const float *u, int *idx, float *pmf) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        pmf[i] = 0;
+        if (s->light_sampler == 1) { idx[i] = sv.power.Sample(s->nlights, u[i], &pmf[i]); continue; }
+        const float pInfinite = float(s->nlights) / float(s->nlights + 0);
+        if (!(u[i] < pInfinite)) { idx[i] = -1; continue; }
+        idx[i] = std::min<int>(u[i] / pInfinite * s->nlights, s->nlights - 1);
+        pmf[i] = pInfinite / s->nlights;
+    }
 }
 
 // One pixel sample: L (4), lambda (4), pdf (4); returns number of tentative collisions.

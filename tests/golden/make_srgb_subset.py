@@ -1,11 +1,16 @@
-"""Generate tests/golden/srgb_table_subset.npz: the entries of pbrt's sRGB
+"""Generate tests/golden/srgb_table_subset.npz and srgb_table_subset_lights.npz: the entries of pbrt's sRGB
 RGBToSpectrumTable (as the reference's own cmd/rgb2spec_opt generates it: oracle/ref/Makefile
 -> oracle/_ref/srgb_table.inc) that the GPU image-light test's environment map touches,
 every other coefficient zero. The GPU box has no reference sources, so the GPU test reads
 this fixture; the conversion of that image through it is asserted identical to the full
 table's here, before the file is written.
 
-usage: python tests/golden/make_srgb_subset.py   (needs oracle/_ref/srgb_table.inc)
+srgb_table_subset_lights.npz holds the cells that the maps of tests/light_cases.py touch (one
+palette of eight colours; grey pixels need no cell), checked in the same way.
+
+usage: python tests/golden/make_srgb_subset.py [envmap] [lights]   (needs oracle/_ref/srgb_table.inc;
+       without an argument both fixtures are written; an .npz holds its time of writing, so write
+       only the one that changed)
 """
 import os
 import sys
@@ -17,6 +22,7 @@ sys.path.insert(0, ROOT)
 from acceleratedvolrenderer_amd.rgbspectrum import RGBToSpectrumTable  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "srgb_table_subset.npz")
+OUT_LIGHTS = os.path.join(ROOT, "tests", "golden", "srgb_table_subset_lights.npz")
 
 
 def envmap_image(res=32):
@@ -53,16 +59,33 @@ def touched(table, rgb):
     return mask
 
 
+def light_maps():
+    """The maps of tests/light_cases.py, by name."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import light_cases
+    return {name: light_cases.map_image(name) for name in light_cases.MAPS}
+
+
+def write_subset(full, images, out):
+    mask = np.zeros(full.coeffs.shape[:4], bool)
+    for img in images:
+        mask |= touched(full, img)
+    sub = RGBToSpectrumTable(full.z_nodes, np.where(mask[..., None], full.coeffs, np.float32(0)))
+    for img in images:
+        a, b = full.spectrum_coeffs(np.maximum(img, np.float32(0))), sub.spectrum_coeffs(np.maximum(img, np.float32(0)))
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "subset table changes the conversion"
+    np.savez_compressed(out, z_nodes=sub.z_nodes, coeffs=sub.coeffs)
+    print(f"{out}: {int(mask.sum())} of {mask.size} cells kept, {os.path.getsize(out)} bytes")
+
+
 def main():
     src = os.path.join(ROOT, "oracle", "_ref", "srgb_table.inc")
     full = RGBToSpectrumTable.load(src)
-    img = envmap_image()
-    mask = touched(full, img)
-    sub = RGBToSpectrumTable(full.z_nodes, np.where(mask[..., None], full.coeffs, np.float32(0)))
-    a, b = full.spectrum_coeffs(img), sub.spectrum_coeffs(img)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "subset table changes the conversion"
-    np.savez_compressed(OUT, z_nodes=sub.z_nodes, coeffs=sub.coeffs)
-    print(f"{OUT}: {int(mask.sum())} of {mask.size} cells kept, {os.path.getsize(OUT)} bytes")
+    which = sys.argv[1:] or ["envmap", "lights"]
+    if "envmap" in which:
+        write_subset(full, [envmap_image()], OUT)
+    if "lights" in which:
+        write_subset(full, list(light_maps().values()), OUT_LIGHTS)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,8 @@ def declared_symbols():
 def test_header_declares_the_boundary():
     syms = declared_symbols()
     for must in ("avr_context_create", "avr_medium_grid", "avr_lights", "avr_camera", "avr_film", "avr_render",
-                 "avr_film_read", "avr_last_error", "avr_last_pass_rays"):
+                 "avr_film_read", "avr_last_error", "avr_last_pass_rays", "avr_light_probe", "avr_light_pick",
+                 "avr_light_sampler_table"):
         assert must in syms
 
 
@@ -41,6 +42,14 @@ def test_errors_are_reported_not_raised():
     assert lib.avr_context_create(0, 0, None) != 0
     assert b"null" in lib.avr_last_error()
     assert lib.avr_render(None, 0, 1, 0, 5) != 0
+
+
+def test_light_readbacks_argument_errors_without_a_gpu():
+    lib = capi.load()
+    assert lib.avr_light_probe(None, 0, 0, None, None, None, None, None, None, None, None) != 0
+    assert b"avr_light_probe" in lib.avr_last_error()
+    assert lib.avr_light_pick(None, 0, None, None, None) != 0
+    assert lib.avr_light_sampler_table(None, None, None, None) != 0
 
 
 def test_film_reduce_argument_errors_without_a_gpu():

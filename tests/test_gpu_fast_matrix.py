@@ -5,8 +5,10 @@ GridMedium, no emission, no image light, box interface, RGBFilm). This module ru
 others: one named case per (medium kind, emission, gray, sampler, image light / power sampler,
 interface shape, film) family, built from the scene builders of the replay tests
 (tests/test_gpu_parity.py, test_gpu_sphere.py, test_gpu_kpaths_parked.py) on their small films,
-and two (grid-affine, cloud-affine) behind a rotation, a non-uniform scale and a box that is not
-the unit cube (tests/media_cases.py).
+two (grid-affine, cloud-affine) behind a rotation, a non-uniform scale and a box that is not
+the unit cube (tests/media_cases.py), and three of the light stage's cases (tests/light_cases.py: two
+surviving map pixels under a mirrored transform, two image lights, eight lights), which keep their
+full depth: the corners' variance does not defeat the correlated-film criterion (err / noise 0.204).
 Each case names, by hand, the instantiation `avr_last_kernel` must report; avr_last_kernel prints
 the flags and not the table slot, so every case also checks what the launched kernel computed:
 
@@ -81,6 +83,9 @@ relative pdf error):
   spectral                 0.125      +1.03      0.9051  1.7e-04 3.2e-04 6.3e-01  -                  0.0e+00     0.0e+00
   grid-affine              0.182      -1.93      0.9509  0.0e+00 0.0e+00 5.1e-01  -                  6.1e-05     5.0e-07
   cloud-affine             0.056      -0.65      0.9935  0.0e+00 0.0e+00 3.5e-07  -                  6.1e-05     5.0e-07
+  lights-corners-mirror    0.204      +0.29      0.8509  0.0e+00 2.1e-01 2.0e+00  0.9969 at depth 1  6.1e-05     4.8e-07
+  lights-two-images        0.042      -0.68      0.8428  0.0e+00 1.7e-01 1.3e+00  0.9962 at depth 1  6.1e-05     4.8e-07
+  lights-eight             0.150      +0.92      0.8912  0.0e+00 1.8e-02 7.8e-01  0.9971 at depth 1  6.1e-05     4.8e-07
 
   spectral film: bucket sums rel RMS 7.2e-02 against a two-seed noise of 6.5e-01.
   White furnace (grid, homogeneous, NanoVDB): max |L - 1| = 0 over 4096 samples each.
@@ -97,6 +102,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import light_cases   # noqa: E402
 import media_cases   # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -325,6 +331,14 @@ CASES = [
     # a rotation, a non-uniform scale and a box of three different extents (tests/media_cases.py)
     Case("grid-affine", lambda pixelsamples=None: _affine("gray"), 6, "k_paths<false, true, 0, 0, false, true>"),
     Case("cloud-affine", lambda pixelsamples=None: _affine("cloud"), 6, "k_paths<false, true, 0, 1, false, true>"),
+    # the light stage's cases (tests/light_cases.py): two surviving pixels under a mirrored transform,
+    # two image lights, eight lights with the image light in the last slot
+    Case("lights-corners-mirror", lambda pixelsamples=None: light_cases.scene_for("corners-5+mirror"), 6,
+         "k_paths<false, true, 0, 0, true, true>", close_depth=1),
+    Case("lights-two-images", lambda pixelsamples=None: light_cases.scene_for("two-images"), 6,
+         "k_paths<false, true, 0, 0, true, true>", close_depth=1),
+    Case("lights-eight", lambda pixelsamples=None: light_cases.scene_for("eight"), 6,
+         "k_paths<false, true, 0, 0, true, true>", close_depth=1),
 ]
 BY_ID = {c.id: c for c in CASES}
 IDS = [c.id for c in CASES]
