@@ -7,7 +7,7 @@ queues with wave64 ballot compaction, RGBFilm accumulation — behind the C-ABI 
 include/avr.h. See DESIGN.md.
 """
 from . import spectra, transform
-from .scene import (GridMedium, DistantLight, UniformInfiniteLight, ImageInfiniteLight, OrthographicCamera, PerspectiveCamera, SphericalCamera, RGBFilm, SpectralFilm, spectral_image, GBufferFilm, gbuffer_image,
+from .scene import (GridMedium, DistantLight, UniformInfiniteLight, ImageInfiniteLight, PointLight, SpotLight, OrthographicCamera, PerspectiveCamera, SphericalCamera, RGBFilm, SpectralFilm, spectral_image, GBufferFilm, gbuffer_image,
                     Scene, film_rgb, HomogeneousMedium, CloudMedium, NanoVDBMedium, RGBGridMedium, BoxFilter, GaussianFilter,
                     IndependentSampler, ZSobolSampler)
 from .vdb import NanoVDBGrid
@@ -23,5 +23,5 @@ from .graph import GraphIntegrator, IntegrationAnalyzer
 __all__ = ["spectra", "transform", "GridMedium", "DistantLight", "UniformInfiniteLight", "OrthographicCamera",
            "PerspectiveCamera", "SphericalCamera", "RGBFilm", "Scene", "film_rgb", "VolPathIntegrator", "shard_samples",
            "INTEGRATOR_NAMES", "capi", "scenes", "HomogeneousMedium", "CloudMedium", "NanoVDBMedium", "NanoVDBGrid", "RGBGridMedium", "RGBToSpectrumTable",
-           "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler",
+           "SpectralFilm", "spectral_image", "GBufferFilm", "gbuffer_image", "ImageInfiniteLight", "PointLight", "SpotLight", "BoxFilter", "GaussianFilter", "IndependentSampler", "ZSobolSampler",
            "graph", "graph_io", "GraphIndex", "GraphUniform", "GraphIntegrator", "IntegrationAnalyzer"]

@@ -128,6 +128,12 @@ SIGNATURES = {
     "avr_light_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [c_float_p] * 8),
     "avr_light_pick": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p]),
     "avr_light_sampler_table": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_int_p]),
+    "avr_light_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, ctypes.c_float,
+                                       ctypes.c_float]),
+    "avr_light_probe_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [c_float_p] * 7),
+    "avr_light_pick_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, c_int_p, c_float_p]),
+    "avr_light_bvh": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_int_p, c_int_p,
+                                     c_float_p, c_int_p]),
     "avr_set_dda_budget": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_grid_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_grid_layout_active": (ctypes.c_int, [ctypes.c_void_p]),
@@ -435,7 +441,8 @@ class Context:
         _check(self.lib.avr_set_dda_budget(self.h, int(cells)))
 
     def set_light_sampler(self, kind):
-        """0: "bvh" / "uniform" (identical for infinite lights); 1: "power" (avr_light_sampler)."""
+        """0: "bvh" (pbrt's BVHLightSampler); 1: "power"; 2: "uniform" — 0 and 2 are the same pick for
+        lists of infinite lights (avr_light_sampler)."""
         _check(self.lib.avr_light_sampler(self.h, int(kind)))
 
     def light_probe(self, index, u2, w3, lambda4):
@@ -459,6 +466,44 @@ class Context:
         idx, pmf = np.zeros(len(u), np.int32), np.zeros(len(u), np.float32)
         _check(self.lib.avr_light_pick(self.h, len(u), _fp(u), idx.ctypes.data_as(c_int_p), _fp(pmf)))
         return idx, pmf
+
+    def light_probe_at(self, index, u2, p3, lambda4):
+        """avr_light_probe_at of light `index`: (wi (n, 3), pdf of the sample (n), Ls (n, 4), distance (n))
+        of SampleLi at n render-space reference points."""
+        u2 = np.ascontiguousarray(u2, np.float32).reshape(-1, 2)
+        p3 = np.ascontiguousarray(p3, np.float32).reshape(-1, 3)
+        lam = np.ascontiguousarray(lambda4, np.float32).reshape(-1, 4)
+        n = len(p3)
+        if len(u2) != n or len(lam) != n:
+            raise ValueError("light_probe_at: u2, p3 and lambda4 need one row per probe")
+        wi, ps, Ls, r = (np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 4), np.float32),
+                         np.zeros(n, np.float32))
+        _check(self.lib.avr_light_probe_at(self.h, int(index), n, _fp(u2), _fp(p3), _fp(lam), _fp(wi), _fp(ps), _fp(Ls),
+                                           _fp(r)))
+        return wi, ps, Ls, r
+
+    def light_pick_at(self, u, p3):
+        """avr_light_pick_at: (index (-1: none), pmf) of the light sampler's pick per draw u at point p."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1)
+        p3 = np.ascontiguousarray(p3, np.float32).reshape(-1, 3)
+        if len(p3) != len(u):
+            raise ValueError("light_pick_at: one point per draw")
+        idx, pmf = np.zeros(len(u), np.int32), np.zeros(len(u), np.float32)
+        _check(self.lib.avr_light_pick_at(self.h, len(u), _fp(u), _fp(p3), idx.ctypes.data_as(c_int_p), _fp(pmf)))
+        return idx, pmf
+
+    def light_bvh(self):
+        """avr_light_bvh: dict(phi, w, qcos, qb, link, leaf) per node, all_bounds (pMin, pMax) and n_infinite."""
+        ip = lambda a: a.ctypes.data_as(c_int_p)   # noqa: E731
+        nn, ninf = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        phi, w, qcos, qb = np.zeros(15, np.float32), np.zeros((15, 3), np.float32), np.zeros((15, 2), np.int32), np.zeros(
+            (15, 2, 3), np.int32)
+        link, leaf, allb = np.zeros(15, np.int32), np.zeros(15, np.int32), np.zeros(6, np.float32)
+        _check(self.lib.avr_light_bvh(self.h, ip(nn), _fp(phi), _fp(w), ip(qcos), ip(qb), ip(link), ip(leaf), _fp(allb),
+                                      ip(ninf)))
+        k = int(nn[0])
+        return dict(phi=phi[:k], w=w[:k], qcos=qcos[:k], qb=qb[:k], link=link[:k], leaf=leaf[:k].astype(bool),
+                    all_bounds=allb, n_infinite=int(ninf[0]))
 
     def light_sampler_table(self, n):
         """avr_light_sampler_table of the n lights: (q, p, alias)."""
@@ -600,6 +645,11 @@ class Context:
                         f32(scene.light_lfr[i])]
                 self._keep += arrs
                 _check(self.lib.avr_light_image(self.h, i, int(light.res), *[_fp(a) for a in arrs]))
+            elif light.type_id in (3, 4):
+                arrs = [f32(scene.light_rfl[i]), f32(scene.light_lfr[i])]
+                self._keep += arrs
+                _check(self.lib.avr_light_local(self.h, i, _fp(arrs[0]), _fp(arrs[1]), float(light.cos_falloff_start),
+                                                float(light.cos_falloff_end)))
         self.set_camera(scene)
         film = scene.film
         _check(self.lib.avr_film(self.h, film.width, film.height, _fp(f32(film.filter_radius)), _fp(f32(film.sensor)),

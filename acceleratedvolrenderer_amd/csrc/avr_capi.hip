@@ -231,6 +231,14 @@ struct avr_context {
     int light_sampler = 0;
     void *d_light_img[avr::kMaxLights] = {};
     int n_image_lights = 0;
+    // PointLight / SpotLight: how many the list holds, which have their avr_light_local, their
+    // renderFromLight (4x4; the device record keeps the position and lightFromRender's 3x3), the
+    // host copy of the lights' tables (Phi and the bounds' I->MaxValue()) and the light BVH
+    int n_local_lights = 0;
+    bool local_ok[avr::kMaxLights] = {};
+    float h_rfl[avr::kMaxLights][16] = {};
+    std::vector<float> h_lightL;
+    avr::ll::Tree h_tree{};
     // film image / --mse-reference-image state
     float *d_image = nullptr, *d_reference = nullptr;
     double *d_metric = nullptr;      // kMetricBlocks * kMetricSlots partials + kMetricSlots totals
@@ -1517,6 +1525,21 @@ static float phi_table_light(int type, const float *L, float scale, float r) {
     }
     return phi_weight(phi, pdf);
 }
+// PointLight::Phi (lights.cpp:164-166): 4 * Pi * scale * I(lambda); SpotLight::Phi
+// (lights.cpp:1365-1368): scale * I(lambda) * 2 * Pi * ((1 - cosStart) + (cosStart - cosEnd) / 2)
+static float phi_local_light(int type, const float *I, float scale, float cosStart, float cosEnd) {
+    avr::Spec pdf;
+    const avr::Spec l = visible_half_lambda(&pdf);
+    const avr::Spec Il = avr::sample_table(I, avr::lambda_index(l));
+    avr::Spec phi;
+    if (type == avr::ll::kPoint) {
+        const float k = 4 * avr::kPi * scale;
+        phi = avr::Spec{k * Il.v0, k * Il.v1, k * Il.v2, k * Il.v3};
+    } else {
+        phi = Il * scale * 2.f * avr::kPi * ((1 - cosStart) + (cosStart - cosEnd) / 2);
+    }
+    return phi_weight(phi, pdf);
+}
 // RGBSigmoidPolynomial (util/color.h:332-365), the host twin of the device's rsp_eval
 static float rsp_host(float c0, float c1, float c2, float lambda) {
     const float x = std::fma(lambda, std::fma(lambda, c0, c1), c2);
@@ -1571,8 +1594,33 @@ static int update_light_sampler(avr_context *c) {
     const int n = c->lights.n;
     bool ready = c->light_sampler == 1 && n > 0;
     for (int i = 0; i < n && ready; ++i) ready = c->phi_ok[i];
-    c->lights.power = ready ? 1 : 0;
+    // lists of infinite lights: "bvh" and "uniform" are the one pick every kernel evaluates; with
+    // a local light, BVHLightSampler's traversal or UniformLightSampler over the whole list
+    const int plain = c->n_local_lights == 0 ? avr::kPickInfinite
+                                             : (c->light_sampler == 2 ? avr::kPickUniform : avr::kPickBvh);
+    c->lights.mode = ready ? avr::kPickPower : plain;
     if (n == 0) return AVR_OK;
+    // BVHLightSampler's constructor over the list, once every local light has its transform
+    bool localReady = c->n_local_lights > 0;
+    for (int i = 0; i < n && localReady; ++i) localReady = c->h_lights[i].type < avr::ll::kPoint || c->local_ok[i];
+    c->h_tree = avr::ll::Tree{};
+    if (localReady) {
+        bool bounded[avr::kMaxLights] = {};
+        avr::ll::LightBounds lb[avr::kMaxLights];
+        for (int i = 0; i < n; ++i) {
+            const avr::DevLight &L = c->h_lights[i];
+            bounded[i] = L.type >= avr::ll::kPoint;
+            if (!bounded[i]) continue;
+            const float *I = c->h_lightL.data() + (size_t)i * avr::kNTable;
+            const float maxI = *std::max_element(I, I + avr::kNTable);   // DenselySampledSpectrum::MaxValue
+            lb[i] = avr::ll::light_bounds(L.type, c->h_rfl[i], L.scale, maxI, L.cos_start, L.cos_end);
+        }
+        avr::ll::build_tree(n, bounded, lb, &c->h_tree);
+    }
+    if (c->d_lights) {
+        HIP_TRY(hipMemcpyAsync(c->d_lights + avr::kMaxLights, &c->h_tree, sizeof(c->h_tree), hipMemcpyHostToDevice,
+                               c->stream));
+    }
     float q[avr::kMaxLights], pm[avr::kMaxLights];
     int al[avr::kMaxLights];
     if (ready) {
@@ -1607,14 +1655,16 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
     if (rc) return rc;
     avr::DevLight h[avr::kMaxLights] = {};
     for (int i = 0; i < n; ++i) {
-        if (types[i] < 0 || types[i] > 2)
-            return fail(AVR_ERR_ARG, "light type must be 0 (distant), 1 (uniform infinite) or 2 (image infinite)");
+        if (types[i] < 0 || types[i] > 4)
+            return fail(AVR_ERR_ARG, "light type must be 0 (distant), 1 (uniform infinite), 2 (image infinite), "
+                                     "3 (point) or 4 (spot)");
         h[i].type = types[i];
         for (int k = 0; k < 3; ++k) h[i].w[k] = w3[3 * i + k];
         h[i].L = c->d_lightL + (size_t)i * avr::kNTable;
         h[i].scale = scale[i];
     }
-    if (!c->d_lights) HIP_TRY(dalloc(&c->d_lights, avr::kMaxLights));
+    // (the records, and behind them the light BVH: light_tree())
+    if (!c->d_lights) HIP_TRY(dalloc(&c->d_lights, avr::kMaxLights + avr::kLightTreeSlots));
     HIP_TRY(hipMemcpyAsync(c->d_lights, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (auto &b : c->d_light_img) if (b) (void)hipFree(b), b = nullptr;
@@ -1624,9 +1674,14 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
     c->lights.list = c->d_lights;
     c->lights.scene_radius = scene_radius;
     c->n_image_lights = 0;
+    c->n_local_lights = 0;
     for (int i = 0; i < n; ++i) c->n_image_lights += types[i] == 2 ? 1 : 0;
+    for (int i = 0; i < n; ++i) c->n_local_lights += types[i] >= avr::ll::kPoint ? 1 : 0;
+    c->h_lightL.assign(L, L + (size_t)n * avr::kNTable);
     for (int i = 0; i < avr::kMaxLights; ++i) {
-        c->phi_ok[i] = i < n && types[i] != 2;
+        c->local_ok[i] = false;
+        // an image light's Phi needs its image, a local light's its cone (avr_light_local)
+        c->phi_ok[i] = i < n && types[i] < 2;
         c->h_phi[i] = c->phi_ok[i] ? phi_table_light(types[i], L + (size_t)i * avr::kNTable, scale[i], scene_radius) : 0.f;
     }
     return update_light_sampler(c);
@@ -1634,7 +1689,7 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
 
 int avr_light_sampler(avr_context *c, int kind) {
     AVR_QUIESCE(c);
-    if (!c || (kind != 0 && kind != 1)) return fail(AVR_ERR_ARG, "light sampler must be 0 (bvh / uniform) or 1 (power)");
+    if (!c || kind < 0 || kind > 2) return fail(AVR_ERR_ARG, "light sampler must be 0 (bvh), 1 (power) or 2 (uniform)");
     HIP_TRY(hipSetDevice(c->device));
     c->light_sampler = kind;
     return update_light_sampler(c);
@@ -1702,10 +1757,41 @@ int avr_light_image(avr_context *c, int index, int res, const float *pixel_coeff
     return update_light_sampler(c);
 }
 
+// PointLight / SpotLight: the transforms and the cone of a type-3 / type-4 light
+int avr_light_local(avr_context *c, int index, const float render_from_light[16], const float light_from_render[16],
+                    float cos_falloff_start, float cos_falloff_end) {
+    AVR_QUIESCE(c);
+    if (!c || index < 0 || index >= c->lights.n || c->h_lights[index].type < avr::ll::kPoint)
+        return fail(AVR_ERR_ARG, "avr_light_local: index must name a type-3 or type-4 light of the last avr_lights call");
+    if (!render_from_light || !light_from_render) return fail(AVR_ERR_ARG, "avr_light_local: null transform");
+    HIP_TRY(hipSetDevice(c->device));
+    avr::DevLight &L = c->h_lights[index];
+    for (int i = 0; i < 16; ++i) c->h_rfl[index][i] = render_from_light[i];
+    avr::ll::light_position(render_from_light, L.w);
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) {
+            L.rfl[3 * r + k] = render_from_light[4 * r + k];
+            L.lfr[3 * r + k] = light_from_render[4 * r + k];
+        }
+    L.cos_start = cos_falloff_start;
+    L.cos_end = cos_falloff_end;
+    c->local_ok[index] = true;
+    c->h_phi[index] = phi_local_light(L.type, c->h_lightL.data() + (size_t)index * avr::kNTable, L.scale, L.cos_start,
+                                      L.cos_end);
+    c->phi_ok[index] = true;
+    return update_light_sampler(c);
+}
+
 // Whether every type-2 light of the list has its image (avr_light_image)
 static bool image_lights_complete(const avr_context *c) {
     for (int i = 0; i < c->lights.n; ++i)
         if (c->h_lights[i].type == 2 && !c->d_light_img[i]) return false;
+    return true;
+}
+// Whether every type-3 / type-4 light of the list has its transform (avr_light_local)
+static bool local_lights_complete(const avr_context *c) {
+    for (int i = 0; i < c->lights.n; ++i)
+        if (c->h_lights[i].type >= avr::ll::kPoint && !c->local_ok[i]) return false;
     return true;
 }
 
@@ -1715,6 +1801,7 @@ int avr_light_probe(avr_context *c, int index, int n, const float *u2, const flo
     if (!c || index < 0 || index >= c->lights.n) return fail(AVR_ERR_ARG, "avr_light_probe: index must name a light");
     if (n < 0 || n > 1 << 20 || (n > 0 && (!u2 || !w3 || !lambda4))) return fail(AVR_ERR_ARG, "avr_light_probe: bad probe arrays");
     if (!image_lights_complete(c)) return fail(AVR_ERR_STATE, "image light without avr_light_image");
+    if (!local_lights_complete(c)) return fail(AVR_ERR_STATE, "point or spot light without avr_light_local");
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)n;
@@ -1741,21 +1828,23 @@ int avr_light_probe(avr_context *c, int index, int n, const float *u2, const flo
     return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
 }
 
-int avr_light_pick(avr_context *c, int n, const float *u, int *idx, float *pmf) {
-    AVR_QUIESCE(c);
-    if (!c || n < 0 || n > 1 << 20 || (n > 0 && (!u || !idx || !pmf))) return fail(AVR_ERR_ARG, "avr_light_pick: bad arrays");
-    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+// avr_light_pick (p3 null: the origin) and avr_light_pick_at
+static int light_pick_impl(avr_context *c, int n, const float *u, const float *p3, int *idx, float *pmf) {
+    if (c->light_sampler == 1 && c->lights.n > 0 && c->lights.mode != avr::kPickPower)
         return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
+    if (!local_lights_complete(c)) return fail(AVR_ERR_STATE, "point or spot light without avr_light_local");
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)n;
     float *d = nullptr;
-    HIP_TRY(dalloc(&d, N * 3));
-    float *du = d, *dp = d + N;
+    HIP_TRY(dalloc(&d, N * 6));
+    float *du = d, *dp = d + N, *dpt = d + 3 * N;
     int *di = (int *)(d + 2 * N);
     hipError_t e = hipMemcpyAsync(du, u, N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && p3) e = hipMemcpyAsync(dpt, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_light_pick, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, n, du, di, dp);
+        hipLaunchKernelGGL(avr::k_light_pick, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, n, du,
+                           p3 ? dpt : nullptr, di, dp);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(idx, di, N * sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -1765,10 +1854,76 @@ int avr_light_pick(avr_context *c, int n, const float *u, int *idx, float *pmf) 
     (void)hipFree(d);
     return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
 }
+int avr_light_pick(avr_context *c, int n, const float *u, int *idx, float *pmf) {
+    AVR_QUIESCE(c);
+    if (!c || n < 0 || n > 1 << 20 || (n > 0 && (!u || !idx || !pmf))) return fail(AVR_ERR_ARG, "avr_light_pick: bad arrays");
+    return light_pick_impl(c, n, u, nullptr, idx, pmf);
+}
+int avr_light_pick_at(avr_context *c, int n, const float *u, const float *p3, int *idx, float *pmf) {
+    AVR_QUIESCE(c);
+    if (!c || n < 0 || n > 1 << 20 || (n > 0 && (!u || !p3 || !idx || !pmf)))
+        return fail(AVR_ERR_ARG, "avr_light_pick_at: bad arrays");
+    return light_pick_impl(c, n, u, p3, idx, pmf);
+}
+
+int avr_light_probe_at(avr_context *c, int index, int n, const float *u2, const float *p3, const float *lambda4,
+                       float *wi3, float *pdf_sample, float *Ls4, float *dist) {
+    AVR_QUIESCE(c);
+    if (!c || index < 0 || index >= c->lights.n) return fail(AVR_ERR_ARG, "avr_light_probe_at: index must name a light");
+    if (n < 0 || n > 1 << 20 || (n > 0 && (!u2 || !p3 || !lambda4)))
+        return fail(AVR_ERR_ARG, "avr_light_probe_at: bad probe arrays");
+    if (!image_lights_complete(c)) return fail(AVR_ERR_STATE, "image light without avr_light_image");
+    if (!local_lights_complete(c)) return fail(AVR_ERR_STATE, "point or spot light without avr_light_local");
+    if (n == 0) return AVR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t N = (size_t)n;
+    float *d = nullptr;
+    HIP_TRY(dalloc(&d, N * 18));
+    float *du = d, *dp = d + 2 * N, *dl = d + 5 * N, *dwi = d + 9 * N, *dps = d + 12 * N, *dLs = d + 13 * N, *dr = d + 17 * N;
+    hipError_t e = hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(avr::k_light_probe_at, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du,
+                           dp, dl, dwi, dps, dLs, dr);
+        e = hipGetLastError();
+    }
+    const struct { float *host; const float *dev; size_t k; } outs[] = {{wi3, dwi, 3}, {pdf_sample, dps, 1}, {Ls4, dLs, 4},
+                                                                       {dist, dr, 1}};
+    for (const auto &o : outs)
+        if (e == hipSuccess && o.host)
+            e = hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+}
+
+int avr_light_bvh(avr_context *c, int *n_nodes, float *phi, float *w3, int *qcos, int *qb, int *link, int *leaf,
+                  float all_bounds[6], int *n_infinite) {
+    if (!c) return fail(AVR_ERR_ARG, "avr_light_bvh: null context");
+    if (!local_lights_complete(c)) return fail(AVR_ERR_STATE, "point or spot light without avr_light_local");
+    const avr::ll::Tree &t = c->h_tree;
+    if (n_nodes) *n_nodes = t.nNodes;
+    if (n_infinite) *n_infinite = c->n_local_lights > 0 ? t.nInf : c->lights.n;
+    for (int i = 0; i < t.nNodes; ++i) {
+        const avr::ll::Node &nd = t.nodes[i];
+        if (phi) phi[i] = nd.phi;
+        if (w3) avr::ll::oct_decode(nd.wx, nd.wy, w3 + 3 * i);
+        if (qcos) qcos[2 * i] = (int)nd.q_cos_o(), qcos[2 * i + 1] = (int)nd.q_cos_e();
+        if (qb)
+            for (int k = 0; k < 6; ++k) qb[6 * i + k] = nd.qb[k / 3][k % 3];
+        if (link) link[i] = (int)nd.index();
+        if (leaf) leaf[i] = nd.leaf() ? 1 : 0;
+    }
+    if (all_bounds)
+        for (int k = 0; k < 6; ++k) all_bounds[k] = t.allb[k];
+    return AVR_OK;
+}
 
 int avr_light_sampler_table(avr_context *c, float *q, float *p, int *alias) {
     if (!c || (c->lights.n > 0 && (!q || !p || !alias))) return fail(AVR_ERR_ARG, "avr_light_sampler_table: null arg");
-    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+    if (c->light_sampler == 1 && c->lights.n > 0 && c->lights.mode != avr::kPickPower)
         return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
     for (int i = 0; i < c->lights.n; ++i) {
         q[i] = c->h_lights[i].aq;

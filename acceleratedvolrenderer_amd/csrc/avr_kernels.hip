@@ -22,6 +22,7 @@
 #include "avr_vdb.h"
 #include "avr_envmap.h"
 #include "avr_camera.h"
+#include "avr_local_light.h"
 #include "avr_flip.h"
 #include "avr_boundary.h"
 
@@ -107,8 +108,8 @@ struct DevMedium {
 
 constexpr int kMaxLights = 8;
 struct DevLight {
-    int type;                         // 0 distant (delta), 1 uniform infinite, 2 image infinite
-    float w[3];                       // render-space direction towards a distant light
+    int type;                         // 0 distant (delta), 1 uniform infinite, 2 image infinite, 3 point, 4 spot
+    float w[3];                       // render-space direction towards a distant light; a local light's position
     float scale;
     const float *L;                   // 471-entry table
     // type 2, ImageInfiniteLight (lights.h:552-640): res x res equal-area image, per pixel the
@@ -123,13 +124,29 @@ struct DevLight {
     // (util/sampling.h:822-826) over the lights' Phi; p is the light's PMF
     float aq, ap;
     int alias;
+    // types 3 and 4, PointLight and SpotLight (lights.h:191-236, 741-797): w holds
+    // renderFromLight(0, 0, 0), lfr lightFromRender's 3x3 (avr_light_local keeps both 4x4s on the
+    // host for the bounds); the spot light's falloff cosines (a point light's cone is everything)
+    float cos_start, cos_end;
 };
+// DevLights::mode. The list of infinite lights alone under "bvh" or "uniform" is kPickInfinite,
+// what every k_paths instantiation evaluates; the other three run in the general ones.
+constexpr int kPickInfinite = 0, kPickPower = 1, kPickBvh = 2, kPickUniform = 3;
 struct DevLights {
     int n;
-    const DevLight *list;             // device array (indexed by the sampled light)
+    // device array (indexed by the sampled light): kMaxLights records, and behind them the light
+    // BVH (ll::Tree, light_tree()) that kPickBvh traverses
+    const DevLight *list;
     float scene_radius;
-    int power;                        // 1: PowerLightSampler; 0: BVH / uniform (infinite lights)
+    int mode;                         // kPickInfinite, kPickPower (PowerLightSampler), kPickBvh, kPickUniform
 };
+// The light BVH lives in the device array behind the records: 544 bytes that every lane reads at
+// its own node, so neither kernel arguments (k_paths keeps its own in registers) nor LDS (the
+// general instantiations' blocks are sized by it) would hold it better; it stays in L2 / L1.
+constexpr int kLightTreeSlots = (int)((sizeof(ll::Tree) + sizeof(DevLight) - 1) / sizeof(DevLight));
+__host__ __device__ __forceinline__ const ll::Tree &light_tree(const DevLights &ls) {
+    return *reinterpret_cast<const ll::Tree *>(ls.list + kMaxLights);
+}
 
 // VolPath's light pick among infinite lights: BVHLightSampler's infinite branch and
 // UniformLightSampler (lightsamplers.h:266-277, 35-50): index min(u / pInf * n, n - 1), PMF
@@ -141,7 +158,7 @@ struct DevLights {
 template <bool kGeneral>
 __device__ __forceinline__ int light_pick(const DevLights &ls, float u, float *pmf) {
     const int nl = ls.n;
-    if (kGeneral && ls.power) {
+    if (kGeneral && ls.mode == kPickPower) {
         int offset = (int)(u * nl);
         offset = offset < nl - 1 ? offset : nl - 1;
         const float up = fminf_(u * nl - offset, kOneMinusEpsilon);
@@ -160,8 +177,40 @@ __device__ __forceinline__ int light_pick(const DevLights &ls, float u, float *p
 // the sampler's PMF of light k (PowerLightSampler::PMF, lightsamplers.h:78-82; BVH: pInf / n)
 template <bool kGeneral>
 __device__ __forceinline__ float light_pmf(const DevLights &ls, int k) {
-    if (kGeneral && ls.power) return ls.list[k].ap;
+    if (kGeneral && ls.mode == kPickPower) return ls.list[k].ap;
+    if (kGeneral && ls.mode == kPickBvh) return ll::bvh_pmf_infinite(light_tree(ls));
+    if (kGeneral && ls.mode == kPickUniform) return 1.f / ls.n;
     return float(ls.n) / float(ls.n + 0) / ls.n;
+}
+// The general light pick at the scatter point p (the wavefront kernels and k_paths' general
+// instantiations): light_pick<true> for lists of infinite lights and the power sampler; with a
+// local light in the list BVHLightSampler::Sample(ctx, u) (lightsamplers.h:266-320) or
+// UniformLightSampler::Sample over the whole list (lightsamplers.h:33-38)
+__device__ __forceinline__ int light_pick_at(const DevLights &ls, V3 p, float u, float *pmf) {
+    if (ls.mode == kPickBvh) {
+        const float pp[3] = {p.x, p.y, p.z};
+        return ll::bvh_sample(light_tree(ls), pp, u, pmf);
+    }
+    if (ls.mode == kPickUniform) {
+        const int nl = ls.n;
+        int idx = (int)(u * nl);
+        idx = idx < nl - 1 ? idx : nl - 1;
+        *pmf = 1.f / nl;
+        return idx;
+    }
+    return light_pick<true>(ls, u, pmf);
+}
+// PointLight / SpotLight::SampleLi at p (avr_local_light.h): wi, the light's position and
+// Li = falloff * scale * I(lambda) / r^2 (black: no sample)
+__device__ __forceinline__ Spec local_light_li(const DevLight &lt, V3 p, const LambdaIdx &li, V3 *wi, V3 *pLight) {
+    const float pp[3] = {p.x, p.y, p.z};
+    float w[3], dist2, falloff;
+    ll::sample_li(lt.type, lt.w, lt.lfr, lt.cos_start, lt.cos_end, pp, w, &dist2, &falloff);
+    *wi = {w[0], w[1], w[2]};
+    *pLight = {lt.w[0], lt.w[1], lt.w[2]};
+    const Spec I = sample_table(lt.L, li);
+    return {ll::li_channel(lt.type, falloff, lt.scale, I.v0, dist2), ll::li_channel(lt.type, falloff, lt.scale, I.v1, dist2),
+            ll::li_channel(lt.type, falloff, lt.scale, I.v2, dist2), ll::li_channel(lt.type, falloff, lt.scale, I.v3, dist2)};
 }
 
 // k_paths' copy of what its handlers read per lane of the first kLdsLights lights' records, with
@@ -1680,15 +1729,21 @@ __global__ void __launch_bounds__(256) k_medium(Params P) {
                 const int nl = P.lights.n;
                 if (nl > 0) {
                     float pmf = 0.f;
-                    const int idx = light_pick<true>(P.lights, ul, &pmf);
+                    const int idx = light_pick_at(P.lights, pScatter, ul, &pmf);
                     if (idx >= 0) {
                         const DevLight &lt = P.lights.list[idx];
-                        if (lt.type == 0 || lt.type == 2) {
+                        if (lt.type == 0 || lt.type >= 2) {
                             V3 wi = {lt.w[0], lt.w[1], lt.w[2]};
                             Spec Ls;
                             float lsPdf = 1.f;
+                            // the shadow ray's end: 2 x sceneRadius along wi, or the local light itself
+                            bool local = false;
+                            V3 pLocal = {0.f, 0.f, 0.f};
                             if (lt.type == 0) {
                                 Ls = sample_table(lt.L, li) * lt.scale;
+                            } else if (lt.type >= ll::kPoint) {   // PointLight / SpotLight::SampleLi
+                                local = true;
+                                Ls = local_light_li(lt, pScatter, li, &wi, &pLocal);
                             } else {   // ImageInfiniteLight::SampleLi, compensated distribution (lights.h:588-613)
                                 float su, sv;
                                 env::distrib_sample(lt.dist, uL0, uL1, &su, &sv, &lsPdf);
@@ -1703,7 +1758,7 @@ __global__ void __launch_bounds__(256) k_medium(Params P) {
                                 }
                             }
                             if (Ls.nonzero() && lsPdf != 0) {
-                                const V3 pOut = pScatter + wi * (2 * P.lights.scene_radius);
+                                const V3 pOut = local ? pLocal : pScatter + wi * (2 * P.lights.scene_radius);
                                 const float p_l = pmf * lsPdf;
                                 const float fval = hg_eval(dot(wo, wi), P.med.g);
                                 const Spec f_hat = Spec::c(fval);
@@ -1713,7 +1768,7 @@ __global__ void __launch_bounds__(256) k_medium(Params P) {
                                     shBF = to4(beta * f_hat);
                                     shLs = to4(Ls);
                                     shRP = to4(r_u);
-                                    shPdfs = make_float2(p_l, lt.type == 0 ? -1.f : fval);
+                                    shPdfs = make_float2(p_l, lt.type != 2 ? -1.f : fval);
                                     shadowSpawned = true;
                                 }
                             }
@@ -1743,7 +1798,7 @@ __global__ void __launch_bounds__(256) k_medium(Params P) {
                 // escaped: infinite lights (integrators.cpp:1090-1107)
                 for (int k = 0; k < P.lights.n; ++k) {
                     const DevLight &lt = P.lights.list[k];
-                    if (lt.type == 0) continue;
+                    if (lt.type == 0 || lt.type >= ll::kPoint) continue;   // delta lights: nothing at infinity
                     float eu = 0, ev = 0;
                     const Spec Le = lt.type == 1 ? sample_table(lt.L, li) * lt.scale : image_le_dir(lt, d, lamv, &eu, &ev);
                     if (!Le.nonzero()) continue;
@@ -2498,10 +2553,34 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 const int nl = P.lights.n;
                 if (nl > 0) {
                     float pmf = 0.f;
-                    const int idx = light_pick_staged<kStaged>(P.lights, s_lt, ul, &pmf);
+                    int idx;
+                    if constexpr (kImage) idx = light_pick_at(P.lights, po, ul, &pmf);
+                    else idx = light_pick_staged<kStaged>(P.lights, s_lt, ul, &pmf);
                     if (idx >= 0) {
                         const int ltype = light_type<kStaged>(P.lights, s_lt, idx);
-                        if (kImage && ltype == 2) {
+                        if (kImage && ltype >= ll::kPoint) {
+                            // PointLight / SpotLight::SampleLi at the scatter point; the shadow ray
+                            // is SpawnRayTo(pLight): d = pLight - po (a medium interaction has no
+                            // offset). The pick's PMF depends on po: parked beside Ls and f_hat
+                            V3 wi, pL;
+                            const Spec Ls = local_light_li(P.lights.list[idx], po, lambda_index(lam), &wi, &pL);
+                            const float fval = hg_eval_c(dot(wo, wi), m.hg);
+                            if (Ls.nonzero() && fval != 0) {
+                                s_ls[threadIdx.x] = to4(Ls);
+                                s_fhat[threadIdx.x] = fval;
+                                s_img[threadIdx.x] = make_float4(0.f, 0.f, pmf, fval);
+                                const V3 d = pL - po;
+                                light = idx;
+                                T_ray = sr_l = sr_u = sconst<S>(1.f);
+                                seqA = hash_3u32(f2u(po.x), f2u(po.y), f2u(po.z));
+                                seqB = hash_3u32(f2u(d.x), f2u(d.y), f2u(d.z));
+                                sd = d;
+                                segPending = true;
+                                mode = M_SHADOW;
+                                ev = EV_NONE;
+                                AVR_COUNT(nShadow, 4);
+                            }
+                        } else if (kImage && ltype == 2) {
                             const DevLight &lt = P.lights.list[idx];
                             // ImageInfiniteLight::SampleLi with the compensated distribution
                             // (lights.h:588-613), shadow ray to 2 x sceneRadius (integrators.cpp:1311-1338)
@@ -2536,6 +2615,9 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                             if (Ls.nonzero() && fval != 0) {
                                 s_ls[threadIdx.x] = to4(Ls);
                                 s_fhat[threadIdx.x] = fval;
+                                // (general: the pick's PMF, which with a light BVH is not a
+                                // function of the light alone)
+                                if constexpr (kImage) s_img[threadIdx.x] = make_float4(0.f, 0.f, pmf, fval);
                                 const V3 pOut = po + wi * (2 * P.lights.scene_radius);
                                 const V3 d = pOut - po;
                                 light = idx;
@@ -2589,7 +2671,9 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                         contrib = smul(Ls, beta * f_hat * T_ray) / savg(sr_l + sr_u);
                     } else {
                         // the delta light's spectrum and f_hat of the spawn (same wo, wi)
-                        const float p_l = light_pmf_staged<kStaged>(P.lights, s_lt, light) * 1.f;
+                        float p_l;
+                        if constexpr (kImage) p_l = s_img[threadIdx.x].z * 1.f;
+                        else p_l = light_pmf_staged<kStaged>(P.lights, s_lt, light) * 1.f;
                         const S f_hat = sconst<S>(s_fhat[threadIdx.x]);
                         const Spec Ls = spec4(s_ls[threadIdx.x]);
                         sr_l = sr_l * (r_u * p_l);
@@ -2705,6 +2789,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 for (int k = 0; k < P.lights.n; ++k) {
                     const int ltype = light_type<kStaged>(P.lights, s_lt, k);
                     if (ltype == 0 || (!kImage && ltype == 2)) continue;
+                    if (kImage && ltype >= ll::kPoint) continue;   // local lights: nothing at infinity
                     Spec Le;
                     float pdfLi = 0.f;
                     if (kImage && ltype == 2) {
@@ -3463,15 +3548,59 @@ __global__ void __launch_bounds__(256) k_light_probe(DevLights ls, int index, in
     if (pdf_li) pdf_li[i] = pLi;
     if (Le4) { Le4[4 * i] = Le.v0; Le4[4 * i + 1] = Le.v1; Le4[4 * i + 2] = Le.v2; Le4[4 * i + 3] = Le.v3; }
 }
-// light_pick<true> for n draws (avr_light_pick): the index (-1: no light) and its PMF
-__global__ void __launch_bounds__(256) k_light_pick(DevLights ls, int n, const float *__restrict__ u, int *__restrict__ idx,
+// light_pick_at for n draws (avr_light_pick, avr_light_pick_at): the index (-1: no light) and its
+// PMF; p3: a reference point per draw (null: the origin, which lists of infinite lights ignore)
+__global__ void __launch_bounds__(256) k_light_pick(DevLights ls, int n, const float *__restrict__ u,
+                                                    const float *__restrict__ p3, int *__restrict__ idx,
                                                     float *__restrict__ pmf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float p = 0.f;
-    const int k = ls.n > 0 ? light_pick<true>(ls, u[i], &p) : -1;
+    const V3 at = p3 ? V3{p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]} : V3{0.f, 0.f, 0.f};
+    const int k = ls.n > 0 ? light_pick_at(ls, at, u[i], &p) : -1;
     idx[i] = k;
     pmf[i] = k >= 0 ? p : 0.f;
+}
+// SampleLi of light `index` at n reference points (avr_light_probe_at): wi, its pdf (0: no sample),
+// Ls and the distance to the light (infinite lights: 2 x sceneRadius, the shadow ray's length)
+__global__ void __launch_bounds__(256) k_light_probe_at(DevLights ls, int index, int n, const float *__restrict__ u2,
+                                                        const float *__restrict__ p3, const float *__restrict__ lambda,
+                                                        float *__restrict__ wi3, float *__restrict__ pdf_sample,
+                                                        float *__restrict__ Ls4, float *__restrict__ dist) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || index < 0 || index >= ls.n) return;
+    const DevLight &lt = ls.list[index];
+    const Spec lamv = {lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]};
+    const LambdaIdx li = lambda_index(lamv);
+    const V3 p = {p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]};
+    V3 wi = {0.f, 0.f, 0.f};
+    Spec Ls = Spec::c(0.f);
+    float lsPdf = 0.f, r = 2 * ls.scene_radius;
+    if (lt.type == 0) {
+        wi = {lt.w[0], lt.w[1], lt.w[2]};
+        Ls = sample_table(lt.L, li) * lt.scale;
+        lsPdf = 1.f;
+    } else if (lt.type == 2) {
+        float su, sv;
+        env::distrib_sample(lt.dist, u2[2 * i], u2[2 * i + 1], &su, &sv, &lsPdf);
+        if (lsPdf != 0) {
+            V3 wl;
+            env::square_to_sphere(su, sv, &wl.x, &wl.y, &wl.z);
+            wi = xf_vec3(lt.rfl, wl);
+            lsPdf = lsPdf / (4 * kPi);
+            Ls = image_le(lt, su, sv, lamv);
+        }
+    } else if (lt.type >= ll::kPoint) {
+        V3 pL;
+        Ls = local_light_li(lt, p, li, &wi, &pL);
+        lsPdf = Ls.nonzero() ? 1.f : 0.f;
+        const V3 d = pL - p;
+        r = __builtin_sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+    }
+    if (wi3) { wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z; }
+    if (pdf_sample) pdf_sample[i] = lsPdf;
+    if (Ls4) { Ls4[4 * i] = Ls.v0; Ls4[4 * i + 1] = Ls.v1; Ls4[4 * i + 2] = Ls.v2; Ls4[4 * i + 3] = Ls.v3; }
+    if (dist) dist[i] = r;
 }
 
 // ---------------------------------------------------------------------------

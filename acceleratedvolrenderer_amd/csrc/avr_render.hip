@@ -385,7 +385,7 @@ static int pass_camera_stage(avr_context *c, avr::Params *p, bool cam_ahead, int
 // and the LDS left take a camera block. *variant: the slot launched; *end: the event behind it.
 static int pass_kpaths(avr_context *c, const avr::Params &p, bool cam_next, int *variant, int *end) {
     EV_MARK(e0);
-    const int kv = avr::kp::select(c->render_mode != 0, c->n_image_lights > 0 || c->lights.power, c->med.type,
+    const int kv = avr::kp::select(c->render_mode != 0, c->n_image_lights > 0 || c->lights.mode != avr::kPickInfinite, c->med.type,
                                    c->sampler_kind, avr::smp::zsobol_wide(p.zs), c->med.emissive != 0, c->gray);
     const bool hold = cam_next && c->paths_grid[kv] > 4 * c->num_cus;
     hipLaunchKernelGGL(c->kpaths[kv], dim3(hold ? 4 * c->num_cus : c->paths_grid[kv]), dim3(256),
@@ -578,7 +578,8 @@ extern "C" int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, 
     // every type-2 light needs its own image: a count of avr_light_image calls would let a map
     // replaced twice stand in for one never given, whose img and dist are null
     if (!image_lights_complete(c)) return fail(AVR_ERR_STATE, "image light without avr_light_image");
-    if (c->light_sampler == 1 && c->lights.n > 0 && !c->lights.power)
+    if (!local_lights_complete(c)) return fail(AVR_ERR_STATE, "point or spot light without avr_light_local");
+    if (c->light_sampler == 1 && c->lights.n > 0 && c->lights.mode != avr::kPickPower)
         return fail(AVR_ERR_STATE, "power light sampler: light weights incomplete");
     RenderCall rc;
     rc.spp_begin = spp_begin; rc.spp_end = spp_end;
@@ -600,7 +601,7 @@ extern "C" int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, 
     // only behind the ZSobol pass table built ahead
     rc.overlap_ok = persistent && c->pass_overlap && c->ptab_spec && c->sampler_kind == 1 &&
                     c->stream == c->own_stream && c->gray && c->med.type == 0 && !c->med.emissive &&
-                    c->n_image_lights == 0 && !c->lights.power;
+                    c->n_image_lights == 0 && c->lights.mode == avr::kPickInfinite;
     if (rc.overlap_ok) ensure_alt(c);
     EV_MARK(evStart);
     rc.call_stride = (c->prev_call_begin >= 0 && spp_begin > c->prev_call_begin) ? spp_begin - c->prev_call_begin : 0;

@@ -244,8 +244,10 @@ class VolPathIntegrator(FilmIntegrator):
         if lightsampler not in ("bvh", "uniform", "power"):
             raise ValueError(f"{lightsampler}: unknown light sampling strategy")
         # With only infinite lights "bvh" and "uniform" pick uniformly with pmf 1/N
-        # (lightsamplers.h:266-277, 35-50); "power" draws from an alias table over the lights'
-        # Phi (PowerLightSampler, lightsamplers.cpp:76-96; avr_light_sampler)
+        # (lightsamplers.h:266-277, 35-50); with a PointLight or SpotLight in the list "bvh" is
+        # pbrt's whole BVHLightSampler and "uniform" UniformLightSampler over the whole list;
+        # "power" draws from an alias table over the lights' Phi (PowerLightSampler,
+        # lightsamplers.cpp:76-96; avr_light_sampler)
         self.lightsampler = lightsampler
         self.scene = scene
         self.maxdepth = int(maxdepth)
@@ -263,7 +265,7 @@ class VolPathIntegrator(FilmIntegrator):
             raise ValueError("mode must be 'replay' (per-sample parity) or 'fast' (statistical parity)")
         self.mode = mode
         self.ctx.set_render_mode(mode)
-        self.ctx.set_light_sampler(1 if lightsampler == "power" else 0)
+        self.ctx.set_light_sampler({"bvh": 0, "power": 1, "uniform": 2}[lightsampler])
         self.ctx.set_scene(scene)
 
     @staticmethod

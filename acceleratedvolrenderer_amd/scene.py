@@ -373,6 +373,77 @@ class ImageInfiniteLight:
         return np.zeros(3, np.float32)
 
 
+class PointLight:
+    """PointLight::Create (lights.cpp:192-213): "scale" / SpectrumToPhotometric(I), times
+    power / (4 Pi) for power > 0; renderFromLight = world_from_light * Translate(from). I defaults
+    to the colour space illuminant. A delta-position light: Li = scale * I / r^2."""
+    type_id = 3
+    cos_falloff_start, cos_falloff_end = np.float32(1.0), np.float32(-1.0)   # the whole sphere (not read)
+
+    def __init__(self, from_=(0.0, 0.0, 0.0), I=None, scale=1.0, power=None, world_from_light=None):   # noqa: E741
+        f32 = np.float32
+        self.L = spectra.TABLES["D65"].copy() if I is None else spectra.as_table(I, 1.0)
+        sc = f32(f32(scale) / spectra.spectrum_to_photometric(self.L))
+        if power is not None and power > 0:
+            k_e = f32(f32(4) * f32(math.pi))
+            sc = f32(sc * f32(f32(power) / k_e))
+        self.scale = sc
+        base = np.eye(4) if world_from_light is None else np.asarray(world_from_light, np.float64)
+        self.world_from_light = base @ xf.translate(np.asarray(from_, np.float32).astype(np.float64))
+
+    def render_direction(self, render_from_world):
+        return np.zeros(3, np.float32)
+
+
+def _frame_from_z(z):
+    """Frame::FromZ (util/vecmath.h:1868-1872) through CoordinateSystem (util/vecmath.h:1007-1013),
+    float32: the rows x, y, z of the frame's matrix."""
+    f32 = np.float32
+    z = np.asarray(z, f32)
+    sign = f32(np.copysign(f32(1), z[2]))
+    a = f32(f32(-1) / f32(sign + z[2]))
+    b = f32(f32(z[0] * z[1]) * a)
+    x = np.array([f32(f32(1) + f32(f32(sign * f32(z[0] * z[0])) * a)), f32(sign * b), f32(f32(-sign) * z[0])], f32)
+    y = np.array([b, f32(sign + f32(f32(z[1] * z[1]) * a)), f32(-z[1])], f32)
+    return np.stack([x, y, z]).astype(f32)
+
+
+class SpotLight:
+    """SpotLight::Create (lights.cpp:1433-1464): renderFromLight = world_from_light * Translate(from) *
+    Inverse(Frame::FromZ(Normalize(to - from))); "scale" / SpectrumToPhotometric(I), times
+    power / (2 Pi ((1 - cosStart) + (cosStart - cosEnd) / 2)) for power > 0; cosFalloffEnd =
+    cos(Radians(coneangle)), cosFalloffStart = cos(Radians(coneangle - conedeltaangle)), in float.
+    Li = SmoothStep(cos theta, cosFalloffEnd, cosFalloffStart) * scale * I / r^2."""
+    type_id = 4
+
+    def __init__(self, from_=(0.0, 0.0, 0.0), to=(0.0, 0.0, 1.0), I=None, scale=1.0, power=None, coneangle=30.0,   # noqa: E741
+                 conedeltaangle=5.0, world_from_light=None):
+        f32 = np.float32
+        total, start = f32(coneangle), f32(f32(coneangle) - f32(conedeltaangle))
+        if start > total:
+            raise ValueError("SpotLight: falloffStart > totalWidth (a negative conedeltaangle)")
+        self.L = spectra.TABLES["D65"].copy() if I is None else spectra.as_table(I, 1.0)
+        rad = lambda deg: f32(f32(f32(math.pi) / f32(180)) * deg)   # noqa: E731
+        self.cos_falloff_end = f32(np.cos(rad(total)))
+        self.cos_falloff_start = f32(np.cos(rad(start)))
+        sc = f32(f32(scale) / spectra.spectrum_to_photometric(self.L))
+        if power is not None and power > 0:
+            cs, ce = self.cos_falloff_start, self.cos_falloff_end
+            k_e = f32(f32(f32(2) * f32(math.pi)) * f32(f32(f32(1) - cs) + f32(f32(cs - ce) / f32(2))))
+            sc = f32(sc * f32(f32(power) / k_e))
+        self.scale = sc
+        frm, to = np.asarray(from_, f32), np.asarray(to, f32)
+        d = (to - frm).astype(f32)
+        ln = f32(np.sqrt(f32(f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2]))))
+        dir_to_z = np.eye(4)
+        dir_to_z[:3, :3] = _frame_from_z((d / ln).astype(f32)).astype(np.float64)
+        base = np.eye(4) if world_from_light is None else np.asarray(world_from_light, np.float64)
+        self.world_from_light = base @ xf.translate(frm.astype(np.float64)) @ np.linalg.inv(dir_to_z)
+
+    def render_direction(self, render_from_world):
+        return np.zeros(3, np.float32)
+
+
 class _ProjectiveCamera:
     type_id = -1
 
@@ -798,9 +869,10 @@ class Scene:
             (0, spectra.N), np.float32)
         self.light_scale = np.array([l.scale for l in self.lights], np.float32)
         # image lights: renderFromLight and its inverse (ImageInfiniteLight's transform)
-        self.light_rfl = [xf.f32(self.render_from_world @ l.world_from_light) if l.type_id == 2 else None
+        # (and the local lights: PointLight / SpotLight's renderFromLight and its inverse)
+        self.light_rfl = [xf.f32(self.render_from_world @ l.world_from_light) if l.type_id >= 2 else None
                           for l in self.lights]
-        self.light_lfr = [xf.f32(np.linalg.inv(self.render_from_world @ l.world_from_light)) if l.type_id == 2
+        self.light_lfr = [xf.f32(np.linalg.inv(self.render_from_world @ l.world_from_light)) if l.type_id >= 2
                           else None for l in self.lights]
 
 

@@ -324,7 +324,8 @@ int avr_tune_walk(avr_context *ctx, const int *refill, int nr, const int *dda, i
 /* Lights (lights.h:244-305 DistantLight, lights.cpp:950-972 UniformInfiniteLight).
  * type 0 = distant: w = render-space unit vector towards the light
  *          (Normalize(renderFromLight(0,0,1)), lights.h:287); type 1 = uniform infinite;
- * type 2 = image infinite (then avr_light_image).
+ * type 2 = image infinite (then avr_light_image); type 3 = point, type 4 = spot (lights.h:191-236,
+ * 741-797; then avr_light_local; w is ignored and L is the intensity table I).
  * L = n tables of 471 floats; scale = final light scale (1/SpectrumToPhotometric folded in).
  * scene_radius = Bounds3::BoundingSphere radius of the scene bounds (lights.h:280). */
 int avr_lights(avr_context *ctx, int n, const int *types, const float *w3, const float *L, const float *scale,
@@ -342,13 +343,30 @@ int avr_lights(avr_context *ctx, int n, const int *types, const float *w3, const
 int avr_light_image(avr_context *ctx, int index, int res, const float *pixel_coeffs, const float *distribution,
                     const float *illuminant, const float render_from_light[16], const float light_from_render[16]);
 
+/* PointLight / SpotLight for light `index` of the last avr_lights call, which lists it with type 3
+ * or 4: renderFromLight and its inverse (row-major 4x4) and the spot light's
+ * cos(Radians(falloffStart)), cos(Radians(totalWidth)). A point light passes cosines that make the
+ * cone everything (1 and -1); they are not read. The lights are delta-position lights: NEE samples
+ * them at the scatter point (Li = scale * I / r^2, times SmoothStep of the cone for the spot light),
+ * they are invisible to camera rays and escape nothing. A render with a local light that lacks
+ * this call returns AVR_ERR_STATE. Scenes with local lights run k_paths' general instantiations,
+ * as scenes with image lights do. */
+int avr_light_local(avr_context *ctx, int index, const float render_from_light[16], const float light_from_render[16],
+                    float cos_falloff_start, float cos_falloff_end);
+
 /* VolPath's light sampler (VolPathIntegrator::Create "lightsampler", integrators.cpp:1402-1420;
  * LightSampler::Create, lightsamplers.cpp:22-37): 0 = "bvh" (default) or "uniform" — identical
  * for infinite lights (lightsamplers.h:266-277, 35-50); 1 = "power": PowerLightSampler
  * (lightsamplers.h:63-99, lightsamplers.cpp:76-96), lights picked by an AliasTable over
  * Average(Phi(lambda) / pdf) at SampleVisible(0.5) (DistantLight / UniformInfiniteLight /
- * ImageInfiniteLight::Phi, lights.cpp:216, 974, 1042). Kept across avr_lights calls; a power
- * render needs every image light's avr_light_image first. */
+ * ImageInfiniteLight / PointLight / SpotLight::Phi, lights.cpp:216, 974, 1042, 164, 1365). Kept
+ * across avr_lights calls; a power render needs every image light's avr_light_image first.
+ * With a point or spot light in the list, 0 is pbrt's whole BVHLightSampler (lightsamplers.h:
+ * 259-404): the infinite lights share pInfinite = nInf / (nInf + 1) and the rest goes to a
+ * traversal of the light BVH by CompactLightBounds::Importance at the scatter point; the tree is
+ * built on the host (lightsamplers.cpp:109-238) whenever the list or the sampler changes, without
+ * the lights of zero power. 2 = "uniform": UniformLightSampler over the whole list
+ * (lightsamplers.h:35-50); for lists of infinite lights 0 and 2 are the same pick. */
 int avr_light_sampler(avr_context *ctx, int kind);
 
 /* Readbacks of the light stage (replay checks; no render path uses them).
@@ -365,11 +383,27 @@ int avr_light_sampler(avr_context *ctx, int kind);
  * for the next pass, which that pass then makes again.
  * avr_light_pick: the light sampler's pick for n draws u: idx (n; -1: no light) and its PMF (n).
  * avr_light_sampler_table (host only): per light the sampler's bin {q, p, alias}: the AliasTable
- * of the power sampler, or q = 1, p = 1 / n, alias = -1 for "bvh" / "uniform". */
+ * of the power sampler, or q = 1, p = 1 / n, alias = -1 for "bvh" / "uniform" (with a point or
+ * spot light in the list the "bvh" PMF depends on the reference point: avr_light_pick_at). */
 int avr_light_probe(avr_context *ctx, int index, int n, const float *u2, const float *w3, const float *lambda4,
                     float *wi3, float *pdf_sample, float *Ls4, float *pdf_li, float *Le4);
 int avr_light_pick(avr_context *ctx, int n, const float *u, int *idx, float *pmf);
 int avr_light_sampler_table(avr_context *ctx, float *q, float *p, int *alias);
+/* The same with a reference point per probe (p3, n*3, render space), which local lights and the
+ * light BVH depend on. avr_light_probe_at: SampleLi of light `index` at p: wi3 (n*3), pdf_sample
+ * (n; 0: no sample, e.g. outside a spot light's cone), Ls4 (n*4) and the distance to the light
+ * (dist, n; 2 x scene_radius for the infinite lights, the length of their shadow ray).
+ * avr_light_pick_at: the light sampler's pick at p for the draw u.
+ * avr_light_bvh (host only): the light BVH of sampler 0: *n_nodes nodes (at most 15) with, per
+ * node, phi, the decoded direction w (w3), the two quantised cosines (qcos: o, e), the quantised
+ * box (qb: min xyz, max xyz), the second child's node index or the leaf's light index (link) and
+ * the leaf flag; all_bounds: allLightBounds (pMin, pMax); *n_infinite the number of infinite
+ * lights. Any output may be NULL. No tree (no local light of non-zero power): *n_nodes = 0. */
+int avr_light_probe_at(avr_context *ctx, int index, int n, const float *u2, const float *p3, const float *lambda4,
+                       float *wi3, float *pdf_sample, float *Ls4, float *dist);
+int avr_light_pick_at(avr_context *ctx, int n, const float *u, const float *p3, int *idx, float *pmf);
+int avr_light_bvh(avr_context *ctx, int *n_nodes, float *phi, float *w3, int *qcos, int *qb, int *link, int *leaf,
+                  float all_bounds[6], int *n_infinite);
 
 /* Camera: type 0 orthographic, 1 perspective (cameras.cpp:284-306, 404-427).
  * camera_from_raster: full 4x4 (projective for perspective); render_from_camera: affine 4x4. */

@@ -69,12 +69,18 @@ Medium FindMedium(Primitive aggregate) {
 
 // DistantLight (lights.h:244-305) and UniformInfiniteLight (lights.h:508-550): type, render-
 // space direction towards a distant light (lights.h:287), the emitted spectrum with the
-// light's scale folded in (GetLEmit: the same products as scale * Lemit->Sample(lambda))
+// light's scale folded in (GetLEmit: the same products as scale * Lemit->Sample(lambda)).
+// PointLight (lights.h:191-236) and SpotLight (lights.h:741-797): the intensity table with the
+// scale beside it (SampleLi multiplies them per lookup), then avr_light_local with the light's
+// transform and, for the spot light, its two cosines.
 void UploadLights(avr_context *ctx, const std::vector<Light> &lights, const Bounds3f &sceneBounds) {
     std::vector<int> type;
     std::vector<float> w, L, scale;
+    struct Local { int index; Transform renderFromLight; float cosStart, cosEnd; };
+    std::vector<Local> locals;
     for (Light l : lights) {   // (a copy: GetLEmit / GetRenderFromLight are non-const)
         DenselySampledSpectrum Le;
+        float sc = 1.f;
         if (DistantLight *d = l.CastOrNullptr<DistantLight>()) {
             Vector3f wl = Normalize(d->GetRenderFromLight()(Vector3f(0, 0, 1)));
             type.push_back(0);
@@ -84,10 +90,22 @@ void UploadLights(avr_context *ctx, const std::vector<Light> &lights, const Boun
             type.push_back(1);
             w.insert(w.end(), {0.f, 0.f, 0.f});
             Le = u->GetLEmit();
+        } else if (PointLight *p = l.CastOrNullptr<PointLight>()) {
+            locals.push_back({(int)type.size(), p->GetRenderFromLight(), 1.f, -1.f});
+            type.push_back(3);
+            w.insert(w.end(), {0.f, 0.f, 0.f});
+            Le = p->GetI();
+            sc = p->Scale();
+        } else if (SpotLight *s = l.CastOrNullptr<SpotLight>()) {
+            locals.push_back({(int)type.size(), s->GetRenderFromLight(), s->CosFalloffStart(), s->CosFalloffEnd()});
+            type.push_back(4);
+            w.insert(w.end(), {0.f, 0.f, 0.f});
+            Le = s->GetIemit();
+            sc = s->Scale();
         } else {
-            ErrorExit("volpath_mi355x: %s is not a distant or uniform infinite light", l.ToString());
+            ErrorExit("volpath_mi355x: %s is not a distant, uniform infinite, point or spot light", l.ToString());
         }
-        scale.push_back(1.f);
+        scale.push_back(sc);
         L.resize(L.size() + kLambdaSamples);
         Tabulate(Le, L.data() + L.size() - kLambdaSamples);
     }
@@ -96,6 +114,12 @@ void UploadLights(avr_context *ctx, const std::vector<Light> &lights, const Boun
     sceneBounds.BoundingSphere(&center, &radius);
     CheckAvr(avr_lights(ctx, (int)type.size(), type.data(), w.data(), L.data(), scale.data(), radius),
              "avr_lights");
+    for (const Local &lo : locals) {
+        float m[16], mi[16];
+        ToRowMajor(lo.renderFromLight.GetMatrix(), m);
+        ToRowMajor(lo.renderFromLight.GetInverseMatrix(), mi);
+        CheckAvr(avr_light_local(ctx, lo.index, m, mi, lo.cosStart, lo.cosEnd), "avr_light_local");
+    }
 }
 
 void UploadMedium(avr_context *ctx, Medium medium) {

@@ -60,6 +60,16 @@ ACCESSORS = {
         ("SphericalCamera", ["bool IsEqualArea() const { return mapping == EqualArea; }"]),
     ],
     "lights.h": [
+        ("PointLight", [
+            "const DenselySampledSpectrum &GetI() const { return *I; }",
+            "Float Scale() const { return scale; }",
+        ]),
+        ("SpotLight", [
+            "const DenselySampledSpectrum &GetIemit() const { return *Iemit; }",
+            "Float Scale() const { return scale; }",
+            "Float CosFalloffStart() const { return cosFalloffStart; }",
+            "Float CosFalloffEnd() const { return cosFalloffEnd; }",
+        ]),
         ("UniformInfiniteLight", [
             "DenselySampledSpectrum GetLEmit() {",
             "    DenselySampledSpectrum spectrum = *Lemit;",
