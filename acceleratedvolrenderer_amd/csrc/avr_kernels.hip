@@ -25,6 +25,7 @@
 #include "avr_local_light.h"
 #include "avr_flip.h"
 #include "avr_boundary.h"
+#include "avr_kpaths_slot.h"
 
 #include <type_traits>
 
@@ -501,22 +502,34 @@ __device__ __forceinline__ float grid_lookup(const float *__restrict__ v, int nx
 }
 
 // Same value as grid_lookup() bit for bit (same taps, same lerp order) from the fat layout,
-// in two halves so a caller can issue the gather early and combine it later (k_paths issues
-// it before the DDA walk and consumes it after, hiding the HBM latency behind the walk).
-// fat_issue: false when p's footprint lies outside the fat copy (grid_lookup applies).
+// in two halves: the gather (fat_issue) and the lerps (fat_lerp); fat_lookup is their one caller.
+// fat_issue: false when p's footprint lies outside the fat copy. Then every one of the eight
+// taps lies outside the grid (ix < -1 or ix >= nx puts both ix and ix + 1 outside, likewise y and
+// z) and grid_lookup reads them all as zero: the caller lerps zeros with the same dx, dy, dz.
+// kStraight (k_paths' parked kernels): the gather is issued by every lane, without a branch around
+// it, so the caller's arithmetic can follow it before the wait: an outside lane reads the copy's
+// first entry (ix = iy = iz = -1) and the caller drops what it read. The other callers keep the
+// gather behind the bounds test: its eight registers live across their code cost two gray
+// Homogeneous / Cloud kernels 12 B/lane of scratch.
+template <bool kStraight>
 __device__ __forceinline__ bool fat_issue(const float4 *__restrict__ fat, int nx, int ny, int nz, V3 p, float4 &a,
                                           float4 &b, float &dx, float &dy, float &dz, const float *fn = nullptr) {
     const float fx = fn ? fn[0] : (float)nx, fy = fn ? fn[1] : (float)ny, fz = fn ? fn[2] : (float)nz;
     float psx = p.x * fx - .5f, psy = p.y * fy - .5f, psz = p.z * fz - .5f;
     int ix = (int)__builtin_floorf(psx), iy = (int)__builtin_floorf(psy), iz = (int)__builtin_floorf(psz);
-    if (ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz) return false;
     dx = psx - (float)ix, dy = psy - (float)iy, dz = psz - (float)iz;
+    const bool inside = !(ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz);
     // entry index in 32 bits with 24-bit multiplies where every operand fits them
     // ((ny + 1)(nz + 1) < 2^24, nx + 1 < 2^24, < 2^31 entries: cubes to 1289^3, not slabs thin in
-    // x), in 64 bits otherwise; the condition is wave-uniform (avr_grid_index.h)
-    const size_t e = fat_entry_index(nx, ny, nz, ix, iy, iz) * 2;
-    a = fat[e], b = fat[e + 1];
-    return true;
+    // x), in 64 bits otherwise; the condition is wave-uniform (avr_grid_index.h).
+    if constexpr (kStraight) {
+        const size_t e = fat_entry_index(nx, ny, nz, inside ? ix : -1, inside ? iy : -1, inside ? iz : -1) * 2;
+        a = fat[e], b = fat[e + 1];
+    } else if (inside) {
+        const size_t e = fat_entry_index(nx, ny, nz, ix, iy, iz) * 2;
+        a = fat[e], b = fat[e + 1];
+    }
+    return inside;
 }
 __device__ __forceinline__ float fat_lerp(float4 a, float4 b, float dx, float dy, float dz) {
     float d00 = lerp(dx, a.x, a.y);
@@ -526,14 +539,17 @@ __device__ __forceinline__ float fat_lerp(float4 a, float4 b, float dx, float dy
     return lerp(dz, lerp(dy, d00, d10), lerp(dy, d01, d11));
 }
 // Same value as grid_lookup() bit for bit from the bricked layout (DevMedium::brick).
-__device__ __forceinline__ float brick_lookup(const float *__restrict__ brick, const int nb[3],
-                                              const float *__restrict__ v, int nx, int ny, int nz, V3 p,
-                                              const float *fn = nullptr) {
+__device__ __forceinline__ float brick_lookup(const float *__restrict__ brick, const int nb[3], int nx, int ny, int nz,
+                                              V3 p, const float *fn = nullptr) {
     const float fx = fn ? fn[0] : (float)nx, fy = fn ? fn[1] : (float)ny, fz = fn ? fn[2] : (float)nz;
     float psx = p.x * fx - .5f, psy = p.y * fy - .5f, psz = p.z * fz - .5f;
     int ix = (int)__builtin_floorf(psx), iy = (int)__builtin_floorf(psy), iz = (int)__builtin_floorf(psz);
-    if (ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz) return grid_lookup(v, nx, ny, nz, p, fn);
     float dx = psx - (float)ix, dy = psy - (float)iy, dz = psz - (float)iz;
+    // outside the copy all eight taps are zero (fat_issue): grid_lookup's lerps of zeros
+    if (ix < -1 || ix >= nx || iy < -1 || iy >= ny || iz < -1 || iz >= nz) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        return fat_lerp(z, z, dx, dy, dz);
+    }
     // u = i + 1 in 0 .. n: brick u >> 3, apron-local u & 7
     const float *q = brick + brick_float_offset(nb, ix + 1, iy + 1, iz + 1);
     float d00 = lerp(dx, q[0], q[1]);
@@ -545,17 +561,21 @@ __device__ __forceinline__ float brick_lookup(const float *__restrict__ brick, c
 // GridMedium density in the medium's layout: fat, bricked, or pbrt's linear SampledGrid
 __device__ __forceinline__ float grid_density(const DevMedium &m, V3 p);
 
-__device__ __forceinline__ float fat_lookup(const float4 *__restrict__ fat, const float *__restrict__ v, int nx, int ny,
-                                            int nz, V3 p, const float *fn = nullptr) {
+template <bool kStraight = false>
+__device__ __forceinline__ float fat_lookup(const float4 *__restrict__ fat, int nx, int ny, int nz, V3 p,
+                                            const float *fn = nullptr) {
     float4 a, b;
     float dx, dy, dz;
-    if (!fat_issue(fat, nx, ny, nz, p, a, b, dx, dy, dz, fn)) return grid_lookup(v, nx, ny, nz, p, fn);
-    return fat_lerp(a, b, dx, dy, dz);
+    // outside the copy: grid_lookup's eight zero taps, lerped as it lerps them (a NaN or
+    // infinite coordinate gives the same NaN)
+    const bool inside = fat_issue<kStraight>(fat, nx, ny, nz, p, a, b, dx, dy, dz, fn);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    return fat_lerp(inside ? a : z, inside ? b : z, dx, dy, dz);
 }
 
 __device__ __forceinline__ float grid_density(const DevMedium &m, V3 p) {
-    if (m.fat) return fat_lookup(m.fat, m.density, m.nx, m.ny, m.nz, p, m.fn);
-    if (m.brick) return brick_lookup(m.brick, m.nb, m.density, m.nx, m.ny, m.nz, p, m.fn);
+    if (m.fat) return fat_lookup(m.fat, m.nx, m.ny, m.nz, p, m.fn);
+    if (m.brick) return brick_lookup(m.brick, m.nb, m.nx, m.ny, m.nz, p, m.fn);
     return grid_lookup(m.density, m.nx, m.ny, m.nz, p, m.fn);
 }
 
@@ -1976,7 +1996,7 @@ __device__ __forceinline__ void ddal_init(DdaL &q, const DevMedium &m, Ray ray, 
     q.mcur = maj[q.vidx];
 }
 // Reload mcur from pidx: one load per loop iteration into the loop-carried register, so the
-// wait for it lands at the next ddal_next (a load inside ddal_next's predicated block is
+// wait for it lands at the next ddal_step (a load inside ddal_step's predicated block is
 // followed by a phi copy that waits right away).
 __device__ __forceinline__ void ddal_prefetch(DdaL &q, const float *maj) { q.mcur = maj[q.pidx]; }
 // The global (NanoVDB) majorant through a buffer resource over its ncells + 1 floats: the
@@ -1997,17 +2017,18 @@ __device__ __forceinline__ void ddal_prefetch_occ_buf(DdaL &q, __amdgpu_buffer_r
     const unsigned w = occ[p >> 6];   // (LDS: an out-of-range index cannot fault; the bit is then moot)
     q.mcur = maj_load(r, ((w >> ((p >> 1) & 31)) & 1u) ? p : ncells);
 }
-// Next(): false when exhausted. `maj` is the LDS copy; sy/sz the linear strides of y and z.
+// Next() in two halves, so the walk's trip has one masked region: ddal_done() is Next()'s
+// "exhausted" test, ddal_step() the crossing of one cell of an iterator that is not done
+// (branch-free). sy/sz are the linear strides of y and z.
 // The next cell's index (pidx) is left unclamped: the caller's prefetch reads LDS, where an
 // out-of-range index cannot fault, or a bounds-checked buffer (maj_load)
-__device__ __forceinline__ bool ddal_next(DdaL &q, const float *maj, int sy, int sz, float *s0, float *s1,
-                                          float *mval) {
+__device__ __forceinline__ bool ddal_done(const DdaL &q) { return q.tMin >= q.tMax; }
+__device__ __forceinline__ void ddal_step(DdaL &q, int sy, int sz, float *s0, float *s1, float *mval) {
     // fields are copied to values first: a select between struct members invites the
     // compiler to turn the struct into a scratch array indexed by the axis
     const float tMin = q.tMin, tMax = q.tMax, nx = q.nx, ny = q.ny, nz = q.nz;
     const float dx = q.dx, dy = q.dy, dz = q.dz;
     const int rem = q.rem, vidx = q.vidx;
-    if (tMin >= tMax) return false;
     // cmpToAxis = {2, 1, 2, 1, 2, 2, 0, 0} over bits (nx<ny, nx<nz, ny<nz)
     const bool xy = nx < ny, xz = nx < nz, yz = ny < nz;
     const bool ax0 = xy && xz, ax1 = !xy && yz;
@@ -2029,13 +2050,12 @@ __device__ __forceinline__ bool ddal_next(DdaL &q, const float *maj, int sy, int
     q.vidx = nv;
     // the next cell's majorant is loaded by ddal_prefetch so its latency (L2 for NanoVDB's
     // 64^3 grid) hides behind this step's work; past the last cell the index is left as it is
-    // (its value is never used: the next call returns false)
+    // (its value is never used: the iterator is done)
     q.pidx = nv;
     const float nn = nextA + __builtin_fabsf(dA);
     q.nx = ax0 ? nn : nx;
     q.ny = ax1 ? nn : ny;
     q.nz = (ax0 || ax1) ? nz : nn;
-    return true;
 }
 
 // PCG32 Advance(s * 65536) of sample index s (IndependentSampler::StartPixelSample,
@@ -2158,7 +2178,7 @@ __global__ void __launch_bounds__(256) k_bin_scatter(const int *__restrict__ que
 // and the NEE light) lives in per-lane LDS arrays instead of registers, and the majorant grid
 // is read through a bounds-checked buffer (L2) instead of an LDS copy.
 template <bool kEmissive, bool kGray, int kMed, bool kImage> constexpr bool kpaths_parked() {
-    return AVR_KP_PARK != 0 && kGray && kMed == 0 && !kEmissive && !kImage;
+    return AVR_KP_PARK != 0 && kp::parked(kEmissive, kGray, kMed, kImage);   // (the host routes by the same predicate)
 }
 template <bool kEmissive, bool kGray, int kMed, bool kImage> constexpr bool kpaths_bufmaj() {
     return kMed == 3 || (AVR_KP_BUFMAJ != 0 && kGray && kMed == 0 && !kEmissive && !kImage);
@@ -2407,7 +2427,9 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
     const int lane = lane_id();
     const int xcc = xcc_id();
     // work counters off the VGPR budget: per wave in LDS, one ds_add by the first active lane
-    // of each event batch (wave_count); DDA steps as a wave-uniform (scalar) sum of ballots;
+    // of each event batch (wave_count); DDA steps, parked: summed over a walk's trips as a
+    // wave-uniform 32-bit count and added to LDS once per walk; not parked (where that add cost a
+    // NanoVDB instantiation a wave/SIMD): each lane's own count, reduced over the wave at the end;
     // the wave-loop counters wave-uniform (scalar registers)
     __shared__ unsigned s_cnt[4][6];
     if (threadIdx.x < 24) (&s_cnt[0][0])[threadIdx.x] = 0;
@@ -2417,7 +2439,7 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
         const uint64_t am = __ballot(1);
         if (lane_id() == __ffsll((long long)am) - 1) atomicAdd(wcnt + k, (unsigned)__popcll(am));
     };
-    unsigned long long nStepsW = 0;
+    [[maybe_unused]] unsigned nStepsLane = 0;   // (not parked) this lane's own DDA steps, summed over the wave at the end
 #define AVR_COUNT(var, k) wave_count(k)
     unsigned long long nIter = 0, nActive = 0;
 
@@ -2998,37 +3020,43 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
             const S sig_t = sig_a + sig_s;
             const float st0 = sv0(sig_t);
             // walk: 0 walking, 1 candidate pending (accepted or ambiguous), 2 segments exhausted.
-            // Each step crosses at most one majorant cell and tests at most one candidate; the
-            // loop has one wave-uniform exit so the body stays predicated (no per-exit masks).
+            // Each trip crosses at most one majorant cell and tests at most one candidate. The
+            // trip is straight-line code: one masked region for the DDA step; the candidate test
+            // and the RNG advance are computed for every lane and committed by select (a lane
+            // that is not walking computes on stale values and commits nothing), and the loop has
+            // one wave-uniform exit.
             int walk = 0;
+            [[maybe_unused]] unsigned walkSteps = 0;   // parked: DDA steps of this walk, all lanes (wave-uniform)
+            float sm0 = st0 * mv;     // sigma_maj[0] of the cell mv belongs to, carried with it
             for (int b = 0; b < P.dda_budget; ++b) {
-                [[maybe_unused]] bool stepped = false;
-                if (walk == 0 && needNext) {
-                    float s0, s1;
-                    if (!ddal_next(it, majp, maj_sy, maj_sz, &s0, &s1, &mv)) {
-                        walk = 2;
-                    } else {
-                        stepped = true;
-                        // zero-majorant cell: T_maj *= FastExp(-0 * dt); for a gray medium that
-                        // factor is exactly 1, so the multiply is skipped
-                        const S sigma_maj = sig_t * mv;
+                const bool wantNext = walk == 0 && needNext;
+                const bool stepped = wantNext && !ddal_done(it);
+                walk = wantNext && !stepped ? 2 : walk;
+                if constexpr (kParked) walkSteps += (unsigned)__popcll(__ballot(stepped));
+                if (stepped) {
+                    float s0, s1, mc;
+                    ddal_step(it, maj_sy, maj_sz, &s0, &s1, &mc);
+                    if constexpr (!kParked) ++nStepsLane;
+                    mv = mc;
+                    // zero-majorant cell: T_maj *= FastExp(-0 * dt); for a gray medium that
+                    // factor is exactly 1, so the multiply is skipped
+                    const S sigma_maj = sig_t * mc;
+                    sm0 = sv0(sigma_maj);
+                    const bool open = sm0 != 0;
 #ifdef AVR_PROBE_STATS
-                        { const uint64_t z = __ballot(sv0(sigma_maj) == 0); AVR_PROBE(6, __popcll(z)) }
+                    { const uint64_t z = __ballot(!open); AVR_PROBE(6, __popcll(z)) }
 #endif
-                        if (sv0(sigma_maj) == 0) {
-                            if (!kGray) {
-                                float dt = s1 - s0;
-                                if (__builtin_isinf(dt)) dt = kFloatMax;
-                                T_maj = T_maj * sexpm<kFast>(-(sigma_maj * dt));
-                            }
-                        } else {
-                            tMin = s0;
-                            segMax = s1;
-                            needNext = false;
+                    if constexpr (!kGray) {
+                        if (!open) {
+                            float dt = s1 - s0;
+                            if (__builtin_isinf(dt)) dt = kFloatMax;
+                            T_maj = T_maj * sexpm<kFast>(-(sigma_maj * dt));
                         }
                     }
+                    tMin = open ? s0 : tMin;
+                    segMax = open ? s1 : segMax;
+                    needNext = !open;
                 }
-                nStepsW += __popcll(__ballot(stepped));
                 // unconditional (all busy lanes): in flight during the candidate test below
                 // (the next cell's index is unclamped: LDS for the 16^3 majorants, a bounds-checked
                 // buffer for NanoVDB's and the parked instantiations' — +0.9 % grid, +2.2 % NanoVDB,
@@ -3041,12 +3069,12 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                 } else {
                     ddal_prefetch(it, majp);
                 }
-                if (walk == 0 && !needNext) {
+                {
                     // Fast reject: the candidate t = tMin - log(1-u)/sigma_maj is decided against
                     // segMax from T_maj's own FastExp factor when 1-u lies outside an error margin
                     // (below); accepted and ambiguous candidates stay "pending" and are decided
                     // exactly, once per wave, after the walk.
-                    const float sm0 = st0 * mv;
+                    const bool cand = walk == 0 && !needNext;
                     bool pending;
                     float dt = segMax - tMin;
                     // T_maj's factor should the candidate be rejected (media.h:790-801). Replay,
@@ -3056,9 +3084,11 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                     // +3.0 % NanoVDB, profiles/r06_ab_walk.json)
                     constexpr bool kLite = kGray && !kFast;
                     if (!kLite && __builtin_isinf(dt)) dt = kFloatMax;
-                    S fac;
-                    if constexpr (kLite) fac = fast_exp_m40(-((sig_t * mv) * dt));
-                    else fac = sexpm<kFast>(-((sig_t * mv) * dt));
+                    S sigm, fac;
+                    if constexpr (kGray) sigm = sconst<S>(sm0);   // gray: sig_t * mv is sm0's product
+                    else sigm = sig_t * mv;
+                    if constexpr (kLite) fac = fast_exp_m40(-(sigm * dt));
+                    else fac = sexpm<kFast>(-(sigm * dt));
                     if constexpr (kFast) {
                         // fast mode: the hardware candidate is the candidate (decided once)
                         pending = tMin + m_exp_dist<true>(u, sm0) < segMax;
@@ -3071,18 +3101,27 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                         const float A = sm0 * dt;
                         pending = !(A < 40.f && (1 - u) <= sv0(fac) * (1 - 1e-3f - 5e-7f * A));
                     }
-                    if (pending) {
-                        walk = 1;
-                    } else {
-                        u = rng.uniform();
-                        T_maj = T_maj * fac;
-                        needNext = true;
-                    }
+                    // a rejected candidate consumes its draw and closes the cell
+                    const bool reject = cand && !pending;
+                    Pcg32 drawn = rng;
+                    const float uNext = drawn.uniform();
+                    walk = cand && pending ? 1 : walk;
+                    u = reject ? uNext : u;
+                    rng.state = reject ? drawn.state : rng.state;
+                    if (reject) T_maj = T_maj * fac;
+                    needNext = needNext || reject;
                 }
                 const uint64_t walking = __ballot(walk == 0);
                 AVR_PROBE(0, 1)
                 AVR_PROBE(1, __popcll(walking))
                 if (walking == 0) break;
+            }
+            // parked: the walk's DDA steps, one LDS add per walk by the first active lane
+            if constexpr (kParked) {
+                if (walkSteps) {
+                    const uint64_t am = __ballot(1);
+                    if (lane_id() == __ffsll((long long)am) - 1) atomicAdd(wcnt + 5, walkSteps);
+                }
             }
             AVR_SEC(4)
 #ifdef AVR_PROBE_STATS
@@ -3146,7 +3185,10 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
                         AVR_PROBE_LINES(5, ProbeStats::distinct(ent >> 1))
                     }
 #endif
-                    dens = grid_density(m, pm);
+                    // parked: the fat layout, at compile time (the host launches a parked
+                    // instantiation for a medium with a fat copy only: avr::kp::select)
+                    if constexpr (kParked) dens = fat_lookup<true>(m.fat, m.nx, m.ny, m.nz, pm, m.fn);
+                    else dens = grid_density(m, pm);
                 }
                 ms_a = sig_a * dens;
                 ms_s = sig_s * dens;
@@ -3233,8 +3275,8 @@ __global__ void __launch_bounds__(256, (kpaths_waves<kEmissive, kGray, kMed, kIm
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 5 && wcnt[lane]) atomicAdd(P.stats + lane, (unsigned long long)wcnt[lane]);
-    if (lane == 0 && nStepsW) atomicAdd(P.stats + 5, nStepsW);
+    if (lane < 6 && wcnt[lane]) atomicAdd(P.stats + lane, (unsigned long long)wcnt[lane]);
+    if constexpr (!kParked) flush_stat(P.stats, 5, nStepsLane);
 #undef AVR_COUNT
     if (lane == 0) {   // wave-uniform counters: one add per wave
         if (nIter) atomicAdd(P.stats + 8, nIter);

@@ -37,12 +37,21 @@ void alias_rgb_gray(T *table) {
 // (kind 0 independent, 1 ZSobol; wide: the 64-bit index) as template arguments
 constexpr int medium_arg(int medium_type) { return medium_type == 3 ? 3 : (medium_type == 4 ? 4 : (medium_type == 1 || medium_type == 2 ? 1 : 0)); }
 constexpr int sampler_arg(int sampler_kind, bool wide) { return sampler_kind == 0 ? 0 : (wide ? 3 : 2); }
+// The parked instantiations (template arguments as the list spells them): gray GridMedium without
+// emission or image light. They read the density through the fat layout alone, fixed at compile
+// time (k_paths' collision block).
+constexpr bool parked(bool emissive, bool gray, int medium_arg, bool image) {
+    return gray && medium_arg == 0 && !emissive && !image;
+}
 // The slot a render launches. image: image lights or the power light sampler (the kImage
 // instantiation also carries the latter's pick); gray: sigma_a and sigma_s constant over all
-// wavelengths
-constexpr int select(bool fast, bool image, int medium_type, int sampler_kind, bool wide, bool emissive, bool gray) {
-    return slot(fast, image, medium_index(medium_arg(medium_type)), sampler_index(sampler_arg(sampler_kind, wide)),
-                emissive, gray);
+// wavelengths; fat: a GridMedium's density has its fat copy (the default layout). A medium that
+// would run a parked instantiation but has the linear or the bricked layout runs the general
+// instantiation beside it instead (kImage: every light kind, every layout at run time).
+constexpr int select(bool fast, bool image, int medium_type, int sampler_kind, bool wide, bool emissive, bool gray,
+                     bool fat = true) {
+    return slot(fast, image || (!fat && parked(emissive, gray, medium_arg(medium_type), image)),
+                medium_index(medium_arg(medium_type)), sampler_index(sampler_arg(sampler_kind, wide)), emissive, gray);
 }
 
 }  // namespace kp

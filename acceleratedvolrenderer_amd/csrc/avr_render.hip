@@ -386,7 +386,8 @@ static int pass_camera_stage(avr_context *c, avr::Params *p, bool cam_ahead, int
 static int pass_kpaths(avr_context *c, const avr::Params &p, bool cam_next, int *variant, int *end) {
     EV_MARK(e0);
     const int kv = avr::kp::select(c->render_mode != 0, c->n_image_lights > 0 || c->lights.mode != avr::kPickInfinite, c->med.type,
-                                   c->sampler_kind, avr::smp::zsobol_wide(p.zs), c->med.emissive != 0, c->gray);
+                                   c->sampler_kind, avr::smp::zsobol_wide(p.zs), c->med.emissive != 0, c->gray,
+                                   c->med.fat != nullptr);
     const bool hold = cam_next && c->paths_grid[kv] > 4 * c->num_cus;
     hipLaunchKernelGGL(c->kpaths[kv], dim3(hold ? 4 * c->num_cus : c->paths_grid[kv]), dim3(256),
                        hold ? kOverlapLdsPad : 0, c->stream, p);
@@ -595,12 +596,12 @@ extern "C" int avr_render(avr_context *c, int spp_begin, int spp_end, int seed, 
                             c->med.mres[0] <= 255 && c->med.mres[1] <= 255 && c->med.mres[2] <= 255;
     if ((r = pass_plan(c, persistent, spp_begin, spp_end, &rc.plan))) return r;
     if ((r = persistent ? ensure_records(c, rc.plan.need) : ensure_paths(c, rc.plan.need))) return r;
-    // Pass overlap: only the parked k_paths instantiations (gray non-emissive GridMedium without
-    // image lights) leave a block of the camera stage room beside four of their own on a CU;
+    // Pass overlap: only the parked k_paths instantiations (gray non-emissive GridMedium in the fat
+    // layout without image lights) leave a block of the camera stage room beside four of their own on a CU;
     // only on the context's own stream (the side stream is ordered against it by events), and
     // only behind the ZSobol pass table built ahead
     rc.overlap_ok = persistent && c->pass_overlap && c->ptab_spec && c->sampler_kind == 1 &&
-                    c->stream == c->own_stream && c->gray && c->med.type == 0 && !c->med.emissive &&
+                    c->stream == c->own_stream && c->gray && c->med.type == 0 && !c->med.emissive && c->med.fat != nullptr &&
                     c->n_image_lights == 0 && c->lights.mode == avr::kPickInfinite;
     if (rc.overlap_ok) ensure_alt(c);
     EV_MARK(evStart);
