@@ -22,6 +22,7 @@ AVR_KP_ALL(AVR_KP_DECL)
 }  // namespace avr
 #endif
 #include "avr_graph.hip"
+#include "avr_devmem.h"
 #include "../../include/avr.h"
 
 #include <rccl/rccl.h>
@@ -49,38 +50,62 @@ int fail(int code, const std::string &msg) {
             return fail(AVR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
     } while (0)
 
-template <typename T>
-hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)); }
-
 }  // namespace
+
+using avr::devmem::Arena;
+using avr::devmem::Buffer;
 
 // The camera set: k_paths' per-sample records, its camera stage's buffers (PathSoA's rec, cam0..5,
 // camw) and the work heads the stage resets. The one place that lists them.
 struct CameraSet {
-    float4 *rec = nullptr, *cam0 = nullptr, *cam1 = nullptr, *cam2 = nullptr, *cam4 = nullptr;
-    uint4 *cam3 = nullptr, *cam5 = nullptr;
-    float *camw = nullptr;
-    int *heads = nullptr;   // 8 per-XCD work counters of k_paths + the pass generation
+    Buffer<float4> rec, cam0, cam1, cam2, cam4;
+    Buffer<uint4> cam3, cam5;
+    Buffer<float> camw;
+    Buffer<int> heads;   // 8 per-XCD work counters of k_paths + the pass generation
     template <typename F>
     void each_buffer(F f) { f(rec); f(cam0); f(cam1); f(cam2); f(cam3); f(cam4); f(cam5); f(camw); }
     // point a launch's arguments at this set
     void point(avr::Params &p) const {
-        p.ps.rec = rec; p.ps.camw = camw; p.heads = heads;
-        p.ps.cam0 = cam0; p.ps.cam1 = cam1; p.ps.cam2 = cam2; p.ps.cam3 = cam3; p.ps.cam4 = cam4; p.ps.cam5 = cam5;
+        p.ps.rec = rec.get(); p.ps.camw = camw.get(); p.heads = heads.get();
+        p.ps.cam0 = cam0.get(); p.ps.cam1 = cam1.get(); p.ps.cam2 = cam2.get(); p.ps.cam3 = cam3.get();
+        p.ps.cam4 = cam4.get(); p.ps.cam5 = cam5.get();
     }
-    // the eight per-sample buffers for n samples (on failure, those allocated stay for free_buffers)
+    // the eight per-sample buffers for n samples (on failure, those allocated stay for free_buffers;
+    // each_buffer visits every one, so the chain is what stops at the first failure)
     hipError_t alloc_buffers(size_t n) {
         hipError_t e = hipSuccess;
-        each_buffer([&](auto *&p) { if (e == hipSuccess) e = dalloc(&p, n); });
+        each_buffer([&](auto &b) { if (e == hipSuccess) e = b.alloc(n); });
         return e;
     }
     // heads that no pass generation matches
     hipError_t alloc_heads() {
-        hipError_t e = dalloc(&heads, 9);
-        return e == hipSuccess ? hipMemset(heads, 0xff, 9 * sizeof(int)) : e;
+        const hipError_t e = heads.alloc(9);
+        return e == hipSuccess ? hipMemset(heads.get(), 0xff, 9 * sizeof(int)) : e;
     }
-    void free_buffers() { each_buffer([](auto *&p) { if (p) (void)hipFree(p); p = nullptr; }); }
-    void free_heads() { if (heads) (void)hipFree(heads); heads = nullptr; }
+    void free_buffers() { each_buffer([](auto &b) { b.reset(); }); }
+    void free_heads() { heads.reset(); }
+};
+
+// The wavefront kernels' path state (PathSoA, ShadowSoA) and queues, one buffer per array
+struct PathBuffers {
+    Buffer<float4> o, d, lambda, pdf, beta, r_u, r_l, L, sh_o, sh_d, sh_bf, sh_Ls, sh_rp;
+    Buffer<uint64_t> smp_state, smp_inc;
+    Buffer<int> depth, sh_path, queue[2];
+    Buffer<float> weight;
+    Buffer<float2> sh_pdfs;
+    template <typename F>
+    void each_buffer(F f) {
+        f(o); f(d); f(lambda); f(pdf); f(beta); f(r_u); f(r_l); f(L); f(smp_state); f(smp_inc); f(depth); f(weight);
+        f(sh_path); f(sh_o); f(sh_d); f(sh_bf); f(sh_Ls); f(sh_rp); f(sh_pdfs); f(queue[0]); f(queue[1]);
+    }
+    // the kernels' views (the k_paths records and camera stage are not in them: CameraSet)
+    void point(avr::PathSoA &ps, avr::ShadowSoA &sh) const {
+        ps = {};
+        ps.o = o.get(); ps.d = d.get(); ps.lambda = lambda.get(); ps.pdf = pdf.get(); ps.beta = beta.get();
+        ps.r_u = r_u.get(); ps.r_l = r_l.get(); ps.L = L.get(); ps.smp_state = smp_state.get();
+        ps.smp_inc = smp_inc.get(); ps.depth = depth.get(); ps.weight = weight.get();
+        sh = {sh_path.get(), sh_o.get(), sh_d.get(), sh_bf.get(), sh_Ls.get(), sh_rp.get(), sh_pdfs.get()};
+    }
 };
 
 constexpr int kPtabKey = 8;   // what a built ZSobol pass table depends on (ptab_key)
@@ -158,31 +183,37 @@ struct avr_context {
     long long max_paths = 16ll << 20;
     bool max_paths_set = false;
     long long rec_cap = 0;   // k_paths records and camera stage allocated (samples)
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    // The streams and events come before every device buffer: members go in reverse order, so the
+    // buffers are freed (avr_context_destroy: on the context's device, both streams drained)
+    // before the streams are destroyed. tstream, ev_cam, ev_tab: the side stream (LookAhead).
+    avr::devmem::Stream own_stream, tstream;
+    hipStream_t stream = nullptr;
+    avr::devmem::Event ev_cam, ev_tab;
+    std::vector<avr::devmem::Event> evpool;   // timing events; the first ev_used are recorded, unresolved
     // medium
     avr::DevMedium med{};
-    float *d_density_owned = nullptr;
-    float *d_sigma_a = nullptr, *d_sigma_s = nullptr, *d_Le = nullptr, *d_lescale = nullptr, *d_majorant = nullptr;
+    Buffer<float> d_density_owned;
+    Buffer<float> d_sigma_a, d_sigma_s, d_Le, d_lescale, d_majorant;
     bool has_medium = false;
     // lights / camera / film
     avr::DevLights lights{};
-    float *d_lightL = nullptr;
-    avr::DevLight *d_lights = nullptr;
+    Buffer<float> d_lightL;
+    Buffer<avr::DevLight> d_lights;
     avr::DevCamera cam{};
     bool has_camera = false;
-    avr::DevFilm film{};
-    float *d_xyz = nullptr;
+    avr::DevFilm film{};   // its sums: d_film_rgb, d_film_w, d_film_bucket ({bucket_sum, bucket_w})
+    Buffer<double> d_film_rgb, d_film_w, d_film_bucket;
+    Buffer<float> d_xyz;
     bool has_film = false;
     // path state
     long long cap = 0;
     avr::PathSoA ps{};
     avr::ShadowSoA sh{};
-    int *d_queue[2] = {nullptr, nullptr};
-    int *d_counts = nullptr;  // [0],[1] queue counts, [2] shadow count
-    unsigned long long *d_stats = nullptr;
-    int *h_count = nullptr;   // pinned
+    PathBuffers paths;
+    Buffer<int> d_counts;  // [0],[1] queue counts, [2] shadow count
+    Buffer<unsigned long long> d_stats;
+    avr::devmem::PinnedInts h_count;
     avr_stats stats{};
-    std::vector<hipEvent_t> evpool;   // timing events; the first ev_used are recorded, unresolved
     size_t ev_used = 0;
     struct Timed { int a, b; double avr_stats::*field; bool launch; };
     std::vector<Timed> timed;         // pending (event a -> event b) intervals to fold into stats
@@ -191,7 +222,7 @@ struct avr_context {
     int pass_gen = 0;         // k_paths passes enqueued (the camera stage stamps it into its set's heads[8])
     // k_paths' pixel order (avr_set_pixel_order): slot -> pixel and pixel -> slot, and the
     // host copy of the latter (to return the last pass in pixel order); empty = scanline
-    int *d_pix_order = nullptr, *d_pix_slot = nullptr;
+    Buffer<int> d_pix_order, d_pix_slot;
     std::vector<int> h_pix_slot;
     // bumped whenever the pixel order changes (avr_set_pixel_order, avr_film); the last
     // render's records are in the order of generation last.order_gen
@@ -204,24 +235,23 @@ struct avr_context {
     int render_mode = 0;      // 0 replay (canonical math, per-sample parity), 1 fast (hardware math)
     int ray_binning = 0;      // wavefront organisation: counting-sort queues by (majorant cell, octant)
     int majorant_occupancy = 0;   // NanoVDB k_paths: coarse occupancy level of the majorant in LDS (opt-in)
-    unsigned *d_occ = nullptr;
-    float4 *d_planes = nullptr;   // convex interface half-spaces (avr_medium_boundary_convex)
-    int *d_bin_keys = nullptr, *d_bin_out = nullptr, *d_bin_hist = nullptr;
-    long long bin_cap = 0;
+    Buffer<unsigned> d_occ;
+    Buffer<float4> d_planes;   // convex interface half-spaces (avr_medium_boundary_convex)
+    Buffer<int> d_bin_keys, d_bin_out, d_bin_hist;
     // pixel sampler (avr_set_sampler) and filter (avr_set_filter)
     int sampler_kind = 0;     // 0 IndependentSampler, 1 ZSobolSampler
     int sampler_spp = 16;     // samplesPerPixel of the sampler (ZSobol's Morton layout)
     int filter_type = 0;      // 0 BoxFilter (radius from avr_film), 1 GaussianFilter
-    float *d_filter = nullptr;
-    float *d_temperature = nullptr;
+    Buffer<float> d_filter;
+    Buffer<float> d_temperature;
     // NanoVDBMedium grids (0 density, 1 temperature): block slots, leaves, tile values
-    int *d_vdb_slot[2] = {nullptr, nullptr};
-    float *d_vdb_leaves[2] = {nullptr, nullptr}, *d_vdb_tiles[2] = {nullptr, nullptr};
+    Buffer<int> d_vdb_slot[2];
+    Buffer<float> d_vdb_leaves[2], d_vdb_tiles[2];
     int vdb_ibbox[6] = {};    // density grid's active index bbox (majorant clamp)
     long long vdb_napron[2] = {0, 0};   // apron blocks of the density / temperature grid
     // RGBGridMedium grids (sigma_a, sigma_s, Le as float4 {c0, c1, c2, scale}) and illuminant
-    float4 *d_rgb[3] = {nullptr, nullptr, nullptr};   // owned copies (avr_medium_rgbgrid only)
-    float *d_illum = nullptr;
+    Buffer<float4> d_rgb[3];   // owned copies (avr_medium_rgbgrid only)
+    Buffer<float> d_illum;
     // lights: host copy of the device list, ImageInfiniteLight buffers
     avr::DevLight h_lights[avr::kMaxLights] = {};
     // PowerLightSampler: each light's Phi-based weight (phi_ok once known: an image light's
@@ -229,7 +259,7 @@ struct avr_context {
     float h_phi[avr::kMaxLights] = {};
     bool phi_ok[avr::kMaxLights] = {};
     int light_sampler = 0;
-    void *d_light_img[avr::kMaxLights] = {};
+    Buffer<unsigned char> d_light_img[avr::kMaxLights];
     int n_image_lights = 0;
     // PointLight / SpotLight: how many the list holds, which have their avr_light_local, their
     // renderFromLight (4x4; the device record keeps the position and lightFromRender's 3x3), the
@@ -240,30 +270,26 @@ struct avr_context {
     std::vector<float> h_lightL;
     avr::ll::Tree h_tree{};
     // film image / --mse-reference-image state
-    float *d_image = nullptr, *d_reference = nullptr;
-    double *d_metric = nullptr;      // kMetricBlocks * kMetricSlots partials + kMetricSlots totals
+    Buffer<float> d_image, d_reference;
+    Buffer<double> d_metric;      // kMetricBlocks * kMetricSlots partials + kMetricSlots totals
     avr::Mat3 ref_out_from_sensor{};
     int ref_fp16 = 1;
     avr::smp::FilterTables ftab{};
     // ZSobol pixel table (zsobol_upper per Morton(pixel) x dimension < zs_dims), rebuilt
     // when the sampler's spp or the film resolution change; zs_dims 0 = no table
-    uint32_t *d_zs_table = nullptr;
+    Buffer<uint32_t> d_zs_table;
     int zs_dims = 256;
     int zs_key[3] = {-1, -1, -1};
     // ZSobol pass table (zsobol_pass_entry per Morton(pixel) x dimension < zs_pdims), rebuilt
     // for every k_paths pass: the digits its sample indices share; zs_pdims 0 = no table
     // Two buffers: a pass reads one while the next pass's table is built ahead into the other
     // (ptab_spec) on the low-priority side stream tstream
-    uint64_t *d_zs_ptab[2] = {};
-    size_t zs_ptab_cap[2] = {};   // entries allocated
-    uint64_t *d_zs_ctab[2] = {};  // the camera stage's compact copy (6 entries per pixel)
-    size_t zs_ctab_cap[2] = {};
+    Buffer<uint64_t> d_zs_ptab[2];
+    Buffer<uint64_t> d_zs_ctab[2];  // the camera stage's compact copy (6 entries per pixel)
     int zs_pdims = 96;
     int tab_buf = 1;              // the buffer the last pass read
     int ptab_spec = 1;            // avr_set_pass_table_ahead
     LookAhead look;               // what tstream holds (or is building) for the next pass
-    hipStream_t tstream = nullptr;
-    hipEvent_t ev_cam = nullptr, ev_tab = nullptr;
     long long prev_call_begin = -1;   // avr_render's previous spp_begin (the call stride)
     // Pass overlap (avr_set_pass_overlap): behind the table built ahead, tstream also runs the
     // next pass's camera stage, into the other camera set (alt; set always names the set of the
@@ -279,18 +305,16 @@ struct avr_context {
     unsigned long long cfg_gen = 0;
     // Level-A pass table (the same table for plo + 2, shared by four consecutive passes);
     // zs_akey names the build it holds (rebuilt when any field changes)
-    uint64_t *d_zs_atab = nullptr;
-    size_t zs_atab_cap = 0;
+    Buffer<uint64_t> d_zs_atab;
     long long zs_akey[6] = {-1, -1, -1, -1, -1, -1};
     int refill_min = 0;       // 0: the default (32 lanes; 20 for a non-emissive NanoVDB walk, 16 for RGB grids, 48 for a <= 2^3 GridMedium majorant)
     int refill_batch = 0;     // 0: the default of the medium kind (walk_schedule)
     int dda_budget = 0;       // 0: by majorant resolution (12 cells up to 16^3, 32 for NanoVDB's 64^3)
     int grid_layout = 1;
     bool gray = false;        // sigma_a and sigma_s constant over 360..830 nm      // 1: build the fat (footprint) copy when memory allows, 0: linear only
-    float4 *d_fat = nullptr;
-    float *d_brick = nullptr;   // bricked GridMedium copy (grid_layout 2)
-    uint64_t *d_advance = nullptr;  // per-pass PCG advance table {A, H}
-    long long advance_cap = 0;
+    Buffer<float4> d_fat;
+    Buffer<float> d_brick;   // bricked GridMedium copy (grid_layout 2)
+    Buffer<uint64_t> d_advance;  // per-pass PCG advance table {A, H}
     // avr_film_reduce_rccl: this context's communicator and the clique (contexts in rank
     // order) it was created with by ncclCommInitAll; reused while the same clique reduces
     ncclComm_t comm = nullptr;
@@ -299,25 +323,22 @@ struct avr_context {
     // used, named by the index's id (an address could be reused by a later index); one
     // allocation behind gidx's pointers. d_gside: the pass's {scatter point, neighbour count}.
     unsigned long long gidx_uid = 0;
-    char *d_gidx = nullptr;
+    Buffer<char> d_gidx;
     avr::graph::IndexView gidx{};
-    float4 *d_gside = nullptr;
-    long long gside_cap = 0;
+    Buffer<float4> d_gside;
     // the uniform graph's table (avr_graph_render_uniform, avr_graph_uniform_*_device): the device
     // copy of the last one used, under the graph's id as gidx is
     unsigned long long guni_uid = 0;
-    avr::graph::UniformEntry *d_guni = nullptr;
+    Buffer<avr::graph::UniformEntry> d_guni;
     avr::graph::UniformView guni{};
     // the graph tools' primitive (avr_graph_set_geometry): 0 the bounds box, 1 the interface
     int graph_geometry = 0;
     // graph analysis (avr_graph_analyze): the pass's per-sample records, the per-pixel sums
     // (made by the first analysis on a film, dropped with the film) and, only when a call asks
-    // for it, the pass's per-scatter detail (adetail_cap entries)
-    avr::graph::AnalyzeRec *d_arec = nullptr;
-    long long arec_cap = 0;
-    avr::graph::AnalyzeAcc *d_aacc = nullptr;
-    avr::graph::AnalyzeDetail *d_adetail = nullptr;
-    size_t adetail_cap = 0;
+    // for it, the pass's per-scatter detail
+    Buffer<avr::graph::AnalyzeRec> d_arec;
+    Buffer<avr::graph::AnalyzeAcc> d_aacc;
+    Buffer<avr::graph::AnalyzeDetail> d_adetail;
 };
 
 namespace {
@@ -339,16 +360,7 @@ void release_comms(avr_context *c) {
 }
 
 void free_paths(avr_context *c) {
-    float4 *f4[] = {c->ps.o, c->ps.d, c->ps.lambda, c->ps.pdf, c->ps.beta, c->ps.r_u, c->ps.r_l, c->ps.L,
-                    c->sh.o, c->sh.d, c->sh.bf, c->sh.Ls, c->sh.rp};
-    for (auto p : f4) if (p) (void)hipFree(p);
-    if (c->ps.smp_state) (void)hipFree(c->ps.smp_state);
-    if (c->ps.smp_inc) (void)hipFree(c->ps.smp_inc);
-    if (c->ps.depth) (void)hipFree(c->ps.depth);
-    if (c->ps.weight) (void)hipFree(c->ps.weight);
-    if (c->sh.path) (void)hipFree(c->sh.path);
-    if (c->sh.pdfs) (void)hipFree(c->sh.pdfs);
-    for (auto &q : c->d_queue) if (q) (void)hipFree(q), q = nullptr;
+    c->paths.each_buffer([](auto &b) { b.reset(); });
     // (the k_paths records and camera stage are not in ps: c->set, managed by ensure_records)
     c->ps = {};
     c->sh = {};
@@ -357,9 +369,8 @@ void free_paths(avr_context *c) {
 
 void free_pixel_order(avr_context *c) {
     if (c->d_pix_order) ++c->order_gen;   // back to scanline order
-    if (c->d_pix_order) (void)hipFree(c->d_pix_order);
-    if (c->d_pix_slot) (void)hipFree(c->d_pix_slot);
-    c->d_pix_order = c->d_pix_slot = nullptr;
+    c->d_pix_order.reset();
+    c->d_pix_slot.reset();
     c->h_pix_slot.clear();
 }
 
@@ -377,6 +388,32 @@ void free_records(avr_context *c) {
     c->set.free_buffers();
     c->rec_cap = 0;
     free_alt(c);
+}
+
+// The film's sums (they go with the film, its pixel bounds or, the bucket sums, its buckets)
+void free_film_sums(avr_context *c) {
+    c->d_film_rgb.reset();
+    c->d_film_w.reset();
+    c->d_film_bucket.reset();
+    c->film.rgb_sum = c->film.w_sum = c->film.bucket_sum = c->film.bucket_w = nullptr;
+}
+
+// ... for the film's bounds and buckets
+int alloc_film_sums(avr_context *c) {
+    const size_t np = (size_t)c->film.bw * c->film.bh;
+    if (!c->d_film_rgb) {
+        HIP_TRY(c->d_film_rgb.alloc(3 * np));
+        HIP_TRY(c->d_film_w.alloc(np));
+        c->film.rgb_sum = c->d_film_rgb.get();
+        c->film.w_sum = c->d_film_w.get();
+    }
+    if (c->film.nbuckets > 0) {
+        const size_t nb = np * c->film.nbuckets;
+        HIP_TRY(c->d_film_bucket.alloc(2 * nb));
+        c->film.bucket_sum = c->d_film_bucket.get();
+        c->film.bucket_w = c->film.bucket_sum + nb;
+    }
+    return AVR_OK;
 }
 
 // ... as large as the first set. Without room for it the passes keep the serial chain (no error).
@@ -401,33 +438,13 @@ int ensure_records(avr_context *c, long long n) {
     return AVR_OK;
 }
 
-// Grow a device buffer to n entries (contents are not kept). drain: queued kernels may still
-// read the old one, so the stream is drained before it is freed.
-template <typename T, typename N>
-int grow(avr_context *c, T **p, N *cap, N n, bool drain = true) {
-    if (n <= *cap) return AVR_OK;
-    if (drain) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(dalloc(p, (size_t)n));
-    *cap = n;
-    return AVR_OK;
-}
-
 int ensure_paths(avr_context *c, long long n) {
     if (n <= c->cap) return AVR_OK;
     free_paths(c);
-    const size_t N = (size_t)n;
-    HIP_TRY(dalloc(&c->ps.o, N)); HIP_TRY(dalloc(&c->ps.d, N)); HIP_TRY(dalloc(&c->ps.lambda, N));
-    HIP_TRY(dalloc(&c->ps.pdf, N)); HIP_TRY(dalloc(&c->ps.beta, N)); HIP_TRY(dalloc(&c->ps.r_u, N));
-    HIP_TRY(dalloc(&c->ps.r_l, N)); HIP_TRY(dalloc(&c->ps.L, N));
-    HIP_TRY(dalloc(&c->ps.smp_state, N)); HIP_TRY(dalloc(&c->ps.smp_inc, N)); HIP_TRY(dalloc(&c->ps.depth, N));
-    HIP_TRY(dalloc(&c->ps.weight, N));
-    HIP_TRY(dalloc(&c->sh.path, N)); HIP_TRY(dalloc(&c->sh.o, N)); HIP_TRY(dalloc(&c->sh.d, N));
-    HIP_TRY(dalloc(&c->sh.bf, N)); HIP_TRY(dalloc(&c->sh.Ls, N)); HIP_TRY(dalloc(&c->sh.rp, N));
-    HIP_TRY(dalloc(&c->sh.pdfs, N));
-    HIP_TRY(dalloc(&c->d_queue[0], N)); HIP_TRY(dalloc(&c->d_queue[1], N));
+    hipError_t e = hipSuccess;   // (each_buffer visits every array: the chain stops at the first failure)
+    c->paths.each_buffer([&](auto &b) { if (e == hipSuccess) e = b.alloc((size_t)n); });
+    HIP_TRY(e);
+    c->paths.point(c->ps, c->sh);
     c->cap = n;
     return AVR_OK;
 }
@@ -436,11 +453,11 @@ void copy_xf(avr::Xf &x, const float m[16]) {
     for (int i = 0; i < 12; ++i) x.m[i] = m[i];
 }
 
-int upload_table(float **dst, const float *src, size_t n, hipStream_t s) {
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
+int upload_table(Buffer<float> &dst, const float *src, size_t n, hipStream_t s) {
+    dst.reset();
     if (!src) return AVR_OK;
-    HIP_TRY(dalloc(dst, n));
-    HIP_TRY(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(dst.alloc(n));
+    HIP_TRY(hipMemcpyAsync(dst.get(), src, n * sizeof(float), hipMemcpyHostToDevice, s));
     return AVR_OK;
 }
 
@@ -453,19 +470,17 @@ int blocks_for(long long n, int per = 256, int cap = 256 * 16) {
 bool affine(const float m[16]) { return m[12] == 0 && m[13] == 0 && m[14] == 0 && m[15] == 1; }
 
 void free_rgb(avr_context *c) {
-    for (auto &p : c->d_rgb) if (p) (void)hipFree(p), p = nullptr;
-    if (c->d_illum) (void)hipFree(c->d_illum), c->d_illum = nullptr;
+    for (auto &b : c->d_rgb) b.reset();
+    c->d_illum.reset();
     c->med.rgb_a = c->med.rgb_s = c->med.rgb_le = nullptr;
     c->med.illuminant = nullptr;
 }
 
 void free_vdb(avr_context *c) {
     for (int k = 0; k < 2; ++k) {
-        if (c->d_vdb_slot[k]) (void)hipFree(c->d_vdb_slot[k]);
-        if (c->d_vdb_leaves[k]) (void)hipFree(c->d_vdb_leaves[k]);
-        if (c->d_vdb_tiles[k]) (void)hipFree(c->d_vdb_tiles[k]);
-        c->d_vdb_slot[k] = nullptr;
-        c->d_vdb_leaves[k] = c->d_vdb_tiles[k] = nullptr;
+        c->d_vdb_slot[k].reset();
+        c->d_vdb_leaves[k].reset();
+        c->d_vdb_tiles[k].reset();
     }
     c->med.vdb = {};
     c->med.vdb_temp = {};
@@ -561,50 +576,45 @@ int upload_vdb(avr_context *c, const avr_vdb_grid *G, int k, avr::vdb::Apron &g)
     std::vector<float> consts((size_t)G->n_tiles + 1);
     for (int t = 0; t < G->n_tiles; ++t) consts[t] = G->tile_value[t];
     consts[G->n_tiles] = G->background;
-    struct Tmp {
-        int *slot = nullptr;
-        float *leaves = nullptr, *tiles = nullptr;
-        long long *list = nullptr;
-        ~Tmp() {
-            if (slot) (void)hipFree(slot);
-            if (leaves) (void)hipFree(leaves);
-            if (tiles) (void)hipFree(tiles);
-            if (list) (void)hipFree(list);
-        }
-    } tmp;
-    HIP_TRY(dalloc(&tmp.slot, slot.size()));
-    HIP_TRY(hipMemcpyAsync(tmp.slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // (declared after the host vectors: it drains the stream before they go, on every return)
+    Arena<> tmp(c->stream);
     const size_t nleaf = (size_t)G->n_leaves * 512;
-    HIP_TRY(dalloc(&tmp.leaves, std::max<size_t>(nleaf, 1)));
+    const auto rSlot = tmp.reserve<int>(slot.size());
+    const auto rLeaves = tmp.reserve<float>(nleaf);
+    const auto rTiles = tmp.reserve<float>((size_t)G->n_tiles);
+    const auto rList = tmp.reserve<long long>(list.size());
+    HIP_TRY(tmp.commit());
+    HIP_TRY(hipMemcpyAsync(tmp.get(rSlot), slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (nleaf)
-        HIP_TRY(hipMemcpyAsync(tmp.leaves, G->leaf_values, nleaf * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(dalloc(&tmp.tiles, std::max<size_t>((size_t)G->n_tiles, 1)));
+        HIP_TRY(hipMemcpyAsync(tmp.get(rLeaves), G->leaf_values, nleaf * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (G->n_tiles)
-        HIP_TRY(hipMemcpyAsync(tmp.tiles, G->tile_value, G->n_tiles * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    base.slot = tmp.slot;
-    base.leaves = tmp.leaves;
-    base.tiles = tmp.tiles;
-    HIP_TRY(dalloc(&c->d_vdb_slot[k], aslot.size()));
-    HIP_TRY(hipMemcpyAsync(c->d_vdb_slot[k], aslot.data(), aslot.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(dalloc(&c->d_vdb_tiles[k], consts.size()));
-    HIP_TRY(hipMemcpyAsync(c->d_vdb_tiles[k], consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(tmp.get(rTiles), G->tile_value, G->n_tiles * sizeof(float), hipMemcpyHostToDevice,
+                               c->stream));
+    base.slot = tmp.get(rSlot);
+    base.leaves = tmp.get(rLeaves);
+    base.tiles = tmp.get(rTiles);
+    HIP_TRY(c->d_vdb_slot[k].alloc(aslot.size()));
+    HIP_TRY(hipMemcpyAsync(c->d_vdb_slot[k].get(), aslot.data(), aslot.size() * sizeof(int), hipMemcpyHostToDevice,
                            c->stream));
-    HIP_TRY(dalloc(&c->d_vdb_leaves[k], std::max<size_t>(list.size(), 1) * avr::vdb::kApronVals));
+    HIP_TRY(c->d_vdb_tiles[k].alloc(consts.size()));
+    HIP_TRY(hipMemcpyAsync(c->d_vdb_tiles[k].get(), consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(c->d_vdb_leaves[k].alloc(std::max<size_t>(list.size(), 1) * avr::vdb::kApronVals));
     if (!list.empty()) {
-        HIP_TRY(dalloc(&tmp.list, list.size()));
-        HIP_TRY(hipMemcpyAsync(tmp.list, list.data(), list.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(tmp.get(rList), list.data(), list.size() * sizeof(long long), hipMemcpyHostToDevice,
+                               c->stream));
         const long long nl = (long long)list.size();
         const int nblk = (int)std::min<long long>(nl, 1 << 20);
-        hipLaunchKernelGGL(avr::k_vdb_apron, dim3(nblk), dim3(256), 0, c->stream, base, tmp.list, nl,
-                           c->d_vdb_leaves[k]);
+        hipLaunchKernelGGL(avr::k_vdb_apron, dim3(nblk), dim3(256), 0, c->stream, base, tmp.get(rList), nl,
+                           c->d_vdb_leaves[k].get());
         HIP_TRY(hipGetLastError());
     }
     // the host vectors and the base layout die here: finish the copies and the fill first
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->vdb_napron[k] = (long long)list.size();
-    g.slot = c->d_vdb_slot[k];
-    g.blocks = c->d_vdb_leaves[k];
-    g.consts = c->d_vdb_tiles[k];
+    g.slot = c->d_vdb_slot[k].get();
+    g.blocks = c->d_vdb_leaves[k].get();
+    g.consts = c->d_vdb_tiles[k].get();
     g.ox = base.ox; g.oy = base.oy; g.oz = base.oz;
     g.lnx = base.lnx; g.lny = base.lny; g.lnz = base.lnz;
     return AVR_OK;
@@ -617,15 +627,14 @@ int upload_vdb(avr_context *c, const avr_vdb_grid *G, int k, avr::vdb::Apron &g)
 int build_majorant(avr_context *c, const int mres[3]) {
     avr::DevMedium &m = c->med;
     const int type = m.type;
-    if (c->d_majorant) (void)hipFree(c->d_majorant);
-    c->d_majorant = nullptr;
+    c->d_majorant.reset();
     const int nm = mres[0] * mres[1] * mres[2];
-    if (c->d_occ) (void)hipFree(c->d_occ);
-    c->d_occ = nullptr;
+    c->d_occ.reset();
     m.occ = nullptr;
     // nm cells + one trailing 0: the read target of empty cells under the occupancy level
-    HIP_TRY(dalloc(&c->d_majorant, (size_t)nm + 1));
-    HIP_TRY(hipMemsetAsync(c->d_majorant + nm, 0, sizeof(float), c->stream));
+    HIP_TRY(c->d_majorant.alloc((size_t)nm + 1));
+    float *const d_majorant = c->d_majorant.get();
+    HIP_TRY(hipMemsetAsync(d_majorant + nm, 0, sizeof(float), c->stream));
     for (int i = 0; i < 3; ++i) {
         m.mres[i] = mres[i];
         m.fres[i] = (float)mres[i];
@@ -633,32 +642,32 @@ int build_majorant(avr_context *c, const int mres[3]) {
     }
     if (type == 0) {
         hipLaunchKernelGGL(avr::k_majorant, dim3(nm), dim3(256), 0, c->stream, m.density, m.nx, m.ny, m.nz, mres[0],
-                           mres[1], mres[2], c->d_majorant);
+                           mres[1], mres[2], d_majorant);
         HIP_TRY(hipGetLastError());
     } else if (type == 4) {
         hipLaunchKernelGGL(avr::k_majorant_rgb, dim3(nm), dim3(256), 0, c->stream, m.rgb_a, m.rgb_s, m.nx, m.ny, m.nz,
-                           mres[0], mres[1], mres[2], m.rgb_sigma_scale, c->d_majorant);
+                           mres[0], mres[1], mres[2], m.rgb_sigma_scale, d_majorant);
         HIP_TRY(hipGetLastError());
     } else if (type == 3) {
         const int *b = c->vdb_ibbox;
         hipLaunchKernelGGL(avr::k_majorant_vdb, dim3(nm), dim3(256), 0, c->stream, m.vdb,
                            make_float3(m.bmin[0], m.bmin[1], m.bmin[2]), make_float3(m.bmax[0], m.bmax[1], m.bmax[2]),
                            make_int4(b[0], b[1], b[2], 0), make_int4(b[3], b[4], b[5], 0), mres[0], mres[1], mres[2],
-                           c->d_majorant);
+                           d_majorant);
         HIP_TRY(hipGetLastError());
         const int nw = (nm + 63) / 64;
         if (c->majorant_occupancy && nw <= avr::kOccWords) {
-            HIP_TRY(hipMalloc(&c->d_occ, (size_t)nw * sizeof(unsigned)));
+            HIP_TRY(c->d_occ.alloc((size_t)nw));
             hipLaunchKernelGGL(avr::k_majorant_occupancy, dim3((nw + 255) / 256), dim3(256), 0, c->stream,
-                               c->d_majorant, nm, c->d_occ, nw);
+                               d_majorant, nm, c->d_occ.get(), nw);
             HIP_TRY(hipGetLastError());
-            m.occ = c->d_occ;
+            m.occ = c->d_occ.get();
         }
     } else {   // single segment, sigma_maj = sigma_t * 1 (density <= 1 for the cloud)
         const float one = 1.f;
-        HIP_TRY(hipMemcpyAsync(c->d_majorant, &one, sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_majorant, &one, sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
-    m.majorant = c->d_majorant;
+    m.majorant = d_majorant;
     return AVR_OK;
 }
 
@@ -671,20 +680,20 @@ int medium_common(avr_context *c, const float *d_density, int nx, int ny, int nz
     if (mres[0] < 1 || mres[1] < 1 || mres[2] < 1) return fail(AVR_ERR_ARG, "bad majorant resolution");
     if (Lescale && (lnx < 1 || lny < 1 || lnz < 1)) return fail(AVR_ERR_ARG, "bad Lescale grid");
     int rc;
-    if ((rc = upload_table(&c->d_sigma_a, sigma_a, avr::kNTable, c->stream))) return rc;
-    if ((rc = upload_table(&c->d_sigma_s, sigma_s, avr::kNTable, c->stream))) return rc;
+    if ((rc = upload_table(c->d_sigma_a, sigma_a, avr::kNTable, c->stream))) return rc;
+    if ((rc = upload_table(c->d_sigma_s, sigma_s, avr::kNTable, c->stream))) return rc;
     // Le and LeScale are always resident: a temperature grid attached later makes the medium
     // emissive without an Le spectrum (zeros), and LeScale defaults to pbrt's 1^3 {LeNorm}
     // grid with LeNorm = 1 (media.cpp:288-296)
     static const float zeros[avr::kNTable] = {};
     static const float one = 1.f;
-    if ((rc = upload_table(&c->d_Le, Le ? Le : zeros, avr::kNTable, c->stream))) return rc;
+    if ((rc = upload_table(c->d_Le, Le ? Le : zeros, avr::kNTable, c->stream))) return rc;
     if (!Lescale) { Lescale = &one; lnx = lny = lnz = 1; }
-    if ((rc = upload_table(&c->d_lescale, Lescale, (size_t)lnx * lny * lnz, c->stream))) return rc;
+    if ((rc = upload_table(c->d_lescale, Lescale, (size_t)lnx * lny * lnz, c->stream))) return rc;
     avr::DevMedium &m = c->med;
     if (type != 3) free_vdb(c);
     if (type != 4) free_rgb(c);
-    if (c->d_temperature) { (void)hipFree(c->d_temperature); c->d_temperature = nullptr; }
+    c->d_temperature.reset();
     m.temperature = nullptr;
     m.temp_scale = 1.f;
     m.temp_offset = 0.f;
@@ -702,8 +711,8 @@ int medium_common(avr_context *c, const float *d_density, int nx, int ny, int nz
     m.unit_box = (m.bmax[0] - m.bmin[0] == 1.f && m.bmax[1] - m.bmin[1] == 1.f && m.bmax[2] - m.bmin[2] == 1.f) ? 1 : 0;
     copy_xf(m.render_from_medium, rfm);
     copy_xf(m.medium_from_render, mfr);
-    m.sigma_a = c->d_sigma_a;
-    m.sigma_s = c->d_sigma_s;
+    m.sigma_a = c->d_sigma_a.get();
+    m.sigma_s = c->d_sigma_s.get();
     m.g = g;
     m.hg = avr::hg_consts(g);
     m.fn[0] = (float)nx;
@@ -717,12 +726,12 @@ int medium_common(avr_context *c, const float *d_density, int nx, int ny, int nz
     bool emissive = false;
     if (Le) for (int i = 0; i < avr::kNTable; ++i) emissive |= Le[i] > 0;
     m.emissive = emissive ? 1 : 0;
-    m.Le = c->d_Le;
-    m.lescale = c->d_lescale;
+    m.Le = c->d_Le.get();
+    m.lescale = c->d_lescale.get();
     m.lnx = lnx; m.lny = lny; m.lnz = lnz;
     if ((rc = build_majorant(c, mres))) return rc;
-    if (c->d_fat) { (void)hipFree(c->d_fat); c->d_fat = nullptr; }
-    if (c->d_brick) { (void)hipFree(c->d_brick); c->d_brick = nullptr; }
+    c->d_fat.reset();
+    c->d_brick.reset();
     m.fat = nullptr;
     m.brick = nullptr;
     m.nb[0] = m.nb[1] = m.nb[2] = 0;
@@ -730,33 +739,24 @@ int medium_common(avr_context *c, const float *d_density, int nx, int ny, int nz
         // bricked copy: 8^3 base voxels + apron per brick (k_brickify), 1.42x the grid
         const int nb[3] = {(nx + 8) / 8, (ny + 8) / 8, (nz + 8) / 8};
         const long long nbricks = (long long)nb[0] * nb[1] * nb[2];
-        const size_t bytes = (size_t)nbricks * avr::kBrickFloats * sizeof(float);
-        size_t freeB = 0, totalB = 0;
-        HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-        if (bytes + (8ull << 30) < freeB && hipMalloc((void **)&c->d_brick, bytes) == hipSuccess) {
+        HIP_TRY(c->d_brick.alloc_if_room((size_t)nbricks * avr::kBrickFloats));
+        if (c->d_brick) {
             hipLaunchKernelGGL(avr::k_brickify, dim3(blocks_for(nbricks * avr::kBrickFloats, 256, 256 * 64)), dim3(256), 0,
-                               c->stream, d_density, nx, ny, nz, nb[0], nb[1], nbricks, c->d_brick);
+                               c->stream, d_density, nx, ny, nz, nb[0], nb[1], nbricks, c->d_brick.get());
             HIP_TRY(hipGetLastError());
-            m.brick = c->d_brick;
+            m.brick = c->d_brick.get();
             for (int a = 0; a < 3; ++a) m.nb[a] = nb[a];
-        } else {
-            (void)hipGetLastError();
-            c->d_brick = nullptr;
         }
     }
     if (c->grid_layout == 1 && type == 0) {
         const size_t nfat = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
-        size_t freeB = 0, totalB = 0;
-        HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-        // keep >= 8 GiB for path state / film / other ranks' traffic
-        if (nfat * 32 + (8ull << 30) < freeB && hipMalloc((void **)&c->d_fat, nfat * 32) == hipSuccess) {
+        // 32 B (two float4) per voxel corner, when HBM has them to spare
+        HIP_TRY(c->d_fat.alloc_if_room(2 * nfat));
+        if (c->d_fat) {
             hipLaunchKernelGGL(avr::k_fatten, dim3(blocks_for((long long)nfat, 256, 256 * 64)), dim3(256), 0,
-                               c->stream, d_density, nx, ny, nz, c->d_fat);
+                               c->stream, d_density, nx, ny, nz, c->d_fat.get());
             HIP_TRY(hipGetLastError());
-            m.fat = c->d_fat;
-        } else {
-            (void)hipGetLastError();
-            c->d_fat = nullptr;
+            m.fat = c->d_fat.get();
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -800,19 +800,20 @@ int avr_context_create(int device, long long max_paths, avr_context **out) {
     // path kernels leave free
     int prLeast = 0, prGreatest = 0;
     hipError_t e = hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, prGreatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->tstream, hipStreamNonBlocking, prLeast);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_cam, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_tab, hipEventDisableTiming);
+    // (a chain, not HIP_TRY: the context made so far is destroyed on a failure)
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->own_stream.h, hipStreamNonBlocking, prGreatest);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->tstream.h, hipStreamNonBlocking, prLeast);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_cam.h, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_tab.h, hipEventDisableTiming);
     if (e != hipSuccess) { (void)avr_context_destroy(c); return fail(AVR_ERR_HIP, hipGetErrorString(e)); }
     c->stream = c->own_stream;
-    if (dalloc(&c->d_counts, 4) != hipSuccess || dalloc(&c->d_stats, avr::kNumStats + 8) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_count, sizeof(int) * 4) != hipSuccess) {
+    if (c->d_counts.alloc(4) != hipSuccess || c->d_stats.alloc(avr::kNumStats + 8) != hipSuccess ||
+        hipHostMalloc((void **)&c->h_count.h, sizeof(int) * 4) != hipSuccess) {
         (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
     }
     if (c->set.alloc_heads() != hipSuccess ||
-        hipMemset(c->d_stats, 0, sizeof(unsigned long long) * (avr::kNumStats + 8)) != hipSuccess) {
+        hipMemset(c->d_stats.get(), 0, sizeof(unsigned long long) * (avr::kNumStats + 8)) != hipSuccess) {
         (void)avr_context_destroy(c);
         return fail(AVR_ERR_HIP, "context allocation failed");
     }
@@ -930,52 +931,7 @@ int avr_context_destroy(avr_context *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->tstream) (void)hipStreamSynchronize(c->tstream);
     release_comms(c);
-    free_paths(c);
-    free_records(c);
-    float *fs[] = {c->d_density_owned, c->d_sigma_a, c->d_sigma_s, c->d_Le, c->d_lescale, c->d_majorant,
-                   c->d_lightL, c->d_xyz};
-    if (c->d_lights) (void)hipFree(c->d_lights);
-    for (auto p : fs) if (p) (void)hipFree(p);
-    if (c->film.rgb_sum) (void)hipFree(c->film.rgb_sum);
-    if (c->film.w_sum) (void)hipFree(c->film.w_sum);
-    if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    c->set.free_heads();
-    for (int *b : {c->d_bin_keys, c->d_bin_out, c->d_bin_hist}) if (b) (void)hipFree(b);
-    if (c->d_planes) (void)hipFree(c->d_planes);
-    if (c->d_occ) (void)hipFree(c->d_occ);
-    if (c->d_advance) (void)hipFree(c->d_advance);
-    if (c->d_filter) (void)hipFree(c->d_filter);
-    if (c->d_temperature) (void)hipFree(c->d_temperature);
-    free_vdb(c);
-    free_rgb(c);
-    for (auto &b : c->d_light_img) if (b) (void)hipFree(b), b = nullptr;
-    if (c->d_zs_table) (void)hipFree(c->d_zs_table);
-    for (int b = 0; b < 2; ++b) {
-        if (c->d_zs_ptab[b]) (void)hipFree(c->d_zs_ptab[b]);
-        if (c->d_zs_ctab[b]) (void)hipFree(c->d_zs_ctab[b]);
-    }
-    if (c->d_zs_atab) (void)hipFree(c->d_zs_atab);
-    if (c->d_image) (void)hipFree(c->d_image);
-    if (c->d_reference) (void)hipFree(c->d_reference);
-    if (c->d_metric) (void)hipFree(c->d_metric);
-    if (c->d_fat) (void)hipFree(c->d_fat);
-    if (c->d_brick) (void)hipFree(c->d_brick);
-    if (c->d_gidx) (void)hipFree(c->d_gidx);
-    if (c->d_gside) (void)hipFree(c->d_gside);
-    if (c->d_guni) (void)hipFree(c->d_guni);
-    if (c->d_arec) (void)hipFree(c->d_arec);
-    if (c->d_aacc) (void)hipFree(c->d_aacc);
-    if (c->d_adetail) (void)hipFree(c->d_adetail);
-    free_pixel_order(c);
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->h_count) (void)hipHostFree(c->h_count);
-    for (auto e : c->evpool) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->tstream) (void)hipStreamDestroy(c->tstream);
-    if (c->ev_cam) (void)hipEventDestroy(c->ev_cam);
-    if (c->ev_tab) (void)hipEventDestroy(c->ev_tab);
-    delete c;
+    delete c;   // the device buffers, then the events and streams (avr_context's member order)
     return AVR_OK;
 }
 
@@ -994,12 +950,12 @@ int avr_medium_grid(avr_context *c, const float *density, int nx, int ny, int nz
     AVR_QUIESCE(c);
     if (!c || !density || nx < 1 || ny < 1 || nz < 1) return fail(AVR_ERR_ARG, "bad grid");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->d_density_owned) { (void)hipFree(c->d_density_owned); c->d_density_owned = nullptr; }
+    c->d_density_owned.reset();
     const size_t n = (size_t)nx * ny * nz;
     if (n > (size_t)INT32_MAX) return fail(AVR_ERR_ARG, "grid too large for int32 indexing (containers.h:834)");
-    HIP_TRY(dalloc(&c->d_density_owned, n));
-    HIP_TRY(hipMemcpyAsync(c->d_density_owned, density, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    return medium_common(c, c->d_density_owned, nx, ny, nz, bounds, rfm, mfr, sigma_a, sigma_s, g, Le, Lescale, lnx,
+    HIP_TRY(c->d_density_owned.alloc(n));
+    HIP_TRY(hipMemcpyAsync(c->d_density_owned.get(), density, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return medium_common(c, c->d_density_owned.get(), nx, ny, nz, bounds, rfm, mfr, sigma_a, sigma_s, g, Le, Lescale, lnx,
                          lny, lnz, mres);
 }
 
@@ -1011,7 +967,7 @@ int avr_medium_grid_device(avr_context *c, const float *d_density, int nx, int n
     if (!c || !d_density || nx < 1 || ny < 1 || nz < 1) return fail(AVR_ERR_ARG, "bad grid");
     if ((size_t)nx * ny * nz > (size_t)INT32_MAX) return fail(AVR_ERR_ARG, "grid too large for int32 indexing");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->d_density_owned) { (void)hipFree(c->d_density_owned); c->d_density_owned = nullptr; }
+    c->d_density_owned.reset();
     return medium_common(c, d_density, nx, ny, nz, bounds, rfm, mfr, sigma_a, sigma_s, g, Le, Lescale, lnx, lny, lnz,
                          mres);
 }
@@ -1026,11 +982,9 @@ int avr_medium_temperature(avr_context *c, const float *temperature, float tempe
         return fail(AVR_ERR_ARG, "both \"Le\" and \"temperature\" given (media.cpp:283-284)");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->med.nx * c->med.ny * c->med.nz;
-    if (c->d_temperature) (void)hipFree(c->d_temperature);
-    c->d_temperature = nullptr;
-    HIP_TRY(dalloc(&c->d_temperature, n));
-    HIP_TRY(hipMemcpy(c->d_temperature, temperature, n * sizeof(float), hipMemcpyHostToDevice));
-    c->med.temperature = c->d_temperature;
+    HIP_TRY(c->d_temperature.alloc(n));
+    HIP_TRY(hipMemcpy(c->d_temperature.get(), temperature, n * sizeof(float), hipMemcpyHostToDevice));
+    c->med.temperature = c->d_temperature.get();
     c->med.temp_scale = temperature_scale;
     c->med.temp_offset = temperature_offset;
     c->med.emissive = 1;   // isEmissive = temperatureGrid ? true : ... (media.cpp:238)
@@ -1095,17 +1049,13 @@ int avr_medium_nanovdb(avr_context *c, const avr_vdb_grid *density, const avr_vd
     // of every apron block, when it fits in free HBM with 8 GiB to spare
     if (c->grid_layout == 1 && c->vdb_napron[0] > 0) {
         const size_t nfat = (size_t)c->vdb_napron[0] * 512;
-        size_t freeB = 0, totalB = 0;
-        HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-        if (nfat * 32 + (8ull << 30) < freeB && hipMalloc((void **)&c->d_fat, nfat * 32) == hipSuccess) {
+        HIP_TRY(c->d_fat.alloc_if_room(2 * nfat));
+        if (c->d_fat) {
             hipLaunchKernelGGL(avr::k_vdb_fat, dim3(blocks_for((long long)nfat, 256, 256 * 64)), dim3(256), 0, c->stream,
-                               c->med.vdb.blocks, c->vdb_napron[0], c->d_fat);
+                               c->med.vdb.blocks, c->vdb_napron[0], c->d_fat.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(c->stream));
-            c->med.vdb.fat = reinterpret_cast<const float *>(c->d_fat);
-        } else {
-            (void)hipGetLastError();
-            c->d_fat = nullptr;
+            c->med.vdb.fat = reinterpret_cast<const float *>(c->d_fat.get());
         }
     }
     c->med.vdb_lescale = Lescale;
@@ -1138,16 +1088,16 @@ static int medium_rgbgrid(avr_context *c, int nx, int ny, int nz, const float bo
             grid[k] = reinterpret_cast<const float4 *>(src[k]);
             continue;
         }
-        HIP_TRY(dalloc(&c->d_rgb[k], n));
-        HIP_TRY(hipMemcpyAsync(c->d_rgb[k], src[k], n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        grid[k] = c->d_rgb[k];
+        HIP_TRY(c->d_rgb[k].alloc(n));
+        HIP_TRY(hipMemcpyAsync(c->d_rgb[k].get(), src[k], n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        grid[k] = c->d_rgb[k].get();
     }
     int rc;
-    if (Le && (rc = upload_table(&c->d_illum, illuminant, avr::kNTable, c->stream))) return rc;
+    if (Le && (rc = upload_table(c->d_illum, illuminant, avr::kNTable, c->stream))) return rc;
     c->med.rgb_a = grid[0];
     c->med.rgb_s = grid[1];
     c->med.rgb_le = grid[2];
-    c->med.illuminant = c->d_illum;
+    c->med.illuminant = c->d_illum.get();
     c->med.rgb_sigma_scale = sigma_scale;
     c->med.rgb_le_scale = Le_scale;
     // SampleRay's sigma_t = 1 (media.h:417): tables {1} + {0} make the segments' sigma_maj the
@@ -1210,7 +1160,7 @@ int avr_read_majorant(avr_context *c, float *out) {
     AVR_QUIESCE(c);
     if (!c || !c->has_medium || !out) return fail(AVR_ERR_STATE, "no medium");
     const int nm = c->med.mres[0] * c->med.mres[1] * c->med.mres[2];
-    HIP_TRY(hipMemcpyAsync(out, c->d_majorant, nm * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_majorant.get(), nm * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
@@ -1234,17 +1184,17 @@ int avr_medium_boundary_convex(avr_context *c, const float *planes, int n_planes
     for (int i = 0; i < 4 * n_planes; ++i)
         if (!std::isfinite(planes[i])) return fail(AVR_ERR_ARG, "convex interface planes must be finite");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->d_planes) { (void)hipFree(c->d_planes); c->d_planes = nullptr; }
+    c->d_planes.reset();
     c->med.planes = nullptr;
     c->med.n_planes = 0;
     if (n_planes == 0) {
         if (c->med.boundary == 2) c->med.boundary = 0;
         return AVR_OK;
     }
-    HIP_TRY(dalloc(&c->d_planes, (size_t)n_planes));
-    HIP_TRY(hipMemcpyAsync(c->d_planes, planes, 4 * sizeof(float) * n_planes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->d_planes.alloc((size_t)n_planes));
+    HIP_TRY(hipMemcpyAsync(c->d_planes.get(), planes, 4 * sizeof(float) * n_planes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->med.planes = c->d_planes;
+    c->med.planes = c->d_planes.get();
     c->med.n_planes = n_planes;
     c->med.boundary = 2;
     return AVR_OK;
@@ -1265,9 +1215,9 @@ int avr_density_fetch(avr_context *c, const void *d_points, long long n, float *
     if (!c || !c->has_medium || c->med.type != 0) return fail(AVR_ERR_STATE, "density fetch needs a GridMedium");
     if (n < 0 || (n > 0 && (!d_points || !d_out))) return fail(AVR_ERR_ARG, "bad density fetch batch");
     HIP_TRY(hipSetDevice(c->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    avr::devmem::Event e0, e1;
+    HIP_TRY(hipEventCreate(&e0.h));
+    HIP_TRY(hipEventCreate(&e1.h));
     const int blocks = (int)std::min<long long>((n + 255) / 256, 256LL * 64);
     HIP_TRY(hipEventRecord(e0, c->stream));
     if (n > 0)
@@ -1279,8 +1229,6 @@ int avr_density_fetch(avr_context *c, const void *d_points, long long n, float *
     float t = 0.f;
     HIP_TRY(hipEventElapsedTime(&t, e0, e1));
     if (ms) *ms = t;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return AVR_OK;
 }
 
@@ -1311,18 +1259,29 @@ int avr_set_majorant_res(avr_context *c, const int res[3]) {
 // schedule, e.g. refill 0 and refill 32 when 32 is the default), not one noisy probe.
 constexpr float kProbeNoise = 0.02f;
 extern "C++" {
+// avr_film_export_device's inverse: the film's sums from `src`
+static int film_import_device(avr_context *c, const double *src) {
+    const size_t np = (size_t)c->film.bw * c->film.bh;
+    HIP_TRY(hipMemcpyAsync(c->film.rgb_sum, src, 3 * np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->film.w_sum, src + 3 * np, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (c->film.nbuckets > 0)
+        HIP_TRY(hipMemcpyAsync(c->film.bucket_sum, src + 4 * np, 2 * np * c->film.nbuckets * sizeof(double),
+                               hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
+}
 template <typename Setup, typename Restore>
 static int probe_loop(avr_context *c, int n, Setup setup, Restore restore, int spp_begin, int spp_end, int seed,
                       int max_depth, int *bestk, float *ms, int prefer = -1, const std::vector<char> *same = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     const size_t np = (size_t)c->film.bw * c->film.bh;
     const size_t nd = (4 + 2 * (size_t)std::max(0, c->film.nbuckets)) * np;
-    double *saved = nullptr;
-    HIP_TRY(dalloc(&saved, nd));
-    int rc = avr_film_export_device(c, saved);
+    Buffer<double> saved;
+    HIP_TRY(saved.alloc(nd));
+    int rc = avr_film_export_device(c, saved.get());
     const bool haveSaved = rc == AVR_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = fail(AVR_ERR_HIP, "event");
+    avr::devmem::Event e0, e1;
+    if (!rc && (hipEventCreate(&e0.h) != hipSuccess || hipEventCreate(&e1.h) != hipSuccess)) rc = fail(AVR_ERR_HIP, "event");
     float best = -1.f, tPrefer = -1.f;
     *bestk = 0;
     // the probes render one range over and over: no pass table built ahead on the side stream
@@ -1357,16 +1316,11 @@ static int probe_loop(avr_context *c, int n, Setup setup, Restore restore, int s
     const std::string err = g_err;
     const int rcProbe = rc;
     int rcRestore = restore(rc != 0, *bestk);
-    if (haveSaved) {
-        const double *d = saved;
-        hipError_t e = hipMemcpyAsync(c->film.rgb_sum, d, 3 * np * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(c->film.w_sum, d + 3 * np, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess && c->film.nbuckets > 0)
-            e = hipMemcpyAsync(c->film.bucket_sum, d + 4 * np, 2 * np * c->film.nbuckets * sizeof(double),
-                               hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess && !rcRestore) rcRestore = fail(AVR_ERR_HIP, std::string("film restore: ") + hipGetErrorString(e));
+    if (haveSaved) {   // (restore()'s error comes before the film's)
+        const std::string errRestore = g_err;
+        const int rcFilm = film_import_device(c, saved.get());
+        if (rcRestore) g_err = errRestore;
+        else rcRestore = rcFilm;
     }
     if (rcProbe) {
         rc = rcProbe;
@@ -1374,9 +1328,6 @@ static int probe_loop(avr_context *c, int n, Setup setup, Restore restore, int s
     } else {
         rc = rcRestore;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(saved);
     if (!rc) rc = avr_reset_stats(c);
     return rc;
 }
@@ -1618,7 +1569,7 @@ static int update_light_sampler(avr_context *c) {
         avr::ll::build_tree(n, bounded, lb, &c->h_tree);
     }
     if (c->d_lights) {
-        HIP_TRY(hipMemcpyAsync(c->d_lights + avr::kMaxLights, &c->h_tree, sizeof(c->h_tree), hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(c->d_lights.get() + avr::kMaxLights, &c->h_tree, sizeof(c->h_tree), hipMemcpyHostToDevice,
                                c->stream));
     }
     float q[avr::kMaxLights], pm[avr::kMaxLights];
@@ -1639,7 +1590,7 @@ static int update_light_sampler(avr_context *c) {
         c->h_lights[i].alias = al[i];
     }
     if (c->d_lights) {
-        HIP_TRY(hipMemcpyAsync(c->d_lights, c->h_lights, sizeof(c->h_lights), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_lights.get(), c->h_lights, sizeof(c->h_lights), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return AVR_OK;
@@ -1651,7 +1602,7 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
     if (!c || n < 0 || n > avr::kMaxLights) return fail(AVR_ERR_ARG, "0..8 lights supported");
     if (n > 0 && (!types || !w3 || !L || !scale)) return fail(AVR_ERR_ARG, "null light arrays");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = upload_table(&c->d_lightL, n ? L : nullptr, (size_t)n * avr::kNTable, c->stream);
+    int rc = upload_table(c->d_lightL, n ? L : nullptr, (size_t)n * avr::kNTable, c->stream);
     if (rc) return rc;
     avr::DevLight h[avr::kMaxLights] = {};
     for (int i = 0; i < n; ++i) {
@@ -1660,18 +1611,18 @@ int avr_lights(avr_context *c, int n, const int *types, const float *w3, const f
                                      "3 (point) or 4 (spot)");
         h[i].type = types[i];
         for (int k = 0; k < 3; ++k) h[i].w[k] = w3[3 * i + k];
-        h[i].L = c->d_lightL + (size_t)i * avr::kNTable;
+        h[i].L = c->d_lightL.get() + (size_t)i * avr::kNTable;
         h[i].scale = scale[i];
     }
     // (the records, and behind them the light BVH: light_tree())
-    if (!c->d_lights) HIP_TRY(dalloc(&c->d_lights, avr::kMaxLights + avr::kLightTreeSlots));
-    HIP_TRY(hipMemcpyAsync(c->d_lights, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    if (!c->d_lights) HIP_TRY(c->d_lights.alloc(avr::kMaxLights + avr::kLightTreeSlots));
+    HIP_TRY(hipMemcpyAsync(c->d_lights.get(), h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (auto &b : c->d_light_img) if (b) (void)hipFree(b), b = nullptr;
+    for (auto &b : c->d_light_img) b.reset();
     for (int i = 0; i < avr::kMaxLights; ++i) c->h_lights[i] = h[i];
     c->lights = {};
     c->lights.n = n;
-    c->lights.list = c->d_lights;
+    c->lights.list = c->d_lights.get();
     c->lights.scene_radius = scene_radius;
     c->n_image_lights = 0;
     c->n_local_lights = 0;
@@ -1728,11 +1679,9 @@ int avr_light_image(avr_context *c, int index, int res, const float *pixel_coeff
     for (int y = 0; y < ny; ++y) pc1d_build(f + (size_t)y * nx, nx, 0.f, 1.f, ccdf + (size_t)y * (nx + 1), cint + y);
     pc1d_build(cint, ny, 0.f, 1.f, mcdf, mint);
     std::memcpy(t + ntab, illuminant, avr::kNTable * sizeof(float));
-    if (c->d_light_img[index]) (void)hipFree(c->d_light_img[index]);
-    c->d_light_img[index] = nullptr;
-    HIP_TRY(hipMalloc((void **)&c->d_light_img[index], bytes));
-    HIP_TRY(hipMemcpy(c->d_light_img[index], blob.data(), bytes, hipMemcpyHostToDevice));
-    unsigned char *base = (unsigned char *)c->d_light_img[index];
+    HIP_TRY(c->d_light_img[index].alloc(bytes));
+    unsigned char *base = c->d_light_img[index].get();
+    HIP_TRY(hipMemcpy(base, blob.data(), bytes, hipMemcpyHostToDevice));
     avr::DevLight &L = c->h_lights[index];
     L.img = (const float4 *)base;
     L.res = res;
@@ -1750,7 +1699,7 @@ int avr_light_image(avr_context *c, int index, int res, const float *pixel_coeff
             L.rfl[3 * r + k] = render_from_light[4 * r + k];
             L.lfr[3 * r + k] = light_from_render[4 * r + k];
         }
-    HIP_TRY(hipMemcpyAsync(c->d_lights, c->h_lights, sizeof(c->h_lights), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_lights.get(), c->h_lights, sizeof(c->h_lights), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->h_phi[index] = phi_image_light(pixel_coeffs, res, illuminant, L.scale, c->lights.scene_radius);
     c->phi_ok[index] = true;
@@ -1805,27 +1754,25 @@ int avr_light_probe(avr_context *c, int index, int n, const float *u2, const flo
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)n;
-    float *d = nullptr;
-    HIP_TRY(dalloc(&d, N * 22));
-    float *du = d, *dw = d + 2 * N, *dl = d + 5 * N, *dwi = d + 9 * N, *dps = d + 12 * N, *dLs = d + 13 * N,
-          *dpl = d + 17 * N, *dLe = d + 18 * N;
-    hipError_t e = hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dw, w3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_light_probe, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du, dw,
-                           dl, dwi, dps, dLs, dpl, dLe);
-        e = hipGetLastError();
-    }
+    Arena<> scratch(c->stream);
+    const auto ru = scratch.reserve<float>(2 * N), rw = scratch.reserve<float>(3 * N), rl = scratch.reserve<float>(4 * N);
+    const auto rwi = scratch.reserve<float>(3 * N), rps = scratch.reserve<float>(N), rLs = scratch.reserve<float>(4 * N);
+    const auto rpl = scratch.reserve<float>(N), rLe = scratch.reserve<float>(4 * N);
+    HIP_TRY(scratch.commit());
+    float *du = scratch.get(ru), *dw = scratch.get(rw), *dl = scratch.get(rl), *dwi = scratch.get(rwi);
+    float *dps = scratch.get(rps), *dLs = scratch.get(rLs), *dpl = scratch.get(rpl), *dLe = scratch.get(rLe);
+    HIP_TRY(hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dw, w3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_light_probe, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du, dw, dl,
+                       dwi, dps, dLs, dpl, dLe);
+    HIP_TRY(hipGetLastError());
     const struct { float *host; const float *dev; size_t k; } outs[] = {{wi3, dwi, 3}, {pdf_sample, dps, 1}, {Ls4, dLs, 4},
                                                                        {pdf_li, dpl, 1}, {Le4, dLe, 4}};
     for (const auto &o : outs)
-        if (e == hipSuccess && o.host)
-            e = hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d);
-    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+        if (o.host) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
 }
 
 // avr_light_pick (p3 null: the origin) and avr_light_pick_at
@@ -1836,23 +1783,21 @@ static int light_pick_impl(avr_context *c, int n, const float *u, const float *p
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)n;
-    float *d = nullptr;
-    HIP_TRY(dalloc(&d, N * 6));
-    float *du = d, *dp = d + N, *dpt = d + 3 * N;
-    int *di = (int *)(d + 2 * N);
-    hipError_t e = hipMemcpyAsync(du, u, N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && p3) e = hipMemcpyAsync(dpt, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_light_pick, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, n, du,
-                           p3 ? dpt : nullptr, di, dp);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(idx, di, N * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pmf, dp, N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d);
-    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto ru = scratch.reserve<float>(N), rp = scratch.reserve<float>(N), rpt = scratch.reserve<float>(3 * N);
+    const auto ri = scratch.reserve<int>(N);
+    HIP_TRY(scratch.commit());
+    float *du = scratch.get(ru), *dp = scratch.get(rp), *dpt = scratch.get(rpt);
+    int *di = scratch.get(ri);
+    HIP_TRY(hipMemcpyAsync(du, u, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (p3) HIP_TRY(hipMemcpyAsync(dpt, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_light_pick, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, n, du,
+                       p3 ? dpt : nullptr, di, dp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(idx, di, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(pmf, dp, N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
 }
 int avr_light_pick(avr_context *c, int n, const float *u, int *idx, float *pmf) {
     AVR_QUIESCE(c);
@@ -1877,26 +1822,25 @@ int avr_light_probe_at(avr_context *c, int index, int n, const float *u2, const 
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)n;
-    float *d = nullptr;
-    HIP_TRY(dalloc(&d, N * 18));
-    float *du = d, *dp = d + 2 * N, *dl = d + 5 * N, *dwi = d + 9 * N, *dps = d + 12 * N, *dLs = d + 13 * N, *dr = d + 17 * N;
-    hipError_t e = hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dp, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_light_probe_at, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du,
-                           dp, dl, dwi, dps, dLs, dr);
-        e = hipGetLastError();
-    }
+    Arena<> scratch(c->stream);
+    const auto ru = scratch.reserve<float>(2 * N), rp = scratch.reserve<float>(3 * N), rl = scratch.reserve<float>(4 * N);
+    const auto rwi = scratch.reserve<float>(3 * N), rps = scratch.reserve<float>(N), rLs = scratch.reserve<float>(4 * N);
+    const auto rr = scratch.reserve<float>(N);
+    HIP_TRY(scratch.commit());
+    float *du = scratch.get(ru), *dp = scratch.get(rp), *dl = scratch.get(rl), *dwi = scratch.get(rwi);
+    float *dps = scratch.get(rps), *dLs = scratch.get(rLs), *dr = scratch.get(rr);
+    HIP_TRY(hipMemcpyAsync(du, u2, 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dp, p3, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dl, lambda4, 4 * N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_light_probe_at, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lights, index, n, du, dp,
+                       dl, dwi, dps, dLs, dr);
+    HIP_TRY(hipGetLastError());
     const struct { float *host; const float *dev; size_t k; } outs[] = {{wi3, dwi, 3}, {pdf_sample, dps, 1}, {Ls4, dLs, 4},
                                                                        {dist, dr, 1}};
     for (const auto &o : outs)
-        if (e == hipSuccess && o.host)
-            e = hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d);
-    return e == hipSuccess ? AVR_OK : fail(AVR_ERR_HIP, hipGetErrorString(e));
+        if (o.host) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.k * N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
 }
 
 int avr_light_bvh(avr_context *c, int *n_nodes, float *phi, float *w3, int *qcos, int *qb, int *link, int *leaf,
@@ -1978,14 +1922,11 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     AVR_QUIESCE(c);
     if (!c || width < 1 || height < 1 || !fr || !sensor) return fail(AVR_ERR_ARG, "bad film");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = upload_table(&c->d_xyz, sensor, 3 * (size_t)avr::kNTable, c->stream);
+    int rc = upload_table(c->d_xyz, sensor, 3 * (size_t)avr::kNTable, c->stream);
     if (rc) return rc;
-    if (c->film.rgb_sum) (void)hipFree(c->film.rgb_sum);
-    if (c->film.w_sum) (void)hipFree(c->film.w_sum);
-    if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
+    free_film_sums(c);
     free_pixel_order(c);   // an order is for one film resolution
-    if (c->d_aacc) (void)hipFree(c->d_aacc);   // the analysis' per-pixel sums go with the film
-    c->d_aacc = nullptr;
+    c->d_aacc.reset();     // the analysis' per-pixel sums go with the film
     c->last.analyze = 0;
     c->film = {};
     c->film.width = width;
@@ -1994,12 +1935,10 @@ int avr_film(avr_context *c, int width, int height, const float fr[2], const flo
     c->film.bh = height;
     c->film.filter_rx = fr[0];
     c->film.filter_ry = fr[1];
-    c->film.xyz = c->d_xyz;
+    c->film.xyz = c->d_xyz.get();
     c->film.imaging_ratio = imaging_ratio;
     c->film.max_component = max_component_value;
-    const size_t np = (size_t)width * height;
-    HIP_TRY(dalloc(&c->film.rgb_sum, 3 * np));
-    HIP_TRY(dalloc(&c->film.w_sum, np));
+    if ((rc = alloc_film_sums(c))) return rc;
     c->has_film = true;
     return avr_film_clear(c);
 }
@@ -2019,33 +1958,20 @@ int avr_film_pixel_bounds(avr_context *c, int x0, int y0, int x1, int y1) {
     // what was made for the old bounds: the pixel order, the analysis sums, the metric reference,
     // the ZSobol pixel and level-A tables, and the pass table and camera records built ahead
     free_pixel_order(c);
-    if (c->d_aacc) (void)hipFree(c->d_aacc);
-    c->d_aacc = nullptr;
+    c->d_aacc.reset();
     c->last = LastPass{};
-    if (c->d_reference) (void)hipFree(c->d_reference);
-    if (c->d_image) (void)hipFree(c->d_image);
-    c->d_reference = nullptr;
-    c->d_image = nullptr;
+    c->d_reference.reset();
+    c->d_image.reset();
     c->look.invalidate();
     c->zs_key[0] = -1;
     for (long long &k : c->zs_akey) k = -1;
-    if (c->film.rgb_sum) (void)hipFree(c->film.rgb_sum);
-    if (c->film.w_sum) (void)hipFree(c->film.w_sum);
-    if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
-    c->film.rgb_sum = c->film.w_sum = c->film.bucket_sum = c->film.bucket_w = nullptr;
+    free_film_sums(c);
     c->film.x0 = x0;
     c->film.y0 = y0;
     c->film.bw = x1 - x0;
     c->film.bh = y1 - y0;
-    const size_t np = (size_t)c->film.bw * c->film.bh;
-    HIP_TRY(dalloc(&c->film.rgb_sum, 3 * np));
-    HIP_TRY(dalloc(&c->film.w_sum, np));
-    if (c->film.nbuckets > 0) {
-        const size_t nb = np * c->film.nbuckets;
-        HIP_TRY(dalloc(&c->film.bucket_sum, 2 * nb));
-        c->film.bucket_w = c->film.bucket_sum + nb;
-    }
-    return avr_film_clear(c);
+    const int rc = alloc_film_sums(c);
+    return rc ? rc : avr_film_clear(c);
 }
 
 int avr_film_get_bounds(avr_context *c, int *x0, int *y0, int *x1, int *y1) {
@@ -2114,21 +2040,20 @@ int avr_set_filter(avr_context *c, int type, const float radius[2], float sigma)
     float *wt = t.data() + avr::smp::filter_table_floats(nx, ny) + avr::smp::filter_guide_floats(ny);
     for (int y = 0; y < ny; ++y)
         for (int x = 0; x < nx; ++x) wt[(size_t)y * nx + x] = avr::smp::filter_cell_weight(f, cint, mint_v, nx, y, x);
-    if (c->d_filter) (void)hipFree(c->d_filter);
-    c->d_filter = nullptr;
-    HIP_TRY(dalloc(&c->d_filter, t.size()));
-    HIP_TRY(hipMemcpy(c->d_filter, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c->d_filter.alloc(t.size()));
+    const float *d_filter = c->d_filter.get();
+    HIP_TRY(hipMemcpy(c->d_filter.get(), t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     c->ftab.nx = nx;
     c->ftab.ny = ny;
     c->ftab.rx = radius[0];
     c->ftab.ry = radius[1];
-    c->ftab.f = c->d_filter;
-    c->ftab.ccdf = c->d_filter + nx * ny;
+    c->ftab.f = d_filter;
+    c->ftab.ccdf = d_filter + nx * ny;
     c->ftab.cint = c->ftab.ccdf + ny * (nx + 1);
     c->ftab.mcdf = c->ftab.cint + ny;
     c->ftab.mint = mint_v;
-    c->ftab.guide = (const uint8_t *)(c->d_filter + avr::smp::filter_table_floats(nx, ny));
-    c->ftab.wt = c->d_filter + avr::smp::filter_table_floats(nx, ny) + avr::smp::filter_guide_floats(ny);
+    c->ftab.guide = (const uint8_t *)(d_filter + avr::smp::filter_table_floats(nx, ny));
+    c->ftab.wt = d_filter + avr::smp::filter_table_floats(nx, ny) + avr::smp::filter_guide_floats(ny);
     c->filter_type = 1;
     return AVR_OK;
 }
@@ -2147,10 +2072,10 @@ int avr_set_pixel_order(avr_context *c, const int *order, long long n) {
         if (p < 0 || p >= np || slot[(size_t)p] >= 0) return fail(AVR_ERR_ARG, "pixel order is not a permutation");
         slot[(size_t)p] = (int)j;
     }
-    HIP_TRY(dalloc(&c->d_pix_order, (size_t)np));
-    HIP_TRY(dalloc(&c->d_pix_slot, (size_t)np));
-    HIP_TRY(hipMemcpy(c->d_pix_order, order, np * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_pix_slot, slot.data(), np * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c->d_pix_order.alloc((size_t)np));
+    HIP_TRY(c->d_pix_slot.alloc((size_t)np));
+    HIP_TRY(hipMemcpy(c->d_pix_order.get(), order, np * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_pix_slot.get(), slot.data(), np * sizeof(int), hipMemcpyHostToDevice));
     c->h_pix_slot.swap(slot);
     ++c->order_gen;
     return AVR_OK;
@@ -2201,17 +2126,13 @@ int avr_film_spectral(avr_context *c, int n_buckets, float lambda_min, float lam
         return fail(AVR_ERR_ARG, "SpectralFilm wavelength range must lie within 360..830 nm");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->film.bucket_sum) (void)hipFree(c->film.bucket_sum);
+    c->d_film_bucket.reset();
     c->film.bucket_sum = c->film.bucket_w = nullptr;
     c->film.nbuckets = n_buckets;
     c->film.lmin = lambda_min;
     c->film.lmax = lambda_max;
-    if (n_buckets > 0) {
-        const size_t nb = (size_t)c->film.bw * c->film.bh * n_buckets;
-        HIP_TRY(dalloc(&c->film.bucket_sum, 2 * nb));
-        c->film.bucket_w = c->film.bucket_sum + nb;
-    }
-    return avr_film_clear(c);
+    const int rc = alloc_film_sums(c);   // (the rgb and weight sums stay: the bucket sums only)
+    return rc ? rc : avr_film_clear(c);
 }
 
 // Stats are resolved lazily so that a render stays asynchronous: every timed interval
@@ -2230,7 +2151,7 @@ static int fold_stats(avr_context *c) {
     c->ev_used = 0;
     unsigned long long h[avr::kNumStats];
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(h, c->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, c->d_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
     c->stats.medium_lookups = h[0];
     c->stats.medium_items_in = h[1];
     c->stats.medium_items_out = h[2];
@@ -2241,7 +2162,7 @@ static int fold_stats(avr_context *c) {
     c->stats.loop_iterations = h[8];
     c->stats.active_lane_iterations = h[9];
     if (h[7]) {
-        HIP_TRY(hipMemset(c->d_stats + 7, 0, sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(c->d_stats.get() + 7, 0, sizeof(unsigned long long)));
         return fail(AVR_ERR_STATE, "k_paths launched without its pass's camera stage (work heads not reset): pass not rendered");
     }
     return AVR_OK;
@@ -2261,7 +2182,7 @@ int avr_transmittance_device(avr_context *c, long long n, const float *p0, const
     HIP_TRY(hipSetDevice(c->device));
     avr::Params p{};
     p.med = c->med;
-    p.stats = c->d_stats;
+    p.stats = c->d_stats.get();
     const int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
     EV_MARK(t0);
     hipLaunchKernelGGL(avr::k_transmittance, dim3(blocks), dim3(256), 0, c->stream, p, n, p0, p1, lambda, tr);
@@ -2275,21 +2196,19 @@ int avr_transmittance(avr_context *c, long long n, const float *p0, const float 
     if (!c || n < 0 || (n > 0 && (!p0 || !p1 || !lambda || !tr))) return fail(AVR_ERR_ARG, "bad transmittance query");
     if (n == 0) return AVR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    float *d = nullptr;
-    HIP_TRY(dalloc(&d, (size_t)n * 14));
-    float *dp0 = d, *dp1 = d + 3 * n, *dl = d + 6 * n, *dtr = d + 10 * n;
+    Arena<> scratch(c->stream);
+    const auto r0 = scratch.reserve<float>(3 * (size_t)n), r1 = scratch.reserve<float>(3 * (size_t)n);
+    const auto rl = scratch.reserve<float>(4 * (size_t)n), rtr = scratch.reserve<float>(4 * (size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dp0 = scratch.get(r0), *dp1 = scratch.get(r1), *dl = scratch.get(rl), *dtr = scratch.get(rtr);
     HIP_TRY(hipMemcpyAsync(dp0, p0, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dp1, p1, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dl, lambda, 4 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    int rc = avr_transmittance_device(c, n, dp0, dp1, dl, dtr);
-    if (rc == AVR_OK) {
-        hipError_t e = hipMemcpyAsync(tr, dtr, 4 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(AVR_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    return rc;
+    const int rc = avr_transmittance_device(c, n, dp0, dp1, dl, dtr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(tr, dtr, 4 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
 }
 
 int avr_sync(avr_context *c) {
@@ -2314,7 +2233,7 @@ int avr_reset_stats(avr_context *c) {
     int rc = fold_stats(c);
     if (rc) return rc;
     c->stats = {};
-    HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * avr::kNumStats, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_stats.get(), 0, sizeof(unsigned long long) * avr::kNumStats, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
@@ -2341,14 +2260,12 @@ int avr_film_set_reference(avr_context *c, const float *reference_rgb, const flo
     if (!c || !c->has_film || !reference_rgb || !out_from_sensor) return fail(AVR_ERR_STATE, "no film or null argument");
     HIP_TRY(hipSetDevice(c->device));
     const size_t np = (size_t)c->film.bw * c->film.bh;
-    if (c->d_reference) (void)hipFree(c->d_reference);
-    if (c->d_image) (void)hipFree(c->d_image);
-    c->d_reference = nullptr;
-    c->d_image = nullptr;
-    HIP_TRY(dalloc(&c->d_reference, 3 * np));
-    HIP_TRY(dalloc(&c->d_image, 3 * np));
-    if (!c->d_metric) HIP_TRY(dalloc(&c->d_metric, (size_t)(kMetricBlocks + 1) * avr::kMetricSlots));
-    HIP_TRY(hipMemcpyAsync(c->d_reference, reference_rgb, 3 * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    c->d_reference.reset();
+    c->d_image.reset();
+    HIP_TRY(c->d_reference.alloc(3 * np));
+    HIP_TRY(c->d_image.alloc(3 * np));
+    if (!c->d_metric) HIP_TRY(c->d_metric.alloc((size_t)(kMetricBlocks + 1) * avr::kMetricSlots));
+    HIP_TRY(hipMemcpyAsync(c->d_reference.get(), reference_rgb, 3 * np * sizeof(float), hipMemcpyHostToDevice, c->stream));
     for (int i = 0; i < 9; ++i) c->ref_out_from_sensor.m[i] = out_from_sensor[i];
     c->ref_fp16 = fp16 ? 1 : 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2361,13 +2278,13 @@ int avr_film_metric(avr_context *c, int metric, float *out) {
     if (metric < 0 || metric > 3) return fail(AVR_ERR_ARG, "metric must be 0 MSE, 1 MAE, 2 MRSE, 3 ME");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = film_image(c, c->ref_out_from_sensor, c->ref_fp16, c->d_image))) return rc;
+    if ((rc = film_image(c, c->ref_out_from_sensor, c->ref_fp16, c->d_image.get()))) return rc;
     const int np = c->film.bw * c->film.bh;
-    double *tot = c->d_metric + (size_t)kMetricBlocks * avr::kMetricSlots;
-    hipLaunchKernelGGL(avr::k_metric, dim3(kMetricBlocks), dim3(256), 0, c->stream, c->d_image, c->d_reference, np,
-                       metric, c->d_metric);
+    double *tot = c->d_metric.get() + (size_t)kMetricBlocks * avr::kMetricSlots;
+    hipLaunchKernelGGL(avr::k_metric, dim3(kMetricBlocks), dim3(256), 0, c->stream, c->d_image.get(),
+                       c->d_reference.get(), np, metric, c->d_metric.get());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(avr::k_metric_final, dim3(1), dim3(64), 0, c->stream, c->d_metric, kMetricBlocks, tot);
+    hipLaunchKernelGGL(avr::k_metric_final, dim3(1), dim3(64), 0, c->stream, c->d_metric.get(), kMetricBlocks, tot);
     HIP_TRY(hipGetLastError());
     double h[avr::kMetricSlots];
     HIP_TRY(hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -2390,38 +2307,27 @@ int avr_flip(avr_context *c, const float *test, const float *ref, int width, int
     (void)avr::flip::detection_filter(ppd, true, pf);
     const float cmax = avr::flip::max_distance();
     const size_t n = (size_t)width * height;
-    float *d_in = nullptr, *d_f = nullptr, *d_out = nullptr;
-    avr::flip::F4 *d_yc = nullptr;
-    auto cleanup = [&]() {
-        if (d_in) (void)hipFree(d_in);
-        if (d_f) (void)hipFree(d_f);
-        if (d_out) (void)hipFree(d_out);
-        if (d_yc) (void)hipFree(d_yc);
-    };
     const size_t nf = sf.size() + ef.size() + pf.size();
-    if (dalloc(&d_in, 6 * n) != hipSuccess || dalloc(&d_f, nf) != hipSuccess || dalloc(&d_out, n) != hipSuccess ||
-        dalloc(&d_yc, 2 * n) != hipSuccess) {
-        cleanup();
-        return fail(AVR_ERR_HIP, "avr_flip: allocation failed");
-    }
     std::vector<float> filt(nf);
     std::copy(sf.begin(), sf.end(), filt.begin());
     std::copy(ef.begin(), ef.end(), filt.begin() + sf.size());
     std::copy(pf.begin(), pf.end(), filt.begin() + sf.size() + ef.size());
-    hipError_t e = hipMemcpyAsync(d_in, test, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in + 3 * n, ref, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_f, filt.data(), nf * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_flip_prep, dim3(blocks_for((long long)n)), dim3(256), 0, c->stream, d_in, d_in + 3 * n,
-                           (int)n, d_yc, d_yc + n);
-        hipLaunchKernelGGL(avr::k_flip_error, dim3(blocks_for((long long)n)), dim3(256), 0, c->stream, d_yc, d_yc + n,
-                           width, height, d_f, rs, d_f + sf.size(), d_f + sf.size() + ef.size(), rd, cmax, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(error, d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("avr_flip: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rIn = scratch.reserve<float>(6 * n), rF = scratch.reserve<float>(nf), rOut = scratch.reserve<float>(n);
+    const auto rYc = scratch.reserve<avr::flip::F4>(2 * n);
+    HIP_TRY(scratch.commit());
+    float *d_in = scratch.get(rIn), *d_f = scratch.get(rF), *d_out = scratch.get(rOut);
+    avr::flip::F4 *d_yc = scratch.get(rYc);
+    HIP_TRY(hipMemcpyAsync(d_in, test, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_in + 3 * n, ref, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_f, filt.data(), nf * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_flip_prep, dim3(blocks_for((long long)n)), dim3(256), 0, c->stream, d_in, d_in + 3 * n,
+                       (int)n, d_yc, d_yc + n);
+    hipLaunchKernelGGL(avr::k_flip_error, dim3(blocks_for((long long)n)), dim3(256), 0, c->stream, d_yc, d_yc + n, width,
+                       height, d_f, rs, d_f + sf.size(), d_f + sf.size() + ef.size(), rd, cmax, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(error, d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -2469,16 +2375,16 @@ int avr_last_pass_samples(avr_context *c, float *L, float *lambda, float *pdf, l
         return fail(AVR_ERR_STATE, "the pixel order changed since the last render (its records are in the old order)");
     if (n > 0 && c->last.persistent) {
         // k_paths' records (L), its camera stage's wavelengths and their pdfs as k_film evaluates them
-        HIP_TRY(hipMemcpy(L, c->set.rec, n * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(lambda, c->set.cam2, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(L, c->set.rec.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(lambda, c->set.cam2.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
         {
             avr::DevFilm f = c->film;
-            hipLaunchKernelGGL(avr::k_lambda_pdfs, dim3(blocks_for(n)), dim3(256), 0, c->stream, f, c->set.cam2, c->set.cam4, n,
+            hipLaunchKernelGGL(avr::k_lambda_pdfs, dim3(blocks_for(n)), dim3(256), 0, c->stream, f, c->set.cam2.get(), c->set.cam4.get(), n,
                                c->last.fast ? 1 : 0);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        HIP_TRY(hipMemcpy(pdf, c->set.cam4, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pdf, c->set.cam4.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
         if (!c->h_pix_slot.empty()) {   // slot order -> pixel order
             const long long np = (long long)c->film.bw * c->film.bh;
             std::vector<float> tmp(4 * (size_t)np);
@@ -2516,7 +2422,7 @@ int avr_last_pass_weights(avr_context *c, float *w, long long n_max) {
         for (long long i = 0; i < n; ++i) w[i] = 1.f;   // BoxFilter::Sample weight
     } else if (n > 0 && c->last.persistent) {
         std::vector<float> camw((size_t)n);
-        HIP_TRY(hipMemcpy(camw.data(), c->set.camw, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(camw.data(), c->set.camw.get(), n * sizeof(float), hipMemcpyDeviceToHost));
         const long long np = (long long)c->film.bw * c->film.bh;
         for (long long i = 0; i < n; ++i)
             w[i] = camw[c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]];
@@ -2538,8 +2444,8 @@ int avr_last_pass_rays(avr_context *c, float *o3, float *d3, float *u, long long
     if (n <= 0) return AVR_OK;
     // the camera stage's records: cam0 {o after interface_entry, u}, cam1 {d, .}
     std::vector<float> cam0(4 * (size_t)n), cam1(4 * (size_t)n);
-    HIP_TRY(hipMemcpy(cam0.data(), c->set.cam0, n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cam1.data(), c->set.cam1, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cam0.data(), c->set.cam0.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cam1.data(), c->set.cam1.get(), n * sizeof(float4), hipMemcpyDeviceToHost));
     const long long np = (long long)c->film.bw * c->film.bh;
     for (long long i = 0; i < n; ++i) {
         const size_t src = (size_t)(c->h_pix_slot.empty() ? i : (i / np) * np + c->h_pix_slot[(size_t)(i % np)]);
@@ -2618,7 +2524,7 @@ int avr_film_reduce_rccl(avr_context **ctxs, int n, int root) {
     for (int i = 0; i < n; ++i) {
         (void)hipSetDevice(devs[i]);
         const hipError_t ei = hipStreamSynchronize(ctxs[i]->stream);
-        if (e == hipSuccess) e = ei;
+        if (e == hipSuccess) e = ei;   // (every rank's stream is drained; the first error is kept)
     }
     if (r != ncclSuccess) return fail(AVR_ERR_HIP, std::string("film reduce: ") + ncclGetErrorString(r));
     if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("film reduce: ") + hipGetErrorString(e));
@@ -2629,6 +2535,14 @@ int avr_film_reduce_rccl(avr_context **ctxs, int n, int root) {
 
 #include "avr_graph_capi.hip"
 
+// Not part of include/avr.h: the device memory this process holds through the library's buffers
+// and scratch arenas, in bytes and in blocks (the tests' leak check)
+extern "C" int avr_debug_live_device_bytes(unsigned long long *bytes, unsigned long long *blocks) {
+    if (bytes) *bytes = avr::devmem::g_live_bytes.load();
+    if (blocks) *blocks = avr::devmem::g_live_blocks.load();
+    return AVR_OK;
+}
+
 #if defined(AVR_PROFILE_SECTIONS) || defined(AVR_PROBE_STATS)
 // Variant builds only (not part of include/avr.h): read and clear the k_paths section cycles
 // (or, with AVR_PROBE_STATS, the walk / gather probe counters)
@@ -2637,8 +2551,8 @@ extern "C" int avr_debug_sections(avr_context *c, unsigned long long *out) {
     if (!c || !out) return fail(AVR_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, c->d_stats + avr::kNumStats, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(c->d_stats + avr::kNumStats, 0, 8 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpy(out, c->d_stats.get() + avr::kNumStats, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(c->d_stats.get() + avr::kNumStats, 0, 8 * sizeof(unsigned long long)));
     return AVR_OK;
 }
 #endif

@@ -16,7 +16,7 @@ int graph_params(avr_context *c, const avr_graph_sampling *s, unsigned long long
     if (s->resolution_x <= 0) return fail(AVR_ERR_ARG, "resolution_x must be positive");
     *p = avr::Params{};
     p->med = c->med;
-    p->stats = c->d_stats;
+    p->stats = c->d_stats.get();
     p->seed = s->seed;
     p->sampler_kind = s->sampler;
     if (s->sampler == 1) {
@@ -88,26 +88,21 @@ int ensure_graph_index(avr_context *c, const avr_graph_index *idx) {
     if (c->gidx_uid == idx->uid) return AVR_OK;
     // queued kernels may still read the previous copy
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_gidx) (void)hipFree(c->d_gidx);
-    c->d_gidx = nullptr;
+    c->d_gidx.reset();
     c->gidx_uid = 0;
     const avr::graph::IndexView h = idx->ix.View();
     const size_t n = idx->ix.NumVertices(), cells = idx->ix.NumCells();
     auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t szRec = pad(n * sizeof(avr::graph::IndexRec)), szId = pad(n * sizeof(int));
     const size_t szStart = pad((cells + 1) * sizeof(int)), szRange = h.range2 ? pad(n * sizeof(float)) : 0;
-    HIP_TRY(dalloc(&c->d_gidx, szRec + szId + szStart + szRange));
-    char *d = c->d_gidx;
-    hipError_t e = hipMemcpy(d, h.rec, n * sizeof(avr::graph::IndexRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + szRec, h.id, n * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + szRec + szId, h.cell_start, (cells + 1) * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess && h.range2)
-        e = hipMemcpy(d + szRec + szId + szStart, h.range2, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_gidx);
-        c->d_gidx = nullptr;
-        return fail(AVR_ERR_HIP, std::string("graph index upload: ") + hipGetErrorString(e));
-    }
+    Buffer<char> buf;   // the context's only once every part is there
+    HIP_TRY(buf.alloc(szRec + szId + szStart + szRange));
+    char *d = buf.get();
+    HIP_TRY(hipMemcpy(d, h.rec, n * sizeof(avr::graph::IndexRec), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + szRec, h.id, n * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + szRec + szId, h.cell_start, (cells + 1) * sizeof(int), hipMemcpyHostToDevice));
+    if (h.range2) HIP_TRY(hipMemcpy(d + szRec + szId + szStart, h.range2, n * sizeof(float), hipMemcpyHostToDevice));
+    c->d_gidx = std::move(buf);
     c->gidx = h;
     c->gidx.rec = (const avr::graph::IndexRec *)d;
     c->gidx.id = (const int *)(d + szRec);
@@ -133,20 +128,16 @@ int ensure_graph_uniform(avr_context *c, const avr_graph_uniform *u) {
     if (c->guni_uid == u->uid) return AVR_OK;
     // queued kernels may still read the previous copy
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_guni) (void)hipFree(c->d_guni);
-    c->d_guni = nullptr;
+    c->d_guni.reset();
     c->guni_uid = 0;
     const avr::graph::UniformView h = u->u.View();
     const size_t cap = u->u.Capacity();
-    HIP_TRY(dalloc(&c->d_guni, cap));
-    const hipError_t e = hipMemcpy(c->d_guni, h.tab, cap * sizeof(avr::graph::UniformEntry), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_guni);
-        c->d_guni = nullptr;
-        return fail(AVR_ERR_HIP, std::string("graph uniform upload: ") + hipGetErrorString(e));
-    }
+    Buffer<avr::graph::UniformEntry> tab;   // the context's only once it is filled
+    HIP_TRY(tab.alloc(cap));
+    HIP_TRY(hipMemcpy(tab.get(), h.tab, cap * sizeof(avr::graph::UniformEntry), hipMemcpyHostToDevice));
+    c->d_guni = std::move(tab);
     c->guni = h;
-    c->guni.tab = c->d_guni;
+    c->guni.tab = c->d_guni.get();
     c->guni_uid = u->uid;
     return AVR_OK;
 }
@@ -170,22 +161,20 @@ int avr_graph_start_rays(avr_context *c, const float bounds_center[3], float max
     if (!bounds_center || !in_dir || !type || !o || !t_first) return fail(AVR_ERR_ARG, "null buffer");
     HIP_TRY(hipSetDevice(c->device));
     const long long n = (long long)steps * steps;
-    char *buf = nullptr;
-    const size_t szT = (size_t)n * 4, szO = (size_t)n * 12;
-    HIP_TRY(dalloc(&buf, 2 * szT + szO));
-    int *dTy = (int *)buf;
-    float *dT = (float *)(buf + szT), *dO = (float *)(buf + 2 * szT);
+    Arena<> scratch(c->stream);
+    const auto rTy = scratch.reserve<int>((size_t)n);
+    const auto rT = scratch.reserve<float>((size_t)n), rO = scratch.reserve<float>(3 * (size_t)n);
+    HIP_TRY(scratch.commit());
+    int *dTy = scratch.get(rTy);
+    float *dT = scratch.get(rT), *dO = scratch.get(rO);
     const avr::V3 ctr = {bounds_center[0], bounds_center[1], bounds_center[2]}, dir = {in_dir[0], in_dir[1], in_dir[2]};
     AVR_GRAPH_LAUNCH_G(avr::k_graph_start_rays, graph_interface(c), blocks_for(n, 256, 256 * 64), c->med, ctr,
                        max_dist_to_center, dir, steps, dTy, dO, dT);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(type, dTy, szT, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(o, dO, szO, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t_first, dT, szT, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph start rays: ") + hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(type, dTy, rTy.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(o, dO, rO.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(t_first, dT, rT.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -215,31 +204,27 @@ int avr_graph_walks_from(avr_context *c, const avr_graph_sampling *s, long long 
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const int md = std::max(max_depth, 1);
-    char *buf = nullptr;
-    const size_t szRay = (size_t)n_rays * 3 * sizeof(float), szT = (size_t)n_rays * sizeof(float);
-    const size_t szI = (size_t)n_rays * sizeof(long long), szP = (size_t)nPaths * md * 3 * sizeof(float);
-    const size_t szC = (size_t)nPaths * sizeof(int);
-    HIP_TRY(dalloc(&buf, 2 * szRay + szT + szI + szP + szC + 64));
-    float *dO = (float *)buf, *dD = (float *)(buf + szRay), *dT = (float *)(buf + 2 * szRay);
-    long long *dI = (long long *)(buf + ((2 * szRay + szT + 7) & ~(size_t)7));
-    float *dP = (float *)((char *)dI + szI);
-    int *dC = (int *)((char *)dP + szP);
-    hipError_t e = hipMemcpyAsync(dO, o, szRay, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dD, d, szRay, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dT, t_first, szT, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dI, index0, szI, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        const int blocks = blocks_for(nPaths, 256, 256 * 64);
-        AVR_GRAPH_LAUNCH_ZG(avr::k_graph_walks, p.sampler_kind == 1, graph_interface(c), blocks, p, nPaths, iterations, dO,
-                            dD, dT, dI, sample_index, skip_dims, s->resolution_x, max_depth, dP, dC);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && max_depth > 0) e = hipMemcpyAsync(points, dP, szP, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, dC, szC, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph walks: ") + hipGetErrorString(e));
+    const size_t nR = (size_t)n_rays, nP = (size_t)nPaths;
+    Arena<> scratch(c->stream);
+    const auto rO = scratch.reserve<float>(3 * nR), rD = scratch.reserve<float>(3 * nR), rT = scratch.reserve<float>(nR);
+    const auto rI = scratch.reserve<long long>(nR);
+    const auto rP = scratch.reserve<float>(nP * md * 3);
+    const auto rC = scratch.reserve<int>(nP);
+    HIP_TRY(scratch.commit());
+    float *dO = scratch.get(rO), *dD = scratch.get(rD), *dT = scratch.get(rT), *dP = scratch.get(rP);
+    long long *dI = scratch.get(rI);
+    int *dC = scratch.get(rC);
+    HIP_TRY(hipMemcpyAsync(dO, o, rO.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dD, d, rD.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dT, t_first, rT.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dI, index0, rI.bytes(), hipMemcpyHostToDevice, c->stream));
+    const int blocks = blocks_for(nPaths, 256, 256 * 64);
+    AVR_GRAPH_LAUNCH_ZG(avr::k_graph_walks, p.sampler_kind == 1, graph_interface(c), blocks, p, nPaths, iterations, dO, dD,
+                        dT, dI, sample_index, skip_dims, s->resolution_x, max_depth, dP, dC);
+    HIP_TRY(hipGetLastError());
+    if (max_depth > 0) HIP_TRY(hipMemcpyAsync(points, dP, rP.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts, dC, rC.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -260,28 +245,25 @@ int avr_graph_reinforce_rays(avr_context *c, const avr_graph_sampling *s, int n,
     int rc = graph_params(c, s, (unsigned long long)(maxId + 1) * (unsigned long long)n_rays, cycle, &p);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    char *buf = nullptr;
-    const size_t szI = (size_t)n * 4, szP = (size_t)n * 12, szR = (size_t)nr * 12, szT = (size_t)nr * 4;
-    HIP_TRY(dalloc(&buf, szI + szP + 2 * szR + 2 * szT));
-    int *dId = (int *)buf;
-    float *dPt = (float *)(buf + szI), *dO = (float *)(buf + szI + szP), *dD = (float *)(buf + szI + szP + szR);
-    float *dT = (float *)(buf + szI + szP + 2 * szR);
-    int *dV = (int *)(buf + szI + szP + 2 * szR + szT);
-    hipError_t e = hipMemcpyAsync(dId, vertex_ids, szI, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dPt, points, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        AVR_GRAPH_LAUNCH_ZG(avr::k_graph_reinforce_rays, p.sampler_kind == 1, graph_interface(c), (n + 255) / 256, p, n, dId,
-                            dPt, vertex_radius, n_rays, cycle, s->resolution_x, dO, dD, dT, dV);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(o, dO, szR, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, dD, szR, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t_first, dT, szT, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(valid, dV, szT, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph reinforce rays: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rId = scratch.reserve<int>((size_t)n);
+    const auto rPt = scratch.reserve<float>(3 * (size_t)n);
+    const auto rO = scratch.reserve<float>(3 * (size_t)nr), rD = scratch.reserve<float>(3 * (size_t)nr);
+    const auto rT = scratch.reserve<float>((size_t)nr);
+    const auto rV = scratch.reserve<int>((size_t)nr);
+    HIP_TRY(scratch.commit());
+    int *dId = scratch.get(rId), *dV = scratch.get(rV);
+    float *dPt = scratch.get(rPt), *dO = scratch.get(rO), *dD = scratch.get(rD), *dT = scratch.get(rT);
+    HIP_TRY(hipMemcpyAsync(dId, vertex_ids, rId.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dPt, points, rPt.bytes(), hipMemcpyHostToDevice, c->stream));
+    AVR_GRAPH_LAUNCH_ZG(avr::k_graph_reinforce_rays, p.sampler_kind == 1, graph_interface(c), (n + 255) / 256, p, n, dId,
+                        dPt, vertex_radius, n_rays, cycle, s->resolution_x, dO, dD, dT, dV);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(o, dO, rO.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(d, dD, rD.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(t_first, dT, rT.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(valid, dV, rV.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -301,22 +283,21 @@ int avr_graph_light(avr_context *c, const avr_graph_sampling *s, int n_vertices,
     // tr scratch: at most 2^28 estimates per chunk of vertices (1 GiB)
     const long long perV = (long long)maxPts * iterations;
     const int chunk = (int)std::max<long long>(1, std::min<long long>(n_vertices, (1ll << 28) / perV));
-    float *dV = nullptr, *dL = nullptr, *dTr = nullptr;
-    avr::graph::DiskRec *dRec = nullptr;
-    int *dN = nullptr;
-    hipError_t e = dalloc(&dV, (size_t)n_vertices * 3);
-    if (e == hipSuccess) e = dalloc(&dL, (size_t)n_vertices);
-    if (e == hipSuccess) e = dalloc(&dRec, (size_t)n_vertices * maxPts);
-    if (e == hipSuccess) e = dalloc(&dN, (size_t)n_vertices);
-    if (e == hipSuccess) e = dalloc(&dTr, (size_t)chunk * perV);
-    if (e == hipSuccess) e = hipMemcpyAsync(dV, vertices, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    Arena<> scratch(c->stream);
+    const auto rV = scratch.reserve<float>((size_t)n_vertices * 3), rL = scratch.reserve<float>((size_t)n_vertices);
+    const auto rRec = scratch.reserve<avr::graph::DiskRec>((size_t)n_vertices * maxPts);
+    const auto rN = scratch.reserve<int>((size_t)n_vertices);
+    const auto rTr = scratch.reserve<float>((size_t)chunk * perV);
+    HIP_TRY(scratch.commit());
+    float *dV = scratch.get(rV), *dL = scratch.get(rL), *dTr = scratch.get(rTr);
+    avr::graph::DiskRec *dRec = scratch.get(rRec);
+    int *dN = scratch.get(rN);
+    HIP_TRY(hipMemcpyAsync(dV, vertices, rV.bytes(), hipMemcpyHostToDevice, c->stream));
     const avr::V3 dir = {in_dir[0], in_dir[1], in_dir[2]};
-    if (e == hipSuccess) {
-        AVR_GRAPH_LAUNCH_G(avr::k_graph_disk, graph_interface(c), (n_vertices + 255) / 256, c->med, n_vertices, dV, dir,
-                           sphere_radius, points_on_radius, max_dist_to_center, maxPts, dRec, dN);
-        e = hipGetLastError();
-    }
-    for (int v0 = 0; e == hipSuccess && v0 < n_vertices; v0 += chunk) {
+    AVR_GRAPH_LAUNCH_G(avr::k_graph_disk, graph_interface(c), (n_vertices + 255) / 256, c->med, n_vertices, dV, dir,
+                       sphere_radius, points_on_radius, max_dist_to_center, maxPts, dRec, dN);
+    HIP_TRY(hipGetLastError());
+    for (int v0 = 0; v0 < n_vertices; v0 += chunk) {
         const int nv = std::min(chunk, n_vertices - v0);
         const long long n = (long long)nv * perV;
         const int blocks = blocks_for(n, 256, 256 * 64);
@@ -326,17 +307,13 @@ int avr_graph_light(avr_context *c, const avr_graph_sampling *s, int n_vertices,
         else
             hipLaunchKernelGGL(avr::k_graph_tr<false>, dim3(blocks), dim3(256), 0, c->stream, p, v0, nv, maxPts, iterations,
                                dir, s->resolution_x, dRec, dN, dTr);
-        e = hipGetLastError();
-        if (e != hipSuccess) break;
+        HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(avr::k_graph_average, dim3((nv + 255) / 256), dim3(256), 0, c->stream, v0, nv, maxPts,
                            iterations, dRec, dN, dTr, dL);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(light, dL, (size_t)n_vertices * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(dV); (void)hipFree(dL); (void)hipFree(dRec); (void)hipFree(dN); (void)hipFree(dTr);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph light: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(light, dL, rL.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -346,39 +323,36 @@ int avr_graph_propagate_device(avr_context *c, int n, long long nnz, const int *
     if (n == 0) { if (iterations) *iterations = bounces; return AVR_OK; }
     if (!row_ptr || !light || !total || (nnz > 0 && (!col || !val))) return fail(AVR_ERR_ARG, "null buffer");
     HIP_TRY(hipSetDevice(c->device));
-    float *buf = nullptr;
-    int *flags = nullptr;
-    HIP_TRY(dalloc(&buf, (size_t)2 * n));
-    hipError_t e = dalloc(&flags, (size_t)std::max(bounces, 1));
-    float *cur = buf, *next = buf + n;
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, sizeof(int) * std::max(bounces, 1), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(total, light, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cur, light, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    // (the scratch is freed after the stream drains: the caller's `total` is complete then)
+    Arena<> scratch(c->stream);
+    const auto rCur = scratch.reserve<float>((size_t)n), rNext = scratch.reserve<float>((size_t)n);
+    const auto rFlags = scratch.reserve<int>((size_t)std::max(bounces, 1));
+    HIP_TRY(scratch.commit());
+    float *cur = scratch.get(rCur), *next = scratch.get(rNext);
+    int *flags = scratch.get(rFlags);
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int) * std::max(bounces, 1), c->stream));
+    HIP_TRY(hipMemcpyAsync(total, light, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(cur, light, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     const int blocks = blocks_for(n, 256, 256 * 64);
-    for (int it = 0; e == hipSuccess && it < bounces; ++it) {
+    for (int it = 0; it < bounces; ++it) {
         hipLaunchKernelGGL(avr::k_graph_spmv, dim3(blocks), dim3(256), 0, c->stream, n, row_ptr, col, val, cur, next,
                            total, flags, it);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
         std::swap(cur, next);
     }
-    if (e == hipSuccess && bounces > 0) {
+    if (bounces > 0) {
         hipLaunchKernelGGL(avr::k_graph_accumulate, dim3(blocks), dim3(256), 0, c->stream, n, cur, total, flags, bounces);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess && iterations) {
+    if (iterations) {
         std::vector<int> h(std::max(bounces, 1));
-        e = hipMemcpyAsync(h.data(), flags, sizeof(int) * h.size(), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        HIP_TRY(hipMemcpyAsync(h.data(), flags, sizeof(int) * h.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         int done = bounces;
         for (int j = 0; j < bounces; ++j)
             if (h[j]) { done = j; break; }
         *iterations = done;
     }
-    // the scratch is freed after the stream drains (hipFree synchronises the device)
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    (void)hipFree(flags);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph propagate: ") + hipGetErrorString(e));
     return AVR_OK;
 }
 
@@ -397,23 +371,21 @@ int avr_graph_propagate(avr_context *c, int n, const int *row_ptr, const int *co
         }
     }
     HIP_TRY(hipSetDevice(c->device));
-    char *buf = nullptr;
-    const size_t szR = (size_t)(n + 1) * 4, szE = (size_t)nnz * 4, szN = (size_t)n * 4;
-    HIP_TRY(dalloc(&buf, szR + 2 * szE + 2 * szN));
-    int *dR = (int *)buf, *dC = (int *)(buf + szR);
-    float *dVal = (float *)(buf + szR + szE), *dL = (float *)(buf + szR + 2 * szE), *dT = (float *)(buf + szR + 2 * szE + szN);
-    hipError_t e = hipMemcpyAsync(dR, row_ptr, szR, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(dC, col, szE, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(dVal, val, szE, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dL, light, szN, hipMemcpyHostToDevice, c->stream);
-    int rc = AVR_OK;
-    if (e == hipSuccess) rc = avr_graph_propagate_device(c, n, nnz, dR, dC, dVal, dL, bounces, dT, iterations);
-    if (e == hipSuccess && rc == AVR_OK) e = hipMemcpyAsync(total, dT, szN, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && rc == AVR_OK) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
+    Arena<> scratch(c->stream);
+    const auto rR = scratch.reserve<int>((size_t)n + 1), rC = scratch.reserve<int>((size_t)nnz);
+    const auto rVal = scratch.reserve<float>((size_t)nnz), rL = scratch.reserve<float>((size_t)n);
+    const auto rT = scratch.reserve<float>((size_t)n);
+    HIP_TRY(scratch.commit());
+    int *dR = scratch.get(rR), *dC = scratch.get(rC);
+    float *dVal = scratch.get(rVal), *dL = scratch.get(rL), *dT = scratch.get(rT);
+    HIP_TRY(hipMemcpyAsync(dR, row_ptr, rR.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (nnz) HIP_TRY(hipMemcpyAsync(dC, col, rC.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (nnz) HIP_TRY(hipMemcpyAsync(dVal, val, rVal.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dL, light, rL.bytes(), hipMemcpyHostToDevice, c->stream));
+    const int rc = avr_graph_propagate_device(c, n, nnz, dR, dC, dVal, dL, bounces, dT, iterations);
     if (rc) return rc;
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph propagate: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(total, dT, rT.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -522,26 +494,27 @@ int merge_assign_device(avr_context *c, const avr::graph::MergeGrid &mg, std::ve
     if (n == 0) return AVR_OK;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
-    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t szRec = pad(E * sizeof(avr::graph::MergeRec)), szMask = pad(nw * 8), szStart = pad((cells + 1) * 4);
-    const size_t szN = pad((size_t)n * 4), szCnt = pad(nw * 4);
     constexpr int kCtr = 256;   // one counter per round, zeroed kCtr at a time; the last takes the scan's total
-    char *buf = nullptr;
-    HIP_TRY(dalloc(&buf, 2 * szRec + szMask + szStart + 5 * szN + szCnt + kCtr * 4));
-    char *d = buf;
-    auto take = [&d](size_t b) { char *p = d; d += b; return p; };
-    auto *dRec = (avr::graph::MergeRec *)take(szRec), *dEnt = (avr::graph::MergeRec *)take(szRec);
-    auto *dMask = (unsigned long long *)take(szMask);
-    int *dStart = (int *)take(szStart), *dPrev = (int *)take(szN), *dState = (int *)take(szN);
-    int *dWork[2] = {(int *)take(szN), (int *)take(szN)};
-    int *dIds = (int *)take(szN), *dCnt = (int *)take(szCnt), *dCtr = (int *)take(kCtr * 4);
-    hipError_t e = hipMemcpyAsync(dRec, h.rec, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dEnt, h.ent, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dStart, h.cell_start, (cells + 1) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dPrev, h.prev, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dWork[0], mg.Work().data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dState, 0xff, (size_t)n * 4, c->stream);   // kMergeUndecided
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    Arena<> scratch(c->stream);
+    const auto rRec = scratch.reserve<avr::graph::MergeRec>(E), rEnt = scratch.reserve<avr::graph::MergeRec>(E);
+    const auto rMask = scratch.reserve<unsigned long long>(nw);
+    const auto rStart = scratch.reserve<int>(cells + 1), rPrev = scratch.reserve<int>((size_t)n);
+    const auto rState = scratch.reserve<int>((size_t)n);
+    const auto rWork0 = scratch.reserve<int>((size_t)n), rWork1 = scratch.reserve<int>((size_t)n);
+    const auto rIds = scratch.reserve<int>((size_t)n), rCnt = scratch.reserve<int>(nw), rCtr = scratch.reserve<int>(kCtr);
+    HIP_TRY(scratch.commit());
+    avr::graph::MergeRec *dRec = scratch.get(rRec), *dEnt = scratch.get(rEnt);
+    unsigned long long *dMask = scratch.get(rMask);
+    int *dStart = scratch.get(rStart), *dPrev = scratch.get(rPrev), *dState = scratch.get(rState);
+    int *dWork[2] = {scratch.get(rWork0), scratch.get(rWork1)};
+    int *dIds = scratch.get(rIds), *dCnt = scratch.get(rCnt), *dCtr = scratch.get(rCtr);
+    HIP_TRY(hipMemcpyAsync(dRec, h.rec, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dEnt, h.ent, E * sizeof(avr::graph::MergeRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dStart, h.cell_start, (cells + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dPrev, h.prev, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dWork[0], mg.Work().data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(dState, 0xff, (size_t)n * 4, c->stream));   // kMergeUndecided
+    HIP_TRY(hipStreamSynchronize(c->stream));
     *ms_upload = ms_since(t0);
     avr::graph::MergeView dv = h;
     dv.rec = dRec;
@@ -550,46 +523,35 @@ int merge_assign_device(avr_context *c, const avr::graph::MergeGrid &mg, std::ve
     dv.prev = dPrev;
     // one sweep per launch over the points still open; the host reads the count after each
     int left = n, r = 0, cur = 0;
-    bool stuck = false;
-    while (e == hipSuccess && left > 0) {
+    while (left > 0) {
         int now = 0;
         int *ctr = dCtr + r % (kCtr - 1);
-        if (r % (kCtr - 1) == 0) e = hipMemsetAsync(dCtr, 0, kCtr * 4, c->stream);
-        if (e != hipSuccess) break;
+        if (r % (kCtr - 1) == 0) HIP_TRY(hipMemsetAsync(dCtr, 0, kCtr * 4, c->stream));
         if (left <= kMergeWaveBelow)
             hipLaunchKernelGGL(avr::k_graph_merge_round_wave, dim3(blocks_for(left, 4, 256 * 64)), dim3(256), 0, c->stream,
                                dv, dState, dWork[cur], left, dWork[cur ^ 1], ctr);
         else
             hipLaunchKernelGGL(avr::k_graph_merge_round, dim3(blocks_for(left, 256, 256 * 64)), dim3(256), 0, c->stream, dv,
                                dState, dWork[cur], left, dWork[cur ^ 1], ctr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&now, ctr, 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) break;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&now, ctr, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         ++r;
-        if (now < 0 || now >= left) {   // a round must finalise a point: never loop on a bug
-            stuck = true;
-            break;
-        }
+        // a round must finalise a point: never loop on a bug
+        if (now < 0 || now >= left) return fail(AVR_ERR_INTERNAL, "graph merge: a round finalised no point");
         left = now;
         cur ^= 1;
     }
     int news = 0;
-    if (e == hipSuccess && !stuck) {
-        hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
-                           dState, dMask, dCnt);
-        hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dCtr + kCtr - 1);
-        hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
-                           dState, dMask, dCnt, dIds);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(ids->data(), dIds, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&news, dCtr + kCtr - 1, 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph merge: ") + hipGetErrorString(e));
-    if (stuck) return fail(AVR_ERR_INTERNAL, "graph merge: a round finalised no point");
+    hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
+                       dState, dMask, dCnt);
+    hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dCtr + kCtr - 1);
+    hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, h.v0, n,
+                       dState, dMask, dCnt, dIds);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ids->data(), dIds, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&news, dCtr + kCtr - 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     *rounds = r;
     *new_vertices = news;
     return AVR_OK;
@@ -787,23 +749,19 @@ int avr_graph_connect(avr_context *c, const avr_graph_index *idx, long long n, c
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_graph_index(c, idx);
     if (rc) return rc;
-    char *buf = nullptr;
-    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
-    HIP_TRY(dalloc(&buf, szP + 2 * szL));
-    float *dP = (float *)buf, *dL = (float *)(buf + szP);
-    int *dC = (int *)(buf + szP + szL);
-    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_graph_connect, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n,
-                           dP, dL, dC);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(light_out, dL, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(count_out, dC, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph connect: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rP = scratch.reserve<float>(3 * (size_t)n), rL = scratch.reserve<float>((size_t)n);
+    const auto rC = scratch.reserve<int>((size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dP = scratch.get(rP), *dL = scratch.get(rL);
+    int *dC = scratch.get(rC);
+    HIP_TRY(hipMemcpyAsync(dP, points, rP.bytes(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_graph_connect, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n, dP,
+                       dL, dC);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(light_out, dL, rL.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(count_out, dC, rC.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -823,24 +781,21 @@ int avr_graph_coverage(avr_context *c, const avr_graph_index *idx, long long n, 
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_graph_index(c, idx);
     if (rc) return rc;
-    char *buf = nullptr;
-    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
-    HIP_TRY(dalloc(&buf, szP + 3 * szL));
-    float *dP = (float *)buf, *dS = (float *)(buf + szP + 2 * szL);
-    int *dN = (int *)(buf + szP), *dR = (int *)(buf + szP + szL);
-    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_graph_coverage, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n,
-                           dP, dN, dR, dS);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(node, dN, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(in_range, dR, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(range_sum, dS, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph coverage: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rP = scratch.reserve<float>(3 * (size_t)n);
+    const auto rN = scratch.reserve<int>((size_t)n), rR = scratch.reserve<int>((size_t)n);
+    const auto rS = scratch.reserve<float>((size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dP = scratch.get(rP), *dS = scratch.get(rS);
+    int *dN = scratch.get(rN), *dR = scratch.get(rR);
+    HIP_TRY(hipMemcpyAsync(dP, points, rP.bytes(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_graph_coverage, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->gidx, n, dP,
+                       dN, dR, dS);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(node, dN, rN.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(in_range, dR, rR.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(range_sum, dS, rS.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -863,43 +818,31 @@ int graph_knn_device(avr_context *c, const avr_graph_index *idx, int k, int *ids
     int rc = ensure_graph_index(c, idx);
     if (rc) return rc;
     const int n = (int)idx->ix.NumVertices();
-    const size_t szK = (size_t)n * (size_t)k * 4, szN = (size_t)n * 4;
-    char *buf = nullptr;
-    HIP_TRY(dalloc(&buf, 2 * szK + 2 * szN));
-    int *dIds = (int *)buf;
-    float *dD2 = (float *)(buf + szK), *dAvg = (float *)(buf + 2 * szK), *dRange = (float *)(buf + 2 * szK + szN);
+    Arena<> scratch(c->stream);
+    const auto rIds = scratch.reserve<int>((size_t)n * (size_t)k);
+    const auto rD2 = scratch.reserve<float>((size_t)n * (size_t)k);
+    const auto rAvg = scratch.reserve<float>((size_t)n), rRange = scratch.reserve<float>((size_t)n);
+    HIP_TRY(scratch.commit());
+    int *dIds = scratch.get(rIds);
+    float *dD2 = scratch.get(rD2), *dAvg = scratch.get(rAvg), *dRange = scratch.get(rRange);
     const int blocks = blocks_for(n, 256, 256 * 64);
     // the kernels' times go to avr_stats: k_graph_knn to ms_medium, k_graph_range_average to ms_film
-    int ev[3] = {-1, -1, -1};
-    rc = next_event(c, &ev[0]);
-    hipError_t e = hipSuccess;
-    if (rc == AVR_OK) {
-        hipLaunchKernelGGL(avr::k_graph_knn, dim3(blocks), dim3(256), 0, c->stream, c->gidx, n, k, dIds, dD2,
-                           ranges ? dAvg : nullptr);
-        e = hipGetLastError();
-    }
-    if (rc == AVR_OK && e == hipSuccess) rc = next_event(c, &ev[1]);
-    if (rc == AVR_OK && e == hipSuccess && ranges) {
+    EV_MARK(ev0);
+    hipLaunchKernelGGL(avr::k_graph_knn, dim3(blocks), dim3(256), 0, c->stream, c->gidx, n, k, dIds, dD2,
+                       ranges ? dAvg : nullptr);
+    HIP_TRY(hipGetLastError());
+    EV_MARK(ev1);
+    c->timed.push_back({ev0, ev1, &avr_stats::ms_medium, true});
+    if (ranges) {
         hipLaunchKernelGGL(avr::k_graph_range_average, dim3(blocks), dim3(256), 0, c->stream, n, k, dIds, dAvg, dRange);
-        e = hipGetLastError();
-        if (e == hipSuccess) rc = next_event(c, &ev[2]);
+        HIP_TRY(hipGetLastError());
+        EV_MARK(ev2);
+        c->timed.push_back({ev1, ev2, &avr_stats::ms_film, false});
     }
-    if (rc != AVR_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(buf);
-        return rc;
-    }
-    if (e == hipSuccess) {
-        c->timed.push_back({ev[0], ev[1], &avr_stats::ms_medium, true});
-        if (ranges) c->timed.push_back({ev[1], ev[2], &avr_stats::ms_film, false});
-    }
-    if (e == hipSuccess && ids) e = hipMemcpyAsync(ids, dIds, szK, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && d2) e = hipMemcpyAsync(d2, dD2, szK, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && ranges) e = hipMemcpyAsync(ranges, dRange, szN, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph knn: ") + hipGetErrorString(e));
+    if (ids) HIP_TRY(hipMemcpyAsync(ids, dIds, rIds.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (d2) HIP_TRY(hipMemcpyAsync(d2, dD2, rD2.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (ranges) HIP_TRY(hipMemcpyAsync(ranges, dRange, rRange.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -973,15 +916,15 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
             return fail(AVR_ERR_ARG, "graph analyze: the detail buffer (" + std::to_string(need) + " pass samples x max_depth " +
                                          std::to_string(analyze_depth) + " x 24 B) exceeds the path state's " +
                                          std::to_string(limit) + " B (max_paths x 252 B): lower max_depth or max_paths, or pass detail = 0");
-        if ((rc = grow(c, &c->d_adetail, &c->adetail_cap, (size_t)entries))) return rc;
+        HIP_TRY(c->d_adetail.reserve((size_t)entries, c->stream));
     }
     rc = ensure_paths(c, need);
     if (rc) return rc;
     // (queued kernels may still read the buffer a larger one replaces: grow drains the stream)
-    if ((rc = analyze ? grow(c, &c->d_arec, &c->arec_cap, need) : grow(c, &c->d_gside, &c->gside_cap, need))) return rc;
+    HIP_TRY(analyze ? c->d_arec.reserve((size_t)need, c->stream) : c->d_gside.reserve((size_t)need, c->stream));
     if (analyze && !c->d_aacc) {
-        HIP_TRY(dalloc(&c->d_aacc, (size_t)P));
-        HIP_TRY(hipMemsetAsync(c->d_aacc, 0, (size_t)P * sizeof(avr::graph::AnalyzeAcc), c->stream));
+        HIP_TRY(c->d_aacc.alloc((size_t)P));
+        HIP_TRY(hipMemsetAsync(c->d_aacc.get(), 0, (size_t)P * sizeof(avr::graph::AnalyzeAcc), c->stream));
     }
     EV_MARK(evStart);
     for (long long base = spp_begin; base < spp_end; base += Smax) {
@@ -998,24 +941,24 @@ int graph_passes(avr_context *c, const avr_graph_index *idx, const float graph_f
         // one lane per camera record, as many blocks as records up to 64 per CU's worth
         const int nb = blocks_for(n0, 256, 256 * 64);
         if (analyze) {
-            avr::graph::AnalyzeDetail *det = detail ? c->d_adetail : nullptr;
+            avr::graph::AnalyzeDetail *det = detail ? c->d_adetail.get() : nullptr;
             AVR_GRAPH_LAUNCH_ZG(avr::k_graph_analyze, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
-                                analyze_depth, c->d_arec, det);
+                                analyze_depth, c->d_arec.get(), det);
         } else if (uni) {
             if (view) AVR_GRAPH_LAUNCH_ZGV(avr::k_graph_render_uniform, c->sampler_kind != 0, graph_interface(c), 1, nb, p,
-                                           c->guni, xf, light_scale, c->d_gside);
+                                           c->guni, xf, light_scale, c->d_gside.get());
             else AVR_GRAPH_LAUNCH_ZGV(avr::k_graph_render_uniform, c->sampler_kind != 0, graph_interface(c), 0, nb, p,
-                                      c->guni, xf, light_scale, c->d_gside);
+                                      c->guni, xf, light_scale, c->d_gside.get());
         } else {
             AVR_GRAPH_LAUNCH_ZG(avr::k_graph_render, c->sampler_kind != 0, graph_interface(c), nb, p, c->gidx, xf,
-                                c->d_gside);
+                                c->d_gside.get());
         }
         HIP_TRY(hipGetLastError());
         EV_MARK(m1);
         c->timed.push_back({c1, m1, &avr_stats::ms_medium, true});
         if (analyze) {
             hipLaunchKernelGGL(avr::k_graph_analyze_reduce, dim3(blocks_for(P)), dim3(256), 0, c->stream, (int)P, S,
-                               c->d_arec, c->d_aacc);
+                               c->d_arec.get(), c->d_aacc.get());
             HIP_TRY(hipGetLastError());
             EV_MARK(f1);
             c->timed.push_back({m1, f1, &avr_stats::ms_film, false});
@@ -1080,7 +1023,7 @@ int avr_graph_analysis_clear(avr_context *c) {
     if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
     if (!c->d_aacc) return AVR_OK;   // nothing analysed on this film yet: the sums start at zero
     const size_t np = (size_t)c->film.bw * c->film.bh;
-    HIP_TRY(hipMemsetAsync(c->d_aacc, 0, np * sizeof(avr::graph::AnalyzeAcc), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_aacc.get(), 0, np * sizeof(avr::graph::AnalyzeAcc), c->stream));
     return AVR_OK;
 }
 
@@ -1090,7 +1033,7 @@ int avr_graph_analysis_read(avr_context *c, unsigned long long *total, unsigned 
     if (!c || !c->has_film) return fail(AVR_ERR_STATE, "no film");
     const size_t np = (size_t)c->film.bw * c->film.bh;
     std::vector<avr::graph::AnalyzeAcc> h(np, avr::graph::AnalyzeAcc{0, 0, 0, 0, 0.0});
-    if (c->d_aacc) HIP_TRY(hipMemcpy(h.data(), c->d_aacc, np * sizeof(avr::graph::AnalyzeAcc), hipMemcpyDeviceToHost));
+    if (c->d_aacc) HIP_TRY(hipMemcpy(h.data(), c->d_aacc.get(), np * sizeof(avr::graph::AnalyzeAcc), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < np; ++i) {
         if (total) total[i] = h[i].total;
         if (node) node[i] = h[i].node;
@@ -1126,13 +1069,13 @@ int avr_graph_analyze_last_pass(avr_context *c, float *o, float *d, int *counts,
         }
     }
     std::vector<avr::graph::AnalyzeRec> rec((size_t)n);
-    HIP_TRY(hipMemcpy(rec.data(), c->d_arec, (size_t)n * sizeof(avr::graph::AnalyzeRec), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rec.data(), c->d_arec.get(), (size_t)n * sizeof(avr::graph::AnalyzeRec), hipMemcpyDeviceToHost));
     if (counts)
         for (long long i = 0; i < n; ++i) counts[i] = rec[(size_t)i].total;
     if (md == 0 || (!points && !node && !in_range && !range_sum)) return AVR_OK;
     const size_t entries = (size_t)n * (size_t)md;
     std::vector<avr::graph::AnalyzeDetail> det(entries);
-    HIP_TRY(hipMemcpy(det.data(), c->d_adetail, entries * sizeof(avr::graph::AnalyzeDetail), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(det.data(), c->d_adetail.get(), entries * sizeof(avr::graph::AnalyzeDetail), hipMemcpyDeviceToHost));
     for (long long i = 0; i < n; ++i)
         for (int k = 0; k < md; ++k) {
             const size_t e = (size_t)i * (size_t)md + (size_t)k;
@@ -1159,7 +1102,7 @@ int avr_graph_last_pass(avr_context *c, float *o, float *d, float *points, int *
     if (n_max < n) return fail(AVR_ERR_ARG, "buffer too small for the last pass");
     if (n == 0) return AVR_OK;
     std::vector<float4> h((size_t)n);
-    const float4 *src[3] = {c->ps.o, c->ps.d, c->d_gside};
+    const float4 *src[3] = {c->ps.o, c->ps.d, c->d_gside.get()};
     float *dst[3] = {o, d, points};
     for (int k = 0; k < 3; ++k) {
         if (!dst[k] && !(k == 2 && counts)) continue;
@@ -1242,23 +1185,19 @@ int avr_graph_uniform_lookup_device(avr_context *c, const avr_graph_uniform *u, 
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_graph_uniform(c, u);
     if (rc) return rc;
-    char *buf = nullptr;
-    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
-    HIP_TRY(dalloc(&buf, szP + 2 * szL));
-    float *dP = (float *)buf, *dL = (float *)(buf + szP);
-    int *dI = (int *)(buf + szP + szL);
-    hipError_t e = hipMemcpyAsync(dP, points, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_graph_uniform_lookup, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni,
-                           n, dP, dI, dL);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(light_out, dL, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(id_out, dI, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform lookup: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rP = scratch.reserve<float>(3 * (size_t)n), rL = scratch.reserve<float>((size_t)n);
+    const auto rI = scratch.reserve<int>((size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dP = scratch.get(rP), *dL = scratch.get(rL);
+    int *dI = scratch.get(rI);
+    HIP_TRY(hipMemcpyAsync(dP, points, rP.bytes(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_graph_uniform_lookup, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni, n,
+                       dP, dI, dL);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(light_out, dL, rL.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(id_out, dI, rI.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -1270,26 +1209,22 @@ int avr_graph_uniform_trace_device(avr_context *c, const avr_graph_uniform *u, l
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_graph_uniform(c, u);
     if (rc) return rc;
-    char *buf = nullptr;
-    const size_t szP = (size_t)n * 3 * sizeof(float), szL = (size_t)n * sizeof(float);
-    HIP_TRY(dalloc(&buf, 2 * szP + 3 * szL));
-    float *dO = (float *)buf, *dD = (float *)(buf + szP), *dH0 = (float *)(buf + 2 * szP + szL),
-          *dH1 = (float *)(buf + 2 * szP + 2 * szL);
-    int *dI = (int *)(buf + 2 * szP);
-    hipError_t e = hipMemcpyAsync(dO, o, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dD, d, szP, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(avr::k_graph_uniform_trace, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni,
-                           n, dO, dD, dI, dH0, dH1);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(id_out, dI, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hit0, dH0, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hit1, dH1, szL, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform trace: ") + hipGetErrorString(e));
+    Arena<> scratch(c->stream);
+    const auto rO = scratch.reserve<float>(3 * (size_t)n), rD = scratch.reserve<float>(3 * (size_t)n);
+    const auto rI = scratch.reserve<int>((size_t)n);
+    const auto rH0 = scratch.reserve<float>((size_t)n), rH1 = scratch.reserve<float>((size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dO = scratch.get(rO), *dD = scratch.get(rD), *dH0 = scratch.get(rH0), *dH1 = scratch.get(rH1);
+    int *dI = scratch.get(rI);
+    HIP_TRY(hipMemcpyAsync(dO, o, rO.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dD, d, rD.bytes(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(avr::k_graph_uniform_trace, dim3(blocks_for(n, 256, 256 * 64)), dim3(256), 0, c->stream, c->guni, n,
+                       dO, dD, dI, dH0, dH1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(id_out, dI, rI.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hit0, dH0, rH0.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hit1, dH1, rH1.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AVR_OK;
 }
 
@@ -1312,28 +1247,26 @@ int avr_graph_capture(avr_context *c, int n_bundles, const float *origin, const 
     }
     HIP_TRY(hipSetDevice(c->device));
     const long long n = side * side * n_bundles;
-    char *buf = nullptr;
-    const size_t szB = (size_t)n_bundles * 3 * sizeof(float), szO = (size_t)n * sizeof(float4);
-    HIP_TRY(dalloc(&buf, szO + 4 * szB + 16));
-    float4 *dOut = (float4 *)buf;
-    float *dB = (float *)(buf + szO);
-    int *dN = (int *)(buf + szO + 4 * szB);
+    const size_t szB = (size_t)n_bundles * 3 * sizeof(float);
+    int nCap = 0;   // (before the arena: copied into until the arena's drain)
+    Arena<> scratch(c->stream);
+    const auto rOut = scratch.reserve<float4>((size_t)n);
+    const auto rB = scratch.reserve<float>((size_t)12 * n_bundles);   // origin | dir | xvec | yvec
+    const auto rN = scratch.reserve<int>(1);
+    HIP_TRY(scratch.commit());
+    float4 *dOut = scratch.get(rOut);
+    float *dB = scratch.get(rB);
+    int *dN = scratch.get(rN);
     const float *src[4] = {origin, dir, xvec, yvec};
-    hipError_t e = hipMemsetAsync(dN, 0, sizeof(int), c->stream);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(dB + (size_t)k * 3 * n_bundles, src[k], szB, hipMemcpyHostToDevice, c->stream);
-    int nCap = 0;
-    if (e == hipSuccess) {
-        AVR_GRAPH_LAUNCH_G(avr::k_graph_capture, graph_interface(c), blocks_for(n, 256, 256 * 64), c->med, n, num_steps, dB,
-                           dB + (size_t)3 * n_bundles, dB + (size_t)6 * n_bundles, dB + (size_t)9 * n_bundles, dOut, dN);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_points4, dOut, szO, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&nCap, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(dN, 0, sizeof(int), c->stream));
+    for (int k = 0; k < 4; ++k)
+        HIP_TRY(hipMemcpyAsync(dB + (size_t)k * 3 * n_bundles, src[k], szB, hipMemcpyHostToDevice, c->stream));
+    AVR_GRAPH_LAUNCH_G(avr::k_graph_capture, graph_interface(c), blocks_for(n, 256, 256 * 64), c->med, n, num_steps, dB,
+                       dB + (size_t)3 * n_bundles, dB + (size_t)6 * n_bundles, dB + (size_t)9 * n_bundles, dOut, dN);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_points4, dOut, rOut.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&nCap, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     *n_captured = nCap;
     return AVR_OK;
 }
@@ -1353,43 +1286,38 @@ int uniform_points_device(avr_context *c, long long n, const float *xyz, float s
     size_t cap = 16;
     while (cap < 2 * (size_t)n) cap *= 2;
     const size_t nw = ((size_t)n + 63) / 64;
-    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t szX = pad((size_t)n * 12), szK = cap * 8, szF = cap * 4, szS = pad((size_t)n * 4);
-    const size_t szM = pad(nw * 8), szC = pad(nw * 4);
-    char *buf = nullptr;
-    HIP_TRY(dalloc(&buf, szK + szM + szX + szF + 3 * szS + szC + 16));
-    unsigned long long *dKeys = (unsigned long long *)buf, *dMask = (unsigned long long *)(buf + szK);
-    float *dX = (float *)(buf + szK + szM);
-    int *dFirst = (int *)(buf + szK + szM + szX);
-    int *dSlot = (int *)((char *)dFirst + szF), *dState = (int *)((char *)dSlot + szS), *dIds = (int *)((char *)dState + szS);
-    int *dCnt = (int *)((char *)dIds + szS), *dScal = (int *)((char *)dCnt + szC);   // dScal: bad, count, total
-    int scal[3] = {0x7fffffff, 0, 0};
-    hipError_t e = hipMemsetAsync(dKeys, 0xff, szK, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dFirst, 0x7f, szF, c->stream);   // 0x7f7f7f7f: above every index
-    if (e == hipSuccess) e = hipMemcpyAsync(dScal, scal, sizeof scal, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dX, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        const int blocks = blocks_for(n, 256, 256 * 64);
-        hipLaunchKernelGGL(avr::k_graph_uniform_insert, dim3(blocks), dim3(256), 0, c->stream, n, dX, spacing, dKeys,
-                           (uint32_t)(cap - 1), dFirst, dSlot, dScal);
-        hipLaunchKernelGGL(avr::k_graph_uniform_first, dim3(blocks), dim3(256), 0, c->stream, n, dFirst, dSlot, dState,
-                           dScal + 1);
-        if (vertex_of) {
-            hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt);
-            hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dScal + 2);
-            hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt,
-                               dIds);
-        }
-        e = hipGetLastError();
+    const size_t N = (size_t)n, szK = cap * 8, szF = cap * 4;
+    int scal[3] = {0x7fffffff, 0, 0};   // bad, count, total (before the arena: copied into until its drain)
+    Arena<> scratch(c->stream);
+    const auto rKeys = scratch.reserve<unsigned long long>(cap), rMask = scratch.reserve<unsigned long long>(nw);
+    const auto rX = scratch.reserve<float>(3 * N);
+    const auto rFirst = scratch.reserve<int>(cap), rSlot = scratch.reserve<int>(N), rState = scratch.reserve<int>(N);
+    const auto rIds = scratch.reserve<int>(N), rCnt = scratch.reserve<int>(nw), rScal = scratch.reserve<int>(3);
+    HIP_TRY(scratch.commit());
+    unsigned long long *dKeys = scratch.get(rKeys), *dMask = scratch.get(rMask);
+    float *dX = scratch.get(rX);
+    int *dFirst = scratch.get(rFirst), *dSlot = scratch.get(rSlot), *dState = scratch.get(rState);
+    int *dIds = scratch.get(rIds), *dCnt = scratch.get(rCnt), *dScal = scratch.get(rScal);
+    HIP_TRY(hipMemsetAsync(dKeys, 0xff, szK, c->stream));
+    HIP_TRY(hipMemsetAsync(dFirst, 0x7f, szF, c->stream));   // 0x7f7f7f7f: above every index
+    HIP_TRY(hipMemcpyAsync(dScal, scal, sizeof scal, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dX, xyz, N * 12, hipMemcpyHostToDevice, c->stream));
+    const int blocks = blocks_for(n, 256, 256 * 64);
+    hipLaunchKernelGGL(avr::k_graph_uniform_insert, dim3(blocks), dim3(256), 0, c->stream, n, dX, spacing, dKeys,
+                       (uint32_t)(cap - 1), dFirst, dSlot, dScal);
+    hipLaunchKernelGGL(avr::k_graph_uniform_first, dim3(blocks), dim3(256), 0, c->stream, n, dFirst, dSlot, dState,
+                       dScal + 1);
+    if (vertex_of) {
+        hipLaunchKernelGGL(avr::k_graph_merge_flags, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt);
+        hipLaunchKernelGGL(avr::k_graph_merge_scan, dim3(1), dim3(256), 0, c->stream, (int)nw, dCnt, dScal + 2);
+        hipLaunchKernelGGL(avr::k_graph_merge_ids, dim3(blocks), dim3(256), 0, c->stream, 0, (int)n, dState, dMask, dCnt,
+                           dIds);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(scal, dScal, sizeof scal, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(scal, dScal, sizeof scal, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     // an invalid point has no vertex: its id would be read from outside the scan
-    if (e == hipSuccess && vertex_of && scal[0] == 0x7fffffff)
-        e = hipMemcpy(vertex_of, dIds, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph uniform from points: ") + hipGetErrorString(e));
+    if (vertex_of && scal[0] == 0x7fffffff) HIP_TRY(hipMemcpy(vertex_of, dIds, N * 4, hipMemcpyDeviceToHost));
     if (scal[0] != 0x7fffffff)
         return fail(AVR_ERR_ARG, "graph uniform: vertex " + std::to_string(scal[0]) + ": coordinate outside +-2^20");
     *count = scal[1];
@@ -1401,22 +1329,23 @@ int uniform_points_device(avr_context *c, long long n, const float *xyz, float s
 int voxels_flood_device(avr_context *c, avr::graph::Voxels &vx, bool fill, const std::vector<int> &start, int *levels) {
     HIP_TRY(hipSetDevice(c->device));
     const avr::graph::VoxelDims d = vx.Dims();
-    const size_t szS = vx.StateBytes(), szQ = ((size_t)d.cells * 4 + 15) & ~(size_t)15;
-    char *buf = nullptr;
-    HIP_TRY(dalloc(&buf, ((szS + 15) & ~(size_t)15) + 2 * szQ + 16));
-    unsigned *dState = (unsigned *)buf;
-    int *dQ[2] = {(int *)(buf + ((szS + 15) & ~(size_t)15)), nullptr};
-    dQ[1] = (int *)((char *)dQ[0] + szQ);
-    int *dN = (int *)((char *)dQ[1] + szQ);
-    hipError_t e = hipMemcpyAsync(dState, vx.State(), szS, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dQ[0], start.data(), start.size() * 4, hipMemcpyHostToDevice, c->stream);
-    int nFront = (int)start.size(), lv = 0, cur = 0;
+    const size_t szS = vx.StateBytes();
+    int nFront = (int)start.size(), lv = 0, cur = 0;   // (nFront before the arena: copied into until its drain)
+    Arena<> scratch(c->stream);
+    const auto rState = scratch.reserve<unsigned char>(szS);
+    const auto rQ0 = scratch.reserve<int>((size_t)d.cells), rQ1 = scratch.reserve<int>((size_t)d.cells);
+    const auto rN = scratch.reserve<int>(1);
+    HIP_TRY(scratch.commit());
+    unsigned *dState = (unsigned *)scratch.get(rState);
+    int *dQ[2] = {scratch.get(rQ0), scratch.get(rQ1)};
+    int *dN = scratch.get(rN);
+    HIP_TRY(hipMemcpyAsync(dState, vx.State(), szS, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dQ[0], start.data(), start.size() * 4, hipMemcpyHostToDevice, c->stream));
     long long seen = nFront;
     // each cell joins a frontier at most once, so the levels cannot outnumber the cells
-    while (e == hipSuccess && nFront > 0 && lv < d.cells) {
+    while (nFront > 0 && lv < d.cells) {
         ++lv;
-        e = hipMemsetAsync(dN, 0, sizeof(int), c->stream);
-        if (e != hipSuccess) break;
+        HIP_TRY(hipMemsetAsync(dN, 0, sizeof(int), c->stream));
         const int blocks = blocks_for(nFront, 256, 256 * 64);
         if (fill)
             hipLaunchKernelGGL((avr::k_graph_voxels_level<1>), dim3(blocks), dim3(256), 0, c->stream, d, dState, dQ[cur], nFront,
@@ -1424,20 +1353,14 @@ int voxels_flood_device(avr_context *c, avr::graph::Voxels &vx, bool fill, const
         else
             hipLaunchKernelGGL((avr::k_graph_voxels_level<0>), dim3(blocks), dim3(256), 0, c->stream, d, dState, dQ[cur], nFront,
                                dQ[cur ^ 1], dN);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&nFront, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&nFront, dN, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         cur ^= 1;
         seen += nFront;
-        if (e == hipSuccess && (nFront < 0 || seen > d.cells)) {
-            (void)hipFree(buf);
-            return fail(AVR_ERR_HIP, "graph voxels: frontier count out of range");
-        }
+        if (nFront < 0 || seen > d.cells) return fail(AVR_ERR_HIP, "graph voxels: frontier count out of range");
     }
-    if (e == hipSuccess) e = hipMemcpy(vx.State(), dState, szS, hipMemcpyDeviceToHost);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(AVR_ERR_HIP, std::string("graph voxels flood: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(vx.State(), dState, szS, hipMemcpyDeviceToHost));
     if (levels) *levels = lv;
     return AVR_OK;
 }

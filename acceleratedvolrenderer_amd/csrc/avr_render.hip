@@ -34,41 +34,21 @@ static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParam
     size_t prow;
     (void)film_rowmask(c, &prow);
     const size_t need_e = prow * (size_t)c->zs_pdims;
-    // the same headroom policy as the fat / bricked density copies: allocate only with >= 8 GiB
-    // of HBM to spare
-    auto fits = [](size_t bytes) {
-        size_t freeB = 0, totalB = 0;
-        return hipMemGetInfo(&freeB, &totalB) == hipSuccess && bytes + (8ull << 30) < freeB;
-    };
-    if (need_e > c->zs_ptab_cap[buf]) {
-        if (c->d_zs_ptab[buf]) (void)hipFree(c->d_zs_ptab[buf]);
-        c->d_zs_ptab[buf] = nullptr;
-        c->zs_ptab_cap[buf] = 0;
-        if (!fits(need_e * sizeof(uint64_t)) ||
-            hipMalloc((void **)&c->d_zs_ptab[buf], need_e * sizeof(uint64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_zs_ptab[buf] = nullptr;
-            return AVR_OK;
-        }
-        c->zs_ptab_cap[buf] = need_e;
+    // the same headroom policy as the fat / bricked density copies (alloc_if_room); a failed
+    // query of the free memory counts as no room here
+    if (need_e > c->d_zs_ptab[buf].size()) {
+        if (c->d_zs_ptab[buf].alloc_if_room(need_e) != hipSuccess) (void)hipGetLastError();
+        if (!c->d_zs_ptab[buf]) return AVR_OK;
     }
     // two-level build: the plo + 2 table is shared by the four passes whose indices agree above
     // plo + 2 bits; each pass then derives its own from it (not when the caller's passes stride
     // past each other's group: a sample shard's rank would rebuild it for every pass)
     const uint64_t *atab = nullptr;
     if (two_level && plo + 2 <= zs.log2spp) {
-        if (need_e > c->zs_atab_cap) {
-            if (c->d_zs_atab) (void)hipFree(c->d_zs_atab);
-            c->d_zs_atab = nullptr;
-            c->zs_atab_cap = 0;
+        if (need_e > c->d_zs_atab.size()) {
             for (long long &k : c->zs_akey) k = -1;
-            if (!fits(need_e * sizeof(uint64_t)) ||
-                hipMalloc((void **)&c->d_zs_atab, need_e * sizeof(uint64_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                c->d_zs_atab = nullptr;   // no room: one-level build
-            } else {
-                c->zs_atab_cap = need_e;
-            }
+            // (no room: one-level build)
+            if (c->d_zs_atab.alloc_if_room(need_e) != hipSuccess) (void)hipGetLastError();
         }
         if (c->d_zs_atab) {
             const long long key[6] = {base >> (plo + 2), plo, (long long)zs.log2spp, zs.seed,
@@ -79,32 +59,23 @@ static int ptab_build(avr_context *c, hipStream_t s, const avr::smp::ZSobolParam
                 hipLaunchKernelGGL(avr::k_zsobol_pass_table,
                                    dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s, zs,
                                    c->film.x0, c->film.y0, c->film.bw, c->film.bh, c->zs_pdims, plo + 2,
-                                   (base >> (plo + 2)) << (plo + 2), c->d_zs_atab, (const uint64_t *)nullptr,
+                                   (base >> (plo + 2)) << (plo + 2), c->d_zs_atab.get(), (const uint64_t *)nullptr,
                                    avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.bw),
                                    (uint64_t *)nullptr);
                 HIP_TRY(hipGetLastError());
                 for (int k = 0; k < 6; ++k) c->zs_akey[k] = key[k];
             }
-            atab = c->d_zs_atab;
+            atab = c->d_zs_atab.get();
         }
     }
     // the camera stage's six entries per pixel (dimensions 0, 1, 6..9) also as a compact
     // scanline-ordered copy (48 B per pixel), when the table holds them
     const size_t need_c = c->zs_pdims >= 10 ? 6 * (size_t)P : 0;
-    if (need_c > c->zs_ctab_cap[buf]) {
-        if (c->d_zs_ctab[buf]) (void)hipFree(c->d_zs_ctab[buf]);
-        c->d_zs_ctab[buf] = nullptr;
-        c->zs_ctab_cap[buf] = 0;
-        if (hipMalloc((void **)&c->d_zs_ctab[buf], need_c * sizeof(uint64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->d_zs_ctab[buf] = nullptr;   // no room: the camera reads the rows
-        } else {
-            c->zs_ctab_cap[buf] = need_c;
-        }
-    }
-    uint64_t *ctab = need_c ? c->d_zs_ctab[buf] : nullptr;
+    // (no room: the camera reads the rows)
+    if (c->d_zs_ctab[buf].reserve(need_c) != hipSuccess) (void)hipGetLastError();
+    uint64_t *ctab = need_c ? c->d_zs_ctab[buf].get() : nullptr;
     hipLaunchKernelGGL(avr::k_zsobol_pass_table, dim3(blocks_for(P * (c->zs_pdims / 2), 256, 256 * 64)), dim3(256), 0, s,
-                       zs, c->film.x0, c->film.y0, c->film.bw, c->film.bh, c->zs_pdims, plo, base, c->d_zs_ptab[buf], atab,
+                       zs, c->film.x0, c->film.y0, c->film.bw, c->film.bh, c->zs_pdims, plo, base, c->d_zs_ptab[buf].get(), atab,
                        avr::fastdiv_make((uint32_t)(c->zs_pdims / 2)), avr::fastdiv_make((uint32_t)c->film.bw), ctab);
     HIP_TRY(hipGetLastError());
     return AVR_OK;
@@ -117,9 +88,9 @@ static int next_event(avr_context *c, int *idx, hipStream_t s = nullptr) {
         if (rc) return rc;
     }
     if (c->ev_used == c->evpool.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->evpool.push_back(e);
+        avr::devmem::Event e;
+        HIP_TRY(hipEventCreate(&e.h));
+        c->evpool.push_back(std::move(e));
     }
     *idx = (int)c->ev_used++;
     HIP_TRY(hipEventRecord(c->evpool[*idx], s ? s : c->stream));
@@ -162,26 +133,24 @@ static int render_sampler(avr_context *c, int spp_end, int seed, avr::smp::ZSobo
             // a table built ahead reads the pixel table: let it finish, and drop it
             if (c->tstream) HIP_TRY(hipStreamSynchronize(c->tstream));
             c->look.invalidate();
-            if (c->d_zs_table) (void)hipFree(c->d_zs_table);
-            c->d_zs_table = nullptr;
+            c->d_zs_table.reset();
             for (int k = 0; k < 3; ++k) c->zs_key[k] = key[k];
             if (c->zs_dims > 0) {
-                if (hipMalloc((void **)&c->d_zs_table, rows * c->zs_dims * sizeof(uint32_t)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->d_zs_table = nullptr;   // no room: every call computes all digits
+                if (c->d_zs_table.alloc(rows * c->zs_dims) != hipSuccess) {
+                    (void)hipGetLastError();   // no room: every call computes all digits
                 } else {
                     EV_MARK(t0);
                     hipLaunchKernelGGL(avr::k_zsobol_table, dim3(blocks_for((long long)c->film.bw * c->film.bh *
                                                                             c->zs_dims, 256, 256 * 64)),
                                        dim3(256), 0, c->stream, zs, c->film.x0, c->film.y0, c->film.bw, c->film.bh,
-                                       c->zs_dims, c->d_zs_table);
+                                       c->zs_dims, c->d_zs_table.get());
                     HIP_TRY(hipGetLastError());
                     EV_MARK(t1);
                     c->timed.push_back({t0, t1, &avr_stats::ms_setup, false});
                 }
             }
         }
-        zs.upper = c->d_zs_table;
+        zs.upper = c->d_zs_table.get();
         zs.dmax = c->d_zs_table ? c->zs_dims : 0;
     }
     // (padding bytes zeroed too, here and in pass_params: a pass takes camera records made ahead
@@ -229,7 +198,7 @@ static void pass_params(const avr_context *c, const avr::smp::ZSobolParams &zs, 
     p->div_width = avr::fastdiv_make((uint32_t)c->film.bw);
     p->pass_samples = S;
     p->sample_base = (int)base;
-    p->stats = c->d_stats;
+    p->stats = c->d_stats.get();
 }
 
 // ZSobol quads in the camera stage: 4-aligned sample ranges, at most 8 lower base-4 digits
@@ -301,10 +270,9 @@ struct RenderCall {
 static int pass_advance_table(avr_context *c, long long base, int S) {
     // (two entries per sample; no drain of the stream in front of the free: hipFree waits for
     // queued work itself)
-    int rc = grow(c, &c->d_advance, &c->advance_cap, 2 * (long long)S, false);
-    if (rc) return rc;
+    HIP_TRY(c->d_advance.reserve(2 * (size_t)S));
     if (c->sampler_kind == 0) {   // read by the IndependentSampler's camera stage only
-        hipLaunchKernelGGL(avr::k_advance, dim3((S + 255) / 256), dim3(256), 0, c->stream, c->d_advance, (long long)base,
+        hipLaunchKernelGGL(avr::k_advance, dim3((S + 255) / 256), dim3(256), 0, c->stream, c->d_advance.get(), (long long)base,
                            S);
         HIP_TRY(hipGetLastError());
     }
@@ -341,8 +309,8 @@ static int pass_table(avr_context *c, const RenderCall &rc, long long base, int 
         if (!c->d_zs_ptab[buf]) return AVR_OK;
     }
     c->tab_buf = buf;
-    p->zs.ptab = c->d_zs_ptab[buf];
-    p->zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[buf] : nullptr;
+    p->zs.ptab = c->d_zs_ptab[buf].get();
+    p->zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[buf].get() : nullptr;
     p->zs.pdims = c->zs_pdims;
     p->zs.plo = plo;
     *have = true;
@@ -426,8 +394,8 @@ static int pass_build_ahead(avr_context *c, const RenderCall &rc, long long base
         q.pass_gen = (c->pass_gen + 1) & 0x7fffffff;
         q.cam_quad = cam_quad(nb, S, q.zs);
         q.zs = rc.zs;
-        q.zs.ptab = c->d_zs_ptab[tb];
-        q.zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[tb] : nullptr;
+        q.zs.ptab = c->d_zs_ptab[tb].get();
+        q.zs.ctab = c->zs_pdims >= 10 ? c->d_zs_ctab[tb].get() : nullptr;
         q.zs.pdims = c->zs_pdims;
         q.zs.plo = nplo;
         c->alt.point(q);
@@ -458,10 +426,10 @@ static int pass_build_ahead(avr_context *c, const RenderCall &rc, long long base
 static int render_pass_persistent(avr_context *c, const RenderCall &rc, long long base, int S, avr::Params &p) {
     int r = pass_advance_table(c, base, S);
     if (r) return r;
-    p.advance = c->d_advance;
+    p.advance = c->d_advance.get();
     walk_schedule(c, c->refill_min, c->dda_budget, &p.refill_min, &p.dda_budget, &p.refill_batch);   // defaults: measured optima
     p.pass_gen = ++c->pass_gen & 0x7fffffff;
-    p.pix_order = c->d_pix_order;
+    p.pix_order = c->d_pix_order.get();
     p.cam_quad = cam_quad(base, S, p.zs);
     EV_MARK(ec);
     bool have_table, cam_ahead, cam_taken;
@@ -475,7 +443,7 @@ static int render_pass_persistent(avr_context *c, const RenderCall &rc, long lon
     int variant, e1;
     if ((r = pass_kpaths(c, p, cam_next, &variant, &e1))) return r;
     p.rec_mode = 1;   // k_film reads the records k_paths wrote (in slot order)
-    p.pix_slot = c->d_pix_slot;
+    p.pix_slot = c->d_pix_slot.get();
     p.fast = c->render_mode;
     if ((r = launch_film(c, p, c->render_mode != 0, e1))) return r;
     if (spec_next && (r = pass_build_ahead(c, rc, base, S, pcam, cam_next))) return r;
@@ -492,13 +460,13 @@ static int render_pass_persistent(avr_context *c, const RenderCall &rc, long lon
 static int bin_queue(avr_context *c, int nbins, long long count, const int *queue, const int *count_p, const float4 *o,
                      const float4 *d) {
     EV_MARK(s0);
-    HIP_TRY(hipMemsetAsync(c->d_bin_hist, 0, nbins * sizeof(int), c->stream));
+    int *keys = c->d_bin_keys.get(), *hist = c->d_bin_hist.get();
+    HIP_TRY(hipMemsetAsync(hist, 0, nbins * sizeof(int), c->stream));
     const int nbk = blocks_for(count);
-    hipLaunchKernelGGL(avr::k_bin_count, dim3(nbk), dim3(256), 0, c->stream, c->med, queue, count_p, o, d, c->d_bin_keys,
-                       c->d_bin_hist);
-    hipLaunchKernelGGL(avr::k_bin_scan, dim3(1), dim3(1024), 0, c->stream, c->d_bin_hist, nbins);
-    hipLaunchKernelGGL(avr::k_bin_scatter, dim3(nbk), dim3(256), 0, c->stream, queue, count_p, c->d_bin_keys,
-                       c->d_bin_hist, c->d_bin_out);
+    hipLaunchKernelGGL(avr::k_bin_count, dim3(nbk), dim3(256), 0, c->stream, c->med, queue, count_p, o, d, keys, hist);
+    hipLaunchKernelGGL(avr::k_bin_scan, dim3(1), dim3(1024), 0, c->stream, hist, nbins);
+    hipLaunchKernelGGL(avr::k_bin_scatter, dim3(nbk), dim3(256), 0, c->stream, queue, count_p, keys, hist,
+                       c->d_bin_out.get());
     HIP_TRY(hipGetLastError());
     EV_MARK(s1);
     c->timed.push_back({s0, s1, &avr_stats::ms_binning, false});
@@ -513,7 +481,9 @@ static int render_pass_wavefront(avr_context *c, long long base, int S, avr::Par
     int r = launch_camera(c, p);
     if (r) return r;
     c->h_count[0] = (int)n0;
-    HIP_TRY(hipMemcpyAsync(c->d_counts, c->h_count, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    int *const counts = c->d_counts.get();
+    int *const queue[2] = {c->paths.queue[0].get(), c->paths.queue[1].get()};
+    HIP_TRY(hipMemcpyAsync(counts, c->h_count, sizeof(int), hipMemcpyHostToDevice, c->stream));
     const int nbins = 8 * c->med.mres[0] * c->med.mres[1] * c->med.mres[2];
     const bool bin = c->ray_binning && nbins <= 8 * 4096;
     int cur = 0;
@@ -521,27 +491,24 @@ static int render_pass_wavefront(avr_context *c, long long base, int S, avr::Par
     bool first = true;
     while (count > 0) {
         const int nxt = cur ^ 1;
-        HIP_TRY(hipMemsetAsync(c->d_counts + nxt, 0, sizeof(int), c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_counts + 2, 0, sizeof(int), c->stream));
-        p.queue_in = first ? nullptr : c->d_queue[cur];
-        p.count_in = c->d_counts + cur;
-        if (bin && c->bin_cap < n0) {
-            for (int **b : {&c->d_bin_keys, &c->d_bin_out}) {
-                if (*b) (void)hipFree(*b);
-                HIP_TRY(dalloc(b, (size_t)n0));
-            }
-            if (!c->d_bin_hist) HIP_TRY(dalloc(&c->d_bin_hist, (size_t)8 * 4096));
-            c->bin_cap = n0;
+        HIP_TRY(hipMemsetAsync(counts + nxt, 0, sizeof(int), c->stream));
+        HIP_TRY(hipMemsetAsync(counts + 2, 0, sizeof(int), c->stream));
+        p.queue_in = first ? nullptr : queue[cur];
+        p.count_in = counts + cur;
+        if (bin) {
+            HIP_TRY(c->d_bin_keys.reserve((size_t)n0));
+            HIP_TRY(c->d_bin_out.reserve((size_t)n0));
+            if (!c->d_bin_hist) HIP_TRY(c->d_bin_hist.alloc((size_t)8 * 4096));
         }
         // camera rays keep their pixel order (already coherent); later depths are binned
         if (bin && !first) {
-            if ((r = bin_queue(c, nbins, count, c->d_queue[cur], c->d_counts + cur, c->ps.o, c->ps.d))) return r;
-            HIP_TRY(hipMemcpyAsync(c->d_queue[cur], c->d_bin_out, (size_t)count * sizeof(int), hipMemcpyDeviceToDevice,
+            if ((r = bin_queue(c, nbins, count, queue[cur], counts + cur, c->ps.o, c->ps.d))) return r;
+            HIP_TRY(hipMemcpyAsync(queue[cur], c->d_bin_out.get(), (size_t)count * sizeof(int), hipMemcpyDeviceToDevice,
                                    c->stream));
         }
-        p.queue_out = c->d_queue[nxt];
-        p.count_out = c->d_counts + nxt;
-        p.shadow_count = c->d_counts + 2;
+        p.queue_out = queue[nxt];
+        p.count_out = counts + nxt;
+        p.shadow_count = counts + 2;
         const int nb = blocks_for(count);
         EV_MARK(m0);
         if (c->sampler_kind) hipLaunchKernelGGL(avr::k_medium<true>, dim3(nb), dim3(256), 0, c->stream, p);
@@ -552,8 +519,8 @@ static int render_pass_wavefront(avr_context *c, long long base, int S, avr::Par
         p.sh_perm = nullptr;
         if (bin) {
             // the shadow rays k_medium just pushed, binned the same way (read through sh_perm)
-            if ((r = bin_queue(c, nbins, count, nullptr, c->d_counts + 2, c->sh.o, c->sh.d))) return r;
-            p.sh_perm = c->d_bin_out;
+            if ((r = bin_queue(c, nbins, count, nullptr, counts + 2, c->sh.o, c->sh.d))) return r;
+            p.sh_perm = c->d_bin_out.get();
         }
         EV_MARK(m15);
         hipLaunchKernelGGL(avr::k_shadow, dim3(nb), dim3(256), 0, c->stream, p);
@@ -561,7 +528,7 @@ static int render_pass_wavefront(avr_context *c, long long base, int S, avr::Par
         EV_MARK(m2);
         c->timed.push_back({m15, m2, &avr_stats::ms_shadow, false});
         // the queue length decides the next launch: the wavefront organisation syncs here
-        HIP_TRY(hipMemcpyAsync(c->h_count, c->d_counts + nxt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_count, counts + nxt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         count = c->h_count[0];
         cur = nxt;
