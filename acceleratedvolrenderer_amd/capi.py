@@ -110,6 +110,8 @@ SIGNATURES = {
     "avr_set_render_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_record_lookups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
     "avr_density_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p]),
+    "avr_vdb_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, c_float_p,
+                                     c_float_p]),
     "avr_set_ray_binning": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_majorant_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_pass_table_ahead": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -424,6 +426,14 @@ class Context:
         ms = ctypes.c_float(0.0)
         _check(self.lib.avr_density_fetch(self.h, ctypes.c_void_p(d_points), int(n),
                                           ctypes.cast(ctypes.c_void_p(d_out), c_float_p), ctypes.byref(ms)))
+        return float(ms.value)
+
+    def vdb_fetch(self, grid, d_points, n, d_out):
+        """avr_vdb_fetch (grid 0 density, 1 temperature) on device buffers of medium-space float4
+        points; returns the kernel time in ms."""
+        ms = ctypes.c_float(0.0)
+        _check(self.lib.avr_vdb_fetch(self.h, int(grid), ctypes.c_void_p(d_points or None), int(n),
+                                      ctypes.cast(ctypes.c_void_p(d_out or None), c_float_p), ctypes.byref(ms)))
         return float(ms.value)
 
     def set_kernel_mode(self, mode):

@@ -1232,6 +1232,30 @@ int avr_density_fetch(avr_context *c, const void *d_points, long long n, float *
     return AVR_OK;
 }
 
+int avr_vdb_fetch(avr_context *c, int grid, const void *d_points, long long n, float *d_out, float *ms) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_medium || c->med.type != 3) return fail(AVR_ERR_STATE, "vdb fetch needs a NanoVDBMedium");
+    if (grid != 0 && grid != 1) return fail(AVR_ERR_ARG, "vdb fetch: grid must be 0 (density) or 1 (temperature)");
+    if (grid == 1 && !c->d_vdb_slot[1]) return fail(AVR_ERR_STATE, "vdb fetch: the medium has no temperature grid");
+    if (n < 0 || (n > 0 && (!d_points || !d_out))) return fail(AVR_ERR_ARG, "bad vdb fetch batch");
+    HIP_TRY(hipSetDevice(c->device));
+    avr::devmem::Event e0, e1;
+    HIP_TRY(hipEventCreate(&e0.h));
+    HIP_TRY(hipEventCreate(&e1.h));
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 256LL * 64);
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    if (n > 0)
+        hipLaunchKernelGGL(avr::k_vdb_fetch, dim3(blocks), dim3(256), 0, c->stream, grid ? c->med.vdb_temp : c->med.vdb,
+                           (const float4 *)d_points, n, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    HIP_TRY(hipEventSynchronize(e1));
+    float t = 0.f;
+    HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+    if (ms) *ms = t;
+    return AVR_OK;
+}
+
 int avr_set_majorant_res(avr_context *c, const int res[3]) {
     AVR_QUIESCE(c);
     if (!c || !c->has_medium || !res) return fail(AVR_ERR_STATE, "no medium");

@@ -3491,6 +3491,18 @@ __global__ void __launch_bounds__(256) k_density_fetch(DevMedium m, const float4
     }
 }
 
+// A NanoVDB grid's lookup alone: Grid::worldToIndexF then SampleFromVoxels<Tree, 1, false>
+// (media.h:627-636) at a batch of medium-space points, through vdb::sample_world as
+// sample_point (density, the fat copy when it exists) and vdb_emission (temperature) call it.
+// Test probe for the device-built apron / fat copies (avr_vdb_fetch).
+__global__ void __launch_bounds__(256) k_vdb_fetch(vdb::Apron g, const float4 *__restrict__ pts, long long n,
+                                                   float *__restrict__ out) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float4 p = pts[i];
+        out[i] = vdb::sample_world(g, p.x, p.y, p.z);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Integrator::Tr (cpu/integrators.cpp:324-374): ratio-tracking transmittance between
 // points p0 -> p1 in the medium at four given wavelengths; one query per lane. RNG seeded

@@ -81,6 +81,18 @@ int avr_record_lookups(avr_context *ctx, void *d_points, long long cap, void *d_
  * linear layout code as the path kernels) over n unit-box points (device float4), results
  * to d_out (device, n floats); synchronous; *ms = the kernel's HIP-event time. */
 int avr_density_fetch(avr_context *ctx, const void *d_points, long long n, float *d_out, float *ms);
+/* A NanoVDBMedium grid's lookup alone (test probe): grid 0 = density, 1 = temperature. d_points
+ * holds n device float4 medium-space points (what the kernels hand to the grid after
+ * medium_from_render); d_out[i] = Grid::worldToIndexF then SampleFromVoxels<Tree, 1, false>
+ * (media.h:627-636) of point i, through the lookup the path kernels call, so the density grid's
+ * fat copy is read when avr_grid_layout_active says it exists (the temperature grid has the
+ * apron blocks only). Synchronous; *ms = the kernel's HIP-event time (ms may be NULL).
+ * Domain: finite points whose index-space coordinates lie within +-2^24 of the tree's voxels;
+ * farther or non-finite points are the caller's error (the float -> int conversion of the
+ * index is then unspecified). AVR_ERR_STATE: the current medium is not a NanoVDBMedium, or
+ * grid 1 without a temperature grid; AVR_ERR_ARG: another grid, n < 0, a null buffer with
+ * n > 0. n = 0 launches nothing. */
+int avr_vdb_fetch(avr_context *ctx, int grid, const void *d_points, long long n, float *d_out, float *ms);
 /* Render mode for later renders (SURVEY.md §7 "replay / fast"): 0 = replay (default) — the
  * device evaluates log/atanh/cosh/sin/cos by the canonical f64 sequences and FastExp by pbrt's
  * CPU polynomial (util/math.h:450-471), so every sample replays the CPU VolPathIntegrator's bit

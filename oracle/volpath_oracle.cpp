@@ -747,22 +747,33 @@ static inline float Blackbody(float lambda, float T) {
 // Storage here is a hash map from leaf origin to its 512 values (x-major), independent
 // of the device's block-slot layout.
 struct VdbTree {
-    std::unordered_map<uint64_t, const float *> leaves;
+    // An 8^3 block by its block coordinates (x >> 3, y >> 3, z >> 3), all 32 bits of each: a key
+    // packed into fewer bits makes far voxels alias into a block (getValue there is the background)
+    struct Key {
+        int bx, by, bz;
+        Key(int x, int y, int z) : bx(x >> 3), by(y >> 3), bz(z >> 3) {}
+        bool operator==(const Key &o) const { return bx == o.bx && by == o.by && bz == o.bz; }
+    };
+    struct KeyHash {
+        size_t operator()(const Key &k) const {
+            uint64_t h = (uint64_t)(uint32_t)k.bx * 0x9e3779b97f4a7c15ull;
+            h = (h ^ (h >> 29) ^ (uint32_t)k.by) * 0xbf58476d1ce4e5b9ull;
+            h = (h ^ (h >> 32) ^ (uint32_t)k.bz) * 0x94d049bb133111ebull;
+            return (size_t)(h ^ (h >> 31));
+        }
+    };
+    std::unordered_map<Key, const float *, KeyHash> leaves;
     std::vector<float> leafStore;
     std::vector<int> tileBox;      // ox, oy, oz, size per tile
     std::vector<float> tileValue;
     // 8^3 tiles by origin (a dense grid's constant blocks: ~10^5 of them at 1024^3); larger
     // tiles (128^3 / 4096^3 internal-node tiles, few) are searched in tileBox order
-    std::unordered_map<uint64_t, float> tile8;
+    std::unordered_map<Key, float, KeyHash> tile8;
     std::vector<int> bigTiles;     // indices into tileValue of tiles larger than 8^3
     float background = 0;
     int ibbox[6] = {0, 0, 0, -1, -1, -1};
     double matD[12] = {};          // index -> world (3x3 row-major, translation in column 3)
     float invF[9] = {}, vecF[3] = {};
-    static uint64_t Key(int x, int y, int z) {
-        return ((uint64_t)(uint32_t)(x >> 3) & 0x1fffff) | (((uint64_t)(uint32_t)(y >> 3) & 0x1fffff) << 21) |
-               (((uint64_t)(uint32_t)(z >> 3) & 0x1fffff) << 42);
-    }
     float GetValue(int x, int y, int z) const {
         auto it = leaves.find(Key(x, y, z));
         if (it != leaves.end()) return it->second[(x & 7) * 64 + (y & 7) * 8 + (z & 7)];

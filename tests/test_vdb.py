@@ -13,10 +13,13 @@ no reference test or asset exercises NanoVDBMedium: PARITY UNPINNED. What is che
 """
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import vdb_shim   # noqa: E402
 
 from acceleratedvolrenderer_amd import NanoVDBGrid, NanoVDBMedium
 from oracle import binding
@@ -155,69 +158,13 @@ def test_to_grid_medium_is_nanovdb2pbrt_dump():
 
 
 def _slots(grid):
-    """The device's block-slot layout (avr_capi.hip upload_vdb), built here for the
-    host-compiled header test."""
-    boxes = [(o, 8) for o in grid.leaf_origins] + list(zip(grid.tile_origins, grid.tile_sizes))
-    lo = np.min([o for o, _ in boxes], axis=0)
-    hi = np.max([o + s for o, s in boxes], axis=0)
-    nb = (hi - lo) // 8
-    slot = np.full((nb[2], nb[1], nb[0]), np.iinfo(np.int32).min, np.int32)
-    for t, (o, s) in enumerate(zip(grid.tile_origins, grid.tile_sizes)):
-        b = (o - lo) // 8
-        slot[b[2]:b[2] + s // 8, b[1]:b[1] + s // 8, b[0]:b[0] + s // 8] = -(t + 1)
-    for i, o in enumerate(grid.leaf_origins):
-        b = (o - lo) // 8
-        slot[b[2], b[1], b[0]] = i
-    return slot, lo, nb
+    return vdb_shim.slots(grid)
 
 
 @pytest.fixture(scope="module")
 def hdr(tmp_path_factory):
-    d = tmp_path_factory.mktemp("vdb")
-    src = d / "shim.cpp"
-    src.write_text(
-        "#define AVR_HD inline\n"
-        f'#include "{ROOT}/acceleratedvolrenderer_amd/csrc/avr_vdb.h"\n'
-        "using namespace avr::vdb;\n"
-        'extern "C" void sample(const int *slot, const float *leaves, const float *tiles, const int *o, const int *nb,\n'
-        "                       float bg, const float *inv, const float *vec, int n, const float *p, float *out) {\n"
-        "  Grid g{slot, leaves, tiles, o[0], o[1], o[2], nb[0], nb[1], nb[2], bg};\n"
-        "  for (int k = 0; k < 9; ++k) g.inv[k] = inv[k];\n"
-        "  for (int k = 0; k < 3; ++k) g.vec[k] = vec[k];\n"
-        "  for (int i = 0; i < n; ++i) out[i] = sample_world(g, p[3 * i], p[3 * i + 1], p[3 * i + 2]);\n"
-        "}\n"
-        # the apron layout the kernels sample, built on the host exactly as upload_vdb +
-        # k_vdb_apron build it on the device
-        'extern "C" long long sample_apron(const int *slot, const float *leaves, const float *tiles, int ntiles,\n'
-        "                       const int *o, const int *nb, float bg, const float *inv, const float *vec, int n,\n"
-        "                       const float *p, float *out, float *vals, int fat) {\n"
-        "  Grid g{slot, leaves, tiles, o[0], o[1], o[2], nb[0], nb[1], nb[2], bg};\n"
-        "  std::vector<int> aslot; std::vector<long long> list;\n"
-        "  build_apron_slots(slot, nb[0], nb[1], nb[2], tiles, ntiles, bg, aslot, list);\n"
-        "  std::vector<float> consts(tiles, tiles + ntiles); consts.push_back(bg);\n"
-        "  std::vector<float> blocks(list.size() * kApronVals);\n"
-        "  for (std::size_t i = 0; i < list.size(); ++i) {\n"
-        "    const long long e = list[i];\n"
-        "    const int ex = e % (nb[0] + 1), ey = (e / (nb[0] + 1)) % (nb[1] + 1), ez = e / ((nb[0] + 1) * (nb[1] + 1));\n"
-        "    for (int k = 0; k < kApronVals; ++k) blocks[i * kApronVals + k] = apron_value(g, ex, ey, ez, k);\n"
-        "  }\n"
-        "  Apron a{aslot.data(), blocks.data(), consts.data(), o[0], o[1], o[2], nb[0], nb[1], nb[2], bg};\n"
-        "  for (int k = 0; k < 9; ++k) a.inv[k] = inv[k];\n"
-        "  for (int k = 0; k < 3; ++k) a.vec[k] = vec[k];\n"
-        "  std::vector<float> fatv(fat ? list.size() * 512 * 8 : 0);\n"
-        "  for (long long e = 0; e < (long long)fatv.size() / 8; ++e) apron_fat_entry(blocks.data(), e >> 9, (int)(e & 511), &fatv[8 * e]);\n"
-        "  a.fat = fat ? fatv.data() : nullptr;\n"
-        "  for (int i = 0; i < n; ++i) out[i] = sample_world(a, p[3 * i], p[3 * i + 1], p[3 * i + 2]);\n"
-        "  // getValue over the extent +-10 voxels from the apron layout\n"
-        "  long long q = 0;\n"
-        "  for (int z = o[2] - 10; z < o[2] + 8 * nb[2] + 10; ++z)\n"
-        "    for (int y = o[1] - 10; y < o[1] + 8 * nb[1] + 10; ++y)\n"
-        "      for (int x = o[0] - 10; x < o[0] + 8 * nb[0] + 10; ++x) vals[q++] = get_value(a, x, y, z) - get_value(g, x, y, z);\n"
-        "  return (long long)list.size();\n"
-        "}\n")
-    so = d / "shim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", str(src), "-o", str(so)])
-    return ctypes.CDLL(str(so))
+    """csrc/avr_vdb.h compiled for the host (tests/vdb_shim.py)."""
+    return vdb_shim.build(tmp_path_factory.mktemp("vdb"))
 
 
 def test_device_header_equals_oracle(hdr):
