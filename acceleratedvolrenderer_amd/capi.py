@@ -112,6 +112,8 @@ SIGNATURES = {
     "avr_density_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p]),
     "avr_vdb_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, c_float_p,
                                      c_float_p]),
+    "avr_rgbgrid_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, c_float_p, c_float_p, c_float_p, c_float_p,
+                                         c_float_p]),
     "avr_set_ray_binning": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_majorant_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "avr_set_pass_table_ahead": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -435,6 +437,18 @@ class Context:
         _check(self.lib.avr_vdb_fetch(self.h, int(grid), ctypes.c_void_p(d_points or None), int(n),
                                       ctypes.cast(ctypes.c_void_p(d_out or None), c_float_p), ctypes.byref(ms)))
         return float(ms.value)
+
+    def rgbgrid_probe(self, points, lam, outputs=("sigma_a", "sigma_s", "Le")):
+        """avr_rgbgrid_probe: RGBGridMedium::SamplePoint at n render-space points (n, 3) and
+        wavelength sets (n, 4) in nm; returns (sigma_a, sigma_s, Le), each (n, 4) float32, or
+        None for an output not named in `outputs` (passed as NULL)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        lam = np.ascontiguousarray(lam, np.float32).reshape(-1, 4)
+        if len(p) != len(lam):
+            raise ValueError("rgbgrid_probe: one wavelength set per point")
+        out = [np.zeros((len(p), 4), np.float32) if k in outputs else None for k in ("sigma_a", "sigma_s", "Le")]
+        _check(self.lib.avr_rgbgrid_probe(self.h, len(p), _fp(p), _fp(lam), *[_fp(o) for o in out]))
+        return tuple(out)
 
     def set_kernel_mode(self, mode):
         """0 = persistent megakernel (default), 1 = wavefront queues."""

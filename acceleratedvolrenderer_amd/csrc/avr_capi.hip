@@ -1256,6 +1256,31 @@ int avr_vdb_fetch(avr_context *c, int grid, const void *d_points, long long n, f
     return AVR_OK;
 }
 
+int avr_rgbgrid_probe(avr_context *c, long long n, const float *points, const float *lambda, float *sigma_a4,
+                      float *sigma_s4, float *Le4) {
+    AVR_QUIESCE(c);
+    if (!c || !c->has_medium || c->med.type != 4) return fail(AVR_ERR_STATE, "rgbgrid probe needs an RGBGridMedium");
+    if (n < 0 || (n > 0 && (!points || !lambda))) return fail(AVR_ERR_ARG, "bad rgbgrid probe batch");
+    if (n == 0) return AVR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    Arena<> scratch(c->stream);
+    const auto rp = scratch.reserve<float>(3 * (size_t)n), rl = scratch.reserve<float>(4 * (size_t)n);
+    const auto ro = scratch.reserve<float>(12 * (size_t)n);
+    HIP_TRY(scratch.commit());
+    float *dp = scratch.get(rp), *dl = scratch.get(rl), *dout = scratch.get(ro);
+    float *host[3] = {sigma_a4, sigma_s4, Le4}, *dev[3];
+    for (int k = 0; k < 3; ++k) dev[k] = host[k] ? dout + 4 * (size_t)n * k : nullptr;
+    HIP_TRY(hipMemcpyAsync(dp, points, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dl, lambda, 4 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 256LL * 64);
+    hipLaunchKernelGGL(avr::k_rgb_probe, dim3(blocks), dim3(256), 0, c->stream, c->med, dp, dl, n, dev[0], dev[1], dev[2]);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < 3; ++k)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], 4 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AVR_OK;
+}
+
 int avr_set_majorant_res(avr_context *c, const int res[3]) {
     AVR_QUIESCE(c);
     if (!c || !c->has_medium || !res) return fail(AVR_ERR_STATE, "no medium");

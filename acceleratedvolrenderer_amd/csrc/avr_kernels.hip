@@ -3503,6 +3503,24 @@ __global__ void __launch_bounds__(256) k_vdb_fetch(vdb::Apron g, const float4 *_
     }
 }
 
+// RGBGridMedium::SamplePoint alone (media.h:377-403) at a batch of render-space points and
+// wavelength sets, one lane per probe, through sample_point as both kernel organisations call
+// it (emissive = true). pts n*3, lambda n*4; sigma_a / sigma_s / Le n*4 each, any may be null.
+// Test probe (avr_rgbgrid_probe).
+__global__ void __launch_bounds__(256) k_rgb_probe(DevMedium m, const float *__restrict__ pts,
+                                                   const float *__restrict__ lambda, long long n,
+                                                   float *__restrict__ sigma_a, float *__restrict__ sigma_s,
+                                                   float *__restrict__ Le) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const V3 p{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        const Spec lam{lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]};
+        const MediumSample ms = sample_point(m, p, Spec::c(1.f), Spec::c(0.f), Spec::c(0.f), lam, true);
+        if (sigma_a) { sigma_a[4 * i] = ms.sigma_a.v0; sigma_a[4 * i + 1] = ms.sigma_a.v1; sigma_a[4 * i + 2] = ms.sigma_a.v2; sigma_a[4 * i + 3] = ms.sigma_a.v3; }
+        if (sigma_s) { sigma_s[4 * i] = ms.sigma_s.v0; sigma_s[4 * i + 1] = ms.sigma_s.v1; sigma_s[4 * i + 2] = ms.sigma_s.v2; sigma_s[4 * i + 3] = ms.sigma_s.v3; }
+        if (Le) { Le[4 * i] = ms.Le.v0; Le[4 * i + 1] = ms.Le.v1; Le[4 * i + 2] = ms.Le.v2; Le[4 * i + 3] = ms.Le.v3; }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Integrator::Tr (cpu/integrators.cpp:324-374): ratio-tracking transmittance between
 // points p0 -> p1 in the medium at four given wavelengths; one query per lane. RNG seeded

@@ -93,6 +93,18 @@ int avr_density_fetch(avr_context *ctx, const void *d_points, long long n, float
  * grid 1 without a temperature grid; AVR_ERR_ARG: another grid, n < 0, a null buffer with
  * n > 0. n = 0 launches nothing. */
 int avr_vdb_fetch(avr_context *ctx, int grid, const void *d_points, long long n, float *d_out, float *ms);
+/* RGBGridMedium::SamplePoint alone (test probe; no render path uses it): points holds n render-space
+ * points (host, n * 3), lambda their wavelengths in nm (host, n * 4). sigma_a4 / sigma_s4 / Le4
+ * (host, n * 4 each; any may be NULL) receive sigmaScale * the sigma_a / sigma_s lookups (1 where
+ * the medium has no such grid) and LeScale * the Le lookup (0 for a medium that is not emissive)
+ * of media.h:377-403, one device lane per probe through the sample_point both kernel organisations
+ * call: medium_from_render, Bounds3::Offset, then SampledGrid<RGB*Spectrum>::Lookup with the
+ * spectrum sampled per tap. Works the same for avr_medium_rgbgrid and avr_medium_rgbgrid_device
+ * grids. Synchronous. Domain: finite points (any distance from the box: taps outside the grid
+ * convert to 0) and finite wavelengths. AVR_ERR_STATE: the current medium is not an RGBGridMedium;
+ * AVR_ERR_ARG: n < 0, or null points / lambda with n > 0. n = 0 launches nothing. */
+int avr_rgbgrid_probe(avr_context *ctx, long long n, const float *points, const float *lambda, float *sigma_a4,
+                      float *sigma_s4, float *Le4);
 /* Render mode for later renders (SURVEY.md §7 "replay / fast"): 0 = replay (default) — the
  * device evaluates log/atanh/cosh/sin/cos by the canonical f64 sequences and FastExp by pbrt's
  * CPU polynomial (util/math.h:450-471), so every sample replays the CPU VolPathIntegrator's bit

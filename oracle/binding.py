@@ -175,6 +175,8 @@ def lib():
         L.oracle_transmittance4_points.restype = ctypes.c_longlong
         L.oracle_transmittance4_points.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, c_float_p, c_float_p,
                                                    c_float_p, c_float_p, ctypes.c_longlong, c_float_p]
+        L.oracle_medium_sample.argtypes = [ctypes.POINTER(OracleScene), ctypes.c_int, c_float_p, c_float_p, c_float_p,
+                                           c_float_p, c_float_p]
         L.oracle_get_libm.restype = ctypes.c_int
         c_int_p = ctypes.POINTER(ctypes.c_int)
         L.oracle_vdb_create.restype = ctypes.c_void_p
@@ -663,6 +665,18 @@ class OracleRun:
         set_libm(self.libm)
         lib().oracle_transmittance4(ctypes.byref(self.s), len(p0), fp(p0), fp(p1), fp(lam), fp(out))
         return out
+
+    def medium_sample(self, p3, lambda4):
+        """The medium's SamplePoint at n render-space points (n, 3) and wavelength sets (n, 4):
+        (sigma_a, sigma_s, Le), each (n, 4)."""
+        p = np.ascontiguousarray(p3, np.float32).reshape(-1, 3)
+        lam = np.ascontiguousarray(lambda4, np.float32).reshape(-1, 4)
+        if len(p) != len(lam):
+            raise ValueError("medium_sample: one wavelength set per point")
+        out = [np.zeros((len(p), 4), np.float32) for _ in range(3)]
+        set_libm(self.libm)
+        lib().oracle_medium_sample(ctypes.byref(self.s), len(p), fp(p), fp(lam), fp(out[0]), fp(out[1]), fp(out[2]))
+        return tuple(out)
 
     def transmittance4_points(self, p0, p1, lam, cap=1 << 20):
         """transmittance4 and the render-space point of every SamplePoint call, in query order:

@@ -10,6 +10,8 @@ pbrt-v4 sources under /root/reference (oracle/ref/Makefile), runs it and writes
   tests/golden/gaussian_filter_vectors.json    — GaussianFilter::Sample at that module's radii and sigmas
   tests/golden/light_vectors.json              — the reference's light stage at tests/light_cases.py's maps,
       transforms, probes, alias weights, spectra and distant lights
+  tests/golden/rgbgrid_vectors.json            — SampledGrid<RGBUnboundedSpectrum / RGBIlluminantSpectrum>::
+      Lookup(p, convert) and MaxValue(bounds, convert) over tests/rgbgrid_cases.py's colour grids
 The RGB -> spectrum goldens read the sRGB table that the reference's own rgb2spec_opt
 writes into oracle/_ref (Makefile); the table stays there (not committed).
 The spectral tables are published CIE / ITU data as the reference holds them;
@@ -50,6 +52,11 @@ def main():
                                      input=light_cases.harness_light_lines().encode())
     with open(os.path.join(REPO, "tests", "golden", "light_vectors.json"), "wb") as f:
         f.write(lights)
+    import rgbgrid_cases
+    rgbgrid = subprocess.check_output([exe, "--rgbtable", rgbtable, "--rgb-grid"],
+                                      input=rgbgrid_cases.harness_lines().encode())
+    with open(os.path.join(REPO, "tests", "golden", "rgbgrid_vectors.json"), "wb") as f:
+        f.write(rgbgrid)
     print("wrote", len(out), "bytes of golden vectors and", os.path.getsize(tables), "bytes of tables")
 
 

@@ -24,7 +24,9 @@
 //   RGBIlluminantSpectrum, Transform, CoordinateSystem, AliasTable, SpectrumToPhotometric and
 //   BlackbodySpectrum composed as ImageInfiniteLight (lights.h:552-640, lights.cpp:1007-1060), its
 //   Create (lights.cpp:1620-1648), DistantLight::Create (lights.cpp:246-276) and PowerLightSampler
-//   (lightsamplers.cpp:76-96) compose them (--lights).
+//   (lightsamplers.cpp:76-96) compose them (--lights),
+//   SampledGrid<RGBUnboundedSpectrum> and SampledGrid<RGBIlluminantSpectrum>::Lookup(p, convert) /
+//   MaxValue(bounds, convert) as RGBGridMedium uses them (media.h:377-403, media.cpp:364-377) (--rgb-grid).
 // Output: JSON on stdout (golden vectors) and, with --tables <file>, a raw
 // little-endian float32 table file consumed by oracle/ref/gen_golden.py.
 #include <pbrt/util/rng.h>
@@ -458,11 +460,96 @@ static int light_vectors(const char *rgbTablePath, Allocator alloc) {
     return 0;
 }
 
+// --rgb-grid: tests/golden/rgbgrid_vectors.json, the two grids RGBGridMedium is made of
+// (media.h:355-427). Standard input as tests/rgbgrid_cases.py::harness_lines writes it (floats
+// as uint32 bit patterns, one command per line):
+//   lambda n bits(4n)                  the wavelength sets (probe i uses set i mod n)
+//   grid NAME nx ny nz bits(3 nx ny nz)  the voxels' RGB, x fastest
+//   look NAME n bits(3n)               unit-box points: SampledGrid<RGBUnboundedSpectrum> and
+//                                      SampledGrid<RGBIlluminantSpectrum>::Lookup(p, convert), convert =
+//                                      Sample(lambda) as media.h:381-397
+//   max NAME rx ry rz                  SampledGrid<RGBUnboundedSpectrum>::MaxValue(bounds, convert) over
+//                                      the rx x ry x rz cell bounds of media.cpp:364-377, convert = MaxValue()
+static_assert(sizeof(SampledWavelengths) == 2 * NSpectrumSamples * sizeof(Float) && NSpectrumSamples == 4,
+              "SampledWavelengths is {lambda[4], pdf[4]}");
+static int rgb_grid_vectors(const char *rgbTablePath, Allocator alloc) {
+    std::vector<float> zNodes, coeffs;
+    if (!rgbTablePath || !ReadRgbTable(rgbTablePath, zNodes, coeffs)) { fprintf(stderr, "--rgb-grid needs --rgbtable\n"); return 1; }
+    RGBToSpectrumTable table(zNodes.data(), (const RGBToSpectrumTable::CoefficientArray *)coeffs.data());
+    Spectrum d65 = GetNamedSpectrum("stdillum-D65");
+    RGBColorSpace srgb(Point2f(.64, .33), Point2f(.3, .6), Point2f(.15, .06), d65, &table, alloc);
+    struct Grids { SampledGrid<RGBUnboundedSpectrum> u; SampledGrid<RGBIlluminantSpectrum> il; };
+    std::map<std::string, Grids> grids;
+    std::vector<float> lambdas;
+    std::string line, looks, maxes;
+    auto arr = [](const std::vector<float> &v) {
+        std::string o = "[";
+        for (size_t i = 0; i < v.size(); ++i) o += (i ? "," : "") + std::to_string(fb(v[i]));
+        return o + "]";
+    };
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string cmd, name;
+        in >> cmd;
+        if (cmd == "lambda") {
+            size_t n; in >> n;
+            lambdas = read_floats(in, 4 * n);
+        } else if (cmd == "grid") {
+            int nx, ny, nz;
+            in >> name >> nx >> ny >> nz;
+            std::vector<float> rgb = read_floats(in, 3 * (size_t)nx * ny * nz);
+            std::vector<RGBUnboundedSpectrum> u;
+            std::vector<RGBIlluminantSpectrum> il;
+            for (size_t i = 0; i < rgb.size(); i += 3) {   // media.cpp:431-450
+                RGB c(rgb[i], rgb[i + 1], rgb[i + 2]);
+                u.push_back(RGBUnboundedSpectrum(srgb, c));
+                il.push_back(RGBIlluminantSpectrum(srgb, c));
+            }
+            grids[name] = Grids{SampledGrid<RGBUnboundedSpectrum>(u, nx, ny, nz, alloc),
+                                SampledGrid<RGBIlluminantSpectrum>(il, nx, ny, nz, alloc)};
+        } else if (cmd == "look") {
+            size_t n;
+            in >> name >> n;
+            std::vector<float> p = read_floats(in, 3 * n), sig, Le, used;
+            const Grids &g = grids[name];
+            const size_t nl = lambdas.size() / 4;
+            for (size_t i = 0; i < n; ++i) {
+                float lp[8];
+                for (int k = 0; k < 4; ++k) { lp[k] = lambdas[4 * (i % nl) + k]; lp[4 + k] = 1.f; used.push_back(lp[k]); }
+                SampledWavelengths lambda = SampledWavelengths::SampleUniform(0.5f);
+                std::memcpy((void *)&lambda, lp, sizeof(lp));
+                Point3f pt(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+                SampledSpectrum a = g.u.Lookup(pt, [=](RGBUnboundedSpectrum s) { return s.Sample(lambda); });
+                SampledSpectrum e = g.il.Lookup(pt, [=](RGBIlluminantSpectrum s) { return s.Sample(lambda); });
+                for (int k = 0; k < 4; ++k) { sig.push_back(a[k]); Le.push_back(e[k]); }
+            }
+            looks += (looks.empty() ? "" : ",") + ("\"" + name + "\":{\"p\":" + arr(p) + ",\"lambda\":" + arr(used) +
+                                                   ",\"sigma\":" + arr(sig) + ",\"Le\":" + arr(Le) + "}");
+        } else if (cmd == "max") {
+            int rx, ry, rz;
+            in >> name >> rx >> ry >> rz;
+            const Grids &g = grids[name];
+            std::vector<float> out;
+            for (int z = 0; z < rz; ++z)
+                for (int y = 0; y < ry; ++y)
+                    for (int x = 0; x < rx; ++x) {   // MajorantGrid::VoxelBounds (media.h:103-108)
+                        Bounds3f b(Point3f(Float(x) / rx, Float(y) / ry, Float(z) / rz),
+                                   Point3f(Float(x + 1) / rx, Float(y + 1) / ry, Float(z + 1) / rz));
+                        out.push_back(g.u.MaxValue(b, [](RGBUnboundedSpectrum s) { return s.MaxValue(); }));
+                    }
+            maxes += (maxes.empty() ? "" : ",") + ("\"" + name + "@" + std::to_string(rx) + "x" + std::to_string(ry) + "x" +
+                                                   std::to_string(rz) + "\":" + arr(out));
+        }
+    }
+    printf("{\"lookup\":{%s},\"max_value\":{%s}}\n", looks.c_str(), maxes.c_str());
+    return 0;
+}
+
 int main(int argc, char **argv) {
     Allocator alloc;
     Spectra::Init(alloc);
     const char *tablePath = nullptr, *rgbTablePath = nullptr;
-    bool hgEdges = false, filters = false, lights = false;
+    bool hgEdges = false, filters = false, lights = false, rgbGrid = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--tables") && i + 1 < argc) tablePath = argv[++i];
         if (!strcmp(argv[i], "--rgbtable") && i + 1 < argc) rgbTablePath = argv[++i];
@@ -470,8 +557,10 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "--camera-rays")) return camera_rays();
         if (!strcmp(argv[i], "--filters")) filters = true;
         if (!strcmp(argv[i], "--lights")) lights = true;
+        if (!strcmp(argv[i], "--rgb-grid")) rgbGrid = true;
     }
     if (lights) return light_vectors(rgbTablePath, alloc);
+    if (rgbGrid) return rgb_grid_vectors(rgbTablePath, alloc);
     if (filters) {
         // tests/golden/gaussian_filter_vectors.json: the radii and sigmas of tests/camera_cases.py's
         // Gaussian filters (tables that are not square, 128 x 128, 16 x 16, all-zero rows)

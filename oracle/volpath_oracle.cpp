@@ -2346,6 +2346,22 @@ static void Transmittance4(const OracleScene *s, int n, const float *p0, const f
         for (int k = 0; k < NS; ++k) trOut[4 * i + k] = Tr.v[k];
     }
 }
+// The medium's SamplePoint alone (tests): n render-space points and wavelength sets through the
+// SamplePoint the integrator calls; sigma_a / sigma_s / Le, 4 per point
+void oracle_medium_sample(const OracleScene *s, int n, const float *p, const float *lambdas, float *sigma_a,
+                          float *sigma_s, float *Le) {
+    SceneView sv(*s);
+    for (int i = 0; i < n; ++i) {
+        Lambda l;
+        for (int k = 0; k < NS; ++k) { l.lambda[k] = lambdas[4 * i + k]; l.pdf[k] = VisibleWavelengthsPDF(l.lambda[k]); }
+        const MediumProps mp = SamplePoint(sv, {p[3 * i], p[3 * i + 1], p[3 * i + 2]}, l);
+        for (int k = 0; k < NS; ++k) {
+            sigma_a[4 * i + k] = mp.sigma_a.v[k];
+            sigma_s[4 * i + k] = mp.sigma_s.v[k];
+            Le[4 * i + k] = mp.Le.v[k];
+        }
+    }
+}
 void oracle_transmittance4(const OracleScene *s, int n, const float *p0, const float *p1, const float *lambdas,
                            float *trOut) {
     Transmittance4(s, n, p0, p1, lambdas, trOut, 0, nullptr, nullptr);

@@ -1,4 +1,5 @@
-"""Generate tests/golden/srgb_table_subset.npz and srgb_table_subset_lights.npz: the entries of pbrt's sRGB
+"""Generate tests/golden/srgb_table_subset.npz, srgb_table_subset_lights.npz and
+srgb_table_subset_rgbgrid.npz: the entries of pbrt's sRGB
 RGBToSpectrumTable (as the reference's own cmd/rgb2spec_opt generates it: oracle/ref/Makefile
 -> oracle/_ref/srgb_table.inc) that the GPU image-light test's environment map touches,
 every other coefficient zero. The GPU box has no reference sources, so the GPU test reads
@@ -8,8 +9,11 @@ table's here, before the file is written.
 srgb_table_subset_lights.npz holds the cells that the maps of tests/light_cases.py touch (one
 palette of eight colours; grey pixels need no cell), checked in the same way.
 
-usage: python tests/golden/make_srgb_subset.py [envmap] [lights]   (needs oracle/_ref/srgb_table.inc;
-       without an argument both fixtures are written; an .npz holds its time of writing, so write
+srgb_table_subset_rgbgrid.npz holds the cells that the palette of tests/rgbgrid_cases.py touches
+(RGBGridMedium's voxel colours), checked in the same way.
+
+usage: python tests/golden/make_srgb_subset.py [envmap] [lights] [rgbgrid]   (needs oracle/_ref/srgb_table.inc;
+       without an argument the three fixtures are written; an .npz holds its time of writing, so write
        only the one that changed)
 """
 import os
@@ -23,6 +27,7 @@ from acceleratedvolrenderer_amd.rgbspectrum import RGBToSpectrumTable  # noqa: E
 
 OUT = os.path.join(ROOT, "tests", "golden", "srgb_table_subset.npz")
 OUT_LIGHTS = os.path.join(ROOT, "tests", "golden", "srgb_table_subset_lights.npz")
+OUT_RGBGRID = os.path.join(ROOT, "tests", "golden", "srgb_table_subset_rgbgrid.npz")
 
 
 def envmap_image(res=32):
@@ -66,6 +71,13 @@ def light_maps():
     return {name: light_cases.map_image(name) for name in light_cases.MAPS}
 
 
+def rgbgrid_palette():
+    """The voxel colours of tests/rgbgrid_cases.py, as one (n, 1, 3) image."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rgbgrid_cases
+    return rgbgrid_cases.palette_rgb().reshape(-1, 1, 3)
+
+
 def write_subset(full, images, out):
     mask = np.zeros(full.coeffs.shape[:4], bool)
     for img in images:
@@ -81,11 +93,13 @@ def write_subset(full, images, out):
 def main():
     src = os.path.join(ROOT, "oracle", "_ref", "srgb_table.inc")
     full = RGBToSpectrumTable.load(src)
-    which = sys.argv[1:] or ["envmap", "lights"]
+    which = sys.argv[1:] or ["envmap", "lights", "rgbgrid"]
     if "envmap" in which:
         write_subset(full, [envmap_image()], OUT)
     if "lights" in which:
         write_subset(full, list(light_maps().values()), OUT_LIGHTS)
+    if "rgbgrid" in which:
+        write_subset(full, [rgbgrid_palette()], OUT_RGBGRID)
 
 
 if __name__ == "__main__":

@@ -19,7 +19,7 @@ def test_header_declares_the_boundary():
     syms = declared_symbols()
     for must in ("avr_context_create", "avr_medium_grid", "avr_lights", "avr_camera", "avr_film", "avr_render",
                  "avr_film_read", "avr_last_error", "avr_last_pass_rays", "avr_light_probe", "avr_light_pick",
-                 "avr_light_sampler_table"):
+                 "avr_light_sampler_table", "avr_rgbgrid_probe"):
         assert must in syms
 
 

@@ -529,7 +529,10 @@ def test_nanovdb_transmittance_matches_oracle():
 
 def _rgb_coeffs(rng, shape, scale_hi=3.0):
     """Random RGBSigmoidPolynomial coefficients + scale per voxel (any coefficients are a
-    valid RGBUnboundedSpectrum; the RGB->coefficient table is checked in test_rgbgrid.py)."""
+    valid RGBUnboundedSpectrum; the RGB->coefficient table is checked in test_rgbgrid.py).
+    No colour gives these: c2 stays in [-5, 5] and the scale in [0.2, 3]. Converted colours
+    (black = {0, 0, -inf, 0}, greys with c0 = c1 = 0, primaries, HDR scales) run on the device
+    in test_gpu_rgbgrid.py, over the grids of rgbgrid_cases.py."""
     c = np.empty(shape + (4,), np.float32)
     c[..., 0] = rng.uniform(-2e-5, 2e-5, shape)
     c[..., 1] = rng.uniform(-0.02, 0.02, shape)
